@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: image-pairs/sec (640x480, K=512) -- BASELINE.json's metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs-per-gpu B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs-per-gpu B] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline needs and nothing else: set-up, warm-up, EXACTLY K timed steps, the outputs of the
+last timed step written to DIR (--dump-outputs: one DIR/<name>.npy per array the path returns, float32; the inputs are
+seeded, so two builds compare output for output), and the JSON line (metric, value, unit, ms_per_step, ...).  `--full`
+adds everything else the line has carried: the per-kernel times and rooflines, the N = 1 extras, the CPU baseline with
+its live parity check and the side workloads listed below.
 
 Both forms work for N > 1: under torchrun the ranks exist already; a bare `python bench.py --gpus N` starts N fresh rank
 processes itself (launch_ranks) before touching the GPU.  The N > 1 line records the world size the backend actually
@@ -17,7 +23,9 @@ resident in HBM as float32 (the reference's input type), followed (N > 1) by the
 rank 0.  Configuration = BASELINE.json configs[1] hyper-parameters (the export-CLI values) with
 K=512; pairs are independent, so ranks hold different pairs (weak scaling).  Prints ONE JSON line on rank 0.
 
-Beside `value` the line carries (N = 1 only, all measured after the timed region, none of them part of `value`):
+With --full, beside `value` the line carries `kernels` and `roofline_other` (per-stage HIP-event times of three extra
+steps after the timed region), `roofline` (HIP events around K1's calls inside the timed region) and (N = 1 only, all
+measured after the timed region, none of them part of `value`):
   roofline      K1 corner response (the stencil north_star sets the 60 % target on), float32 input, 8 B/px
   u8_ingest     the same workload on uint8 frames resident in HBM (5 B/px K1), with its own roofline object
   p_materialised  the same workload with P written by forward() and read by the extractor (the reference's two modules)
@@ -30,7 +38,7 @@ Beside `value` the line carries (N = 1 only, all measured after the timed region
                 model (vo), 128 pairs per step, ten steps each: value, roofline of the dominant bandwidth-type kernel,
                 per-call times and the workload's own reference CPU path (one pair per call); `--workload c3|c3dense|c4|vo`
                 gives each a full line of its own, `--workload vo --stream` the one-pair-per-call form per rank
-  sinkhorn_schedule  the stream schedule mi_sinkhorn_dots tuned itself to during the untimed steps
+`sinkhorn_schedule`, the stream schedule mi_sinkhorn_dots tuned itself to during the untimed steps, is in every line.
 """
 from __future__ import annotations
 
@@ -178,6 +186,50 @@ def emit(line: dict) -> None:
 def step_stats(per_step_ms: list[float]) -> dict:
     return {"min": min(per_step_ms), "median": statistics.median(per_step_ms), "max": max(per_step_ms),
             "mean": statistics.fmean(per_step_ms)}
+
+
+def synth_frames_u8(first_seed: int, pairs: int, h: int, w: int) -> tuple[np.ndarray, np.ndarray]:
+    """synth_batch_u8(first_seed, pairs, h, w), the same bytes, generated in chunks of pairs on up to 16 threads (pair i
+    depends on its seed alone; numpy's element-wise kernels release the GIL): on one thread the 448-pair batch
+    takes seconds."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from onnx_image_processing_amd.synth import synth_batch_u8
+    n = max(1, min(16, len(os.sched_getaffinity(0)), pairs))
+    bounds = [(i * pairs // n, (i + 1) * pairs // n) for i in range(n)]
+    with ThreadPoolExecutor(n) as ex:
+        parts = list(ex.map(lambda r: synth_batch_u8(first_seed + r[0], r[1] - r[0], h, w), bounds))
+    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, rec: torch.Tensor, essential: bool = False) -> None:
+    """--dump-outputs: the match records the timed path returned in its last timed step (rank 0: every rank's pairs in
+    global order), unpacked into what a caller of the module receives -- matched keypoints of both images, scores and
+    validity (MatchExtractionWrapper), plus E per pair for the VO model -- as DIR/<name>.npy, float32.  Above 64 MB in
+    all, a fixed seeded sample of the pairs is written, with their indices in pair_index.npy."""
+    from onnx_image_processing_amd import distributed as D
+    rec = rec.detach().float().cpu()
+    arrays = {}
+    if essential:                                      # run_side's VO records: two extra rows per pair hold E (9 of 12)
+        arrays["essential_matrix"] = rec[:, -2:].reshape(rec.shape[0], -1)[:, :9].reshape(-1, 3, 3)
+        rec = rec[:, :-2]
+    mk1, mk2, scores, valid = D.unpack_records(rec)
+    arrays = {"matched_keypoints0": mk1, "matched_keypoints1": mk2, "match_scores": scores,
+              "match_valid": valid.float(), **arrays}
+    arrays = {k: np.ascontiguousarray(v.numpy(), dtype=np.float32) for k, v in arrays.items()}
+    pairs = rec.shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = max(1, DUMP_LIMIT_BYTES * 15 // 16 // (total // pairs))
+        idx = np.sort(np.random.default_rng(0).choice(pairs, size=keep, replace=False))
+        arrays = {k: np.ascontiguousarray(a[idx]) for k, a in arrays.items()}
+        arrays["pair_index"] = idx.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
 
 
 def pmc_traffic(kernel_prefix: str, pairs_per_gpu: int, workload: str = "bench"):
@@ -631,17 +683,18 @@ def cpu_baseline_side(name: str, threads: int | None = None) -> dict:
 
 
 def run_side(name: str, B: int, steps: int, warmup: int, rank: int, world: int, dev, two_step: bool = False,
-             forced: bool = False, extras: bool = True, stream: bool = False):
+             forced: bool = False, extras: bool = True, stream: bool = False, full: bool = True, dump: str | None = None):
     """One side workload through the same modules as the default line: returns the JSON line (rank 0; None elsewhere).
+    full: the per-kernel times, the roofline object and (stream) the per-call gather cost beside the headline; dump: the
+    directory --dump-outputs names (the last timed step's records, rank 0).
     stream: the VO model as its host uses it (sample/visual_odometry.py:520-545) -- ONE frame pair per call per rank,
     replayed as a hipGraph, the host synchronised after every call, the call's record (100 matches + E) gathered to
     rank 0 pipelined by one call; `value` = calls per second over all ranks."""
     from onnx_image_processing_amd import _native, distributed as D
     from onnx_image_processing_amd.pytorch_model.feature_detection import MatchExtractionWrapper
-    from onnx_image_processing_amd.synth import synth_batch
     base, h, w, k, what, roof = side_model(name)
     begin, _ = D.shard_range(B * world, rank, world)
-    a, b = synth_batch(1000 + begin, B, h, w)
+    a, b = (x.astype(np.float32) for x in synth_frames_u8(1000 + begin, B, h, w))     # = synth_batch(1000 + begin, B, h, w)
     img1, img2 = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
     del a, b
     gather = PipelinedGather()
@@ -684,19 +737,24 @@ def run_side(name: str, B: int, steps: int, warmup: int, rank: int, world: int, 
             return gather(compute())
 
     join_group(step, gather.drain, world, forced)
-    _native.enable_timing(True, only={roof[0]})
+    if full:
+        _native.enable_timing(True, only={roof[0]})
     elapsed_ms, per_step_ms, out, own_ms = run_timed(step, steps, warmup, world, dev, torch.cuda.synchronize, gather.drain)
     facts = world_facts(own_ms, steps, dev)
-    timed = _native.timings_ms().get(roof[0], [])
-    timed = timed[-len(timed) * steps // (steps + warmup):] if timed else timed     # drop the warm-up calls
-    _native.enable_timing(True)
-    for _ in range(3):
-        step()
-    gather.drain()
-    per_call = _native.timings_ms()
-    _native.enable_timing(False)
+    if dump and rank == 0:
+        dump_outputs(dump, out, essential=name == "vo")
+    timed, per_call = [], {}
+    if full:
+        timed = _native.timings_ms().get(roof[0], [])
+        timed = timed[-len(timed) * steps // (steps + warmup):] if timed else timed     # drop the warm-up calls
+        _native.enable_timing(True)
+        for _ in range(3):
+            step()
+        gather.drain()
+        per_call = _native.timings_ms()
+        _native.enable_timing(False)
     no_gather_ms = None
-    if stream:                                        # the same loop without the gather: what the per-call collective costs
+    if stream and full:                               # the same loop without the gather: what the per-call collective costs
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -717,9 +775,10 @@ def run_side(name: str, B: int, steps: int, warmup: int, rank: int, world: int, 
             "metric": f"image-pairs/sec ({w}x{h}, K={k})", "value": per_step * world / (ms * 1e-3), "unit": "image-pairs/sec",
             "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": ms, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "config": cfg,
-            "step_ms": step_stats(per_step_ms), **facts,
-            "kernels": {kk: {"ms_per_step": float(np.sum(v)) / 3, "calls_per_step": len(v) / 3} for kk, v in per_call.items()}}
-        if stream:
+            "step_ms": step_stats(per_step_ms), **facts}
+        if full:
+            line["kernels"] = {kk: {"ms_per_step": float(np.sum(v)) / 3, "calls_per_step": len(v) / 3} for kk, v in per_call.items()}
+        if stream and full:
             line["stream"] = {"calls_per_sec_per_rank": [1e3 / x for x in facts["ms_per_step_per_rank"]],
                               "ms_per_call_with_gather": ms, "ms_per_call_without_gather_rank0": no_gather_ms,
                               "gather_cost_ms_per_call": ms - no_gather_ms,
@@ -759,12 +818,13 @@ def run_side(name: str, B: int, steps: int, warmup: int, rank: int, world: int, 
 
 
 def side_workload(args, rank, world, dev) -> None:
-    """`--workload c3|c3dense|c4|vo`: BASELINE configs[2]/[3] and the VO model as lines of their own (value, per-call
-    times, the roofline of the dominant bandwidth-type kernel, and -- N = 1 -- the reference CPU path timed beside it)."""
+    """`--workload c3|c3dense|c4|vo`: BASELINE configs[2]/[3] and the VO model as lines of their own (value; with --full
+    per-call times, the roofline of the dominant bandwidth-type kernel, and -- N = 1 -- the reference CPU path timed beside it)."""
     line = run_side(args.workload, args.pairs_per_gpu, args.steps, args.warmup, rank, world, dev, two_step=args.two_step,
-                    forced=getattr(args, "_forced_group", False), extras=not args.no_extras, stream=args.stream)
+                    forced=getattr(args, "_forced_group", False), extras=not args.no_extras, stream=args.stream,
+                    full=args.full, dump=args.dump_outputs)
     if rank == 0:
-        if world == 1 and args.cpu_pairs > 0 and not args.stream:
+        if args.full and world == 1 and args.cpu_pairs > 0 and not args.stream:
             print(f"[bench] cpu_baseline ({args.workload})", file=sys.stderr, flush=True)
             line["cpu_baseline"] = cpu_baseline_side(args.workload)
         emit(line)
@@ -872,6 +932,8 @@ def dry_run(args, rank: int, world: int) -> None:
     if rank == 0:
         ms = elapsed_ms / args.steps
         ordered = bool(torch.equal(out[:, 0, 0], torch.arange(B * world, dtype=torch.float32)))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out)
         emit({"metric": "image-pairs/sec (640x480, K=512)", "value": B * world / (ms * 1e-3),
                           "unit": "image-pairs/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -889,16 +951,24 @@ def dry_run(args, rank: int, world: int) -> None:
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=500,
-                    help="timed steps (default 500: a timed region of about 1.1 s, so that a 2 %% change is not noise)")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps, exactly (default 500: a timed region of about 1.1 s, so that a 2 %% change is not "
+                         "noise; 50 for --workload c3|c3dense|c4|vo, 200 with --stream)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--pairs-per-gpu", type=int, default=448,
                     help="pairs resident per GPU and processed per step (448: the Sinkhorn row kernel's workgroups of "
                          "each half-batch fill whole rounds of the 256 CUs, and top-k runs two workgroups per CU)")
-    ap.add_argument("--cpu-pairs", type=int, default=64, help="pairs of the live match-set parity check (0 = skip cpu_baseline)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, everything else the line can carry: per-kernel times and rooflines, the "
+                         "N = 1 extras, cpu_baseline with its live parity check, side_workloads (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0: all pairs) as "
+                         "DIR/<name>.npy, float32")
+    ap.add_argument("--cpu-pairs", type=int, default=64,
+                    help="with --full: pairs of the live match-set parity check (0 = skip cpu_baseline)")
     ap.add_argument("--no-host-parallel", action="store_true",
-                    help="cpu_baseline without the W one-thread worker processes (W = physical cores)")
-    ap.add_argument("--no-extras", action="store_true", help="skip u8_ingest / streamed / latency (N = 1 extras)")
+                    help="with --full: cpu_baseline without the W one-thread worker processes (W = physical cores)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip u8_ingest / streamed / latency (N = 1 extras)")
     ap.add_argument("--single-call", action="store_true",
                     help="run the step as ONE C-ABI call (mi_match_pairs); informational: no per-stage timers, so the "
                          "line carries no roofline object")
@@ -917,10 +987,13 @@ def main() -> None:
     ap.add_argument("--pin-schedule", type=int, choices=[0, 1, 2], default=None,
                     help="pin mi_sinkhorn_dots' stream schedule on the launch stream instead of letting it tune itself "
                          "(profiling passes: every row-kernel launch then has the same size; mi_sinkhorn_dots_set_schedule)")
-    ap.add_argument("--no-side", action="store_true", help="skip the side_workloads object of the default line (c3, c4, vo)")
+    ap.add_argument("--no-side", action="store_true",
+                    help="with --full: skip the side_workloads object of the default line (c3, c4, vo)")
     ap.add_argument("--dry-run", action="store_true",
                     help="control flow only: stubbed compute on CPU over gloo (tests the N > 1 launcher; not a measurement)")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 500 if args.workload == "c2" else 200 if args.stream else 50
 
     # `python bench.py --gpus N` (N > 1) outside torchrun: start the N ranks ourselves -- BEFORE anything touches the
     # GPU in this process (nothing above does; this process only waits for its children and relays rank 0's line)
@@ -931,7 +1004,6 @@ def main() -> None:
     from onnx_image_processing_amd import _native, distributed as D
     from onnx_image_processing_amd.pytorch_model.feature_detection import (MatchExtractionWrapper,
                                                                            ShiTomasiSparseBADSinkhornMatcher)
-    from onnx_image_processing_amd.synth import synth_batch_u8
 
     # MI_BENCH_FORCE_DIST=1: form the process group even for one rank, so that a one-GPU box runs the N-rank control flow
     # of this script -- barriers, the pipelined RCCL gather of every step's records, the max reduction -- on real RCCL
@@ -983,15 +1055,13 @@ def main() -> None:
 
     B = args.pairs_per_gpu
     if args.workload != "c2":
-        if args.steps == 500:
-            args.steps = 200 if args.stream else 50
         if args.stream and args.pairs_per_gpu == 448:
             args.pairs_per_gpu = 16                              # resident frame pairs the per-call loop cycles through
         return side_workload(args, rank, world, dev)
     if args.stream:
         raise SystemExit("--stream needs --workload vo")
     begin, _ = D.shard_range(B * world, rank, world)            # this rank's pairs in the global order
-    a8, b8 = synth_batch_u8(1000 + begin, B, H, W)
+    a8, b8 = synth_frames_u8(1000 + begin, B, H, W)
     # float32 [0,255] (B,1,H,W): the reference's input form, resident in HBM before timing
     img1, img2 = torch.from_numpy(a8).to(dev).float(), torch.from_numpy(b8).to(dev).float()
     u8_main = args.frames == "u8"
@@ -1008,8 +1078,8 @@ def main() -> None:
         rec = D.pack_records(*(model.forward_single_call(img1, img2) if args.single_call else model(img1, img2)))
         return gather(rec)
 
-    # HIP events around the roofline kernel's calls only (two per step) inside the timed region; the per-stage table
-    # below comes from extra steps after it, so its 24 events per step do not sit in the measurement
+    # --full: HIP events around the roofline kernel's calls only (two per step) inside the timed region; the per-stage
+    # table below comes from extra steps after it, so its 24 events per step do not sit in the measurement
     join_group(step, gather.drain, world, forced)
     # mi_sinkhorn_dots tunes its stream schedule over the first 9 calls of a shape on a stream (3 schedules x 3 trials) and
     # collects the times on the calls after them: enough untimed steps that no trial lands in the timed region, whatever
@@ -1018,15 +1088,18 @@ def main() -> None:
     for _ in range(max(0, 14 - args.warmup - (2 if (world > 1 or forced) else 0))):
         step()
     gather.drain()
-    _native.enable_timing(True, only=None if args.single_call else {"mi_corner_response_pair"})
+    if args.full:
+        _native.enable_timing(True, only=None if args.single_call else {"mi_corner_response_pair"})
     elapsed_ms, per_step, out, own_ms = run_timed(step, args.steps, args.warmup, world, dev, torch.cuda.synchronize, gather.drain)
     schedule = _ops.sinkhorn_schedule(B, K, K, CFG["sinkhorn_iterations"])
     facts = world_facts(own_ms, args.steps, dev)
-    per_call = _native.timings_ms()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    per_call = _native.timings_ms() if args.full else {}
     _native.enable_timing(False)
     stage_steps = 3
     stages = {}
-    if not args.single_call:                                     # per-stage times (informational), outside the timed region
+    if args.full and not args.single_call:                       # per-stage times (informational), outside the timed region
         _native.enable_timing(True)
         for _ in range(stage_steps):
             step()
@@ -1068,9 +1141,10 @@ def main() -> None:
             # the stream schedule mi_sinkhorn_dots measured fastest for this shape on this stream (include/mi355x_match.h:
             # 0 = halves on {stream, helper}, 1 = on two helpers, 2 = unsplit; -1 = still undecided)
             "sinkhorn_schedule": schedule,
-            "kernels": kernels,
         }
-        if not args.single_call:
+        if args.full:
+            line["kernels"] = kernels
+        if args.full and not args.single_call:
             # K1 corner response: 8 algorithmic bytes per pixel (4 read + 4 written); one launch covers BOTH images of
             # every pair of this rank (mi_corner_response_pair: 2 B images), one launch per step
             k1 = per_call["mi_corner_response_pair"][args.warmup:]
@@ -1108,7 +1182,7 @@ def main() -> None:
                     "hbm_frac_of_its_store_stream": 2.0 * B * K * K / (t * 1e-3) / 1e9 / HBM_PEAK_GBS,
                     "note": "bound by its uint16 store stream (2 B per matrix element), not by the matrix pipe; MFMA busy counters in profiles/ (DESIGN.md K5)"}
             line["roofline_other"] = other
-        if world == 1 and not args.single_call and not u8_main:
+        if args.full and world == 1 and not args.single_call and not u8_main:
             records = out[:args.cpu_pairs].cpu().numpy() if 0 < args.cpu_pairs <= B else None
             def stage(name):                                     # progress on stderr: locates a stage that hangs or faults
                 print(f"[bench] {name}", file=sys.stderr, flush=True)

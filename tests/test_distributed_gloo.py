@@ -264,3 +264,50 @@ def test_bench_parent_makes_no_gpu_call_before_launching():
     assert main.index("launch_ranks(") < main.index("torch.cuda.")
     launcher = src[src.index("def launch_ranks"):src.index("def world_facts")]
     assert "torch.cuda" not in launcher and "os.exec" not in src and "execv" not in src
+
+
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs: after the timed steps rank 0 writes the records the last step returned -- every rank's pairs in
+    global order -- unpacked into the wrapper's outputs, one float32 DIR/<name>.npy each; the same arguments give the
+    same arrays from run to run (the stubbed records of the dry run are seeded like the real inputs)."""
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r, lines = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--pairs-per-gpu", "5", "--dry-run",
+                               "--dump-outputs", str(out)])
+        assert r.returncode == 0, r.stderr
+        assert len(lines) == 1 and lines[0]["steps"] == 3 and lines[0]["gathered_in_global_pair_order"] is True
+        dumps.append({p.stem: np.load(p) for p in out.glob("*.npy")})
+    got = dumps[0]
+    assert set(got) == {"matched_keypoints0", "matched_keypoints1", "match_scores", "match_valid"}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["matched_keypoints0"].shape == (10, 100, 2) and got["match_scores"].shape == (10, 100)
+    assert np.array_equal(got["matched_keypoints0"][:, 0, 0], np.arange(10, dtype=np.float32))   # global pair order
+    assert (got["match_valid"] == 1.0).all()
+    assert all(np.array_equal(got[k], dumps[1][k]) for k in got)
+
+
+def test_bench_steps_is_the_number_of_timed_steps():
+    """--steps is taken as given for every workload (a --workload run once turned an explicit 500 into 50); without it
+    each workload has its documented default."""
+    for argv, steps in ((["--workload", "c4", "--steps", "500"], 500), (["--workload", "c4"], 50),
+                        (["--workload", "vo", "--stream"], 200), ([], 500), (["--steps", "4"], 4)):
+        r, lines = _run_bench(["--gpus", "1", "--warmup", "0", "--pairs-per-gpu", "2", "--dry-run", *argv])
+        assert r.returncode == 0, r.stderr
+        assert len(lines) == 1 and lines[0]["steps"] == steps, argv
+
+
+def test_bench_dump_outputs_samples_a_large_output(tmp_path):
+    """Above 64 MB in all, --dump-outputs writes a fixed seeded sample of the pairs with their indices."""
+    sys.path.insert(0, ROOT)
+    import bench
+    pairs = 30000                                          # 30000 x 100 x 6 float32 records: 72 MB unpacked
+    rec = torch.arange(pairs, dtype=torch.float32)[:, None, None].expand(pairs, 100, 6).contiguous()
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), rec)
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    idx = got["pair_index"]
+    assert idx.dtype == np.float64 and 0 < len(idx) < pairs and (np.diff(idx) > 0).all()
+    assert np.array_equal(got["match_scores"][:, 0], idx.astype(np.float32))
+    assert all(np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy")) for k in got)

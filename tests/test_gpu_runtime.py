@@ -802,7 +802,7 @@ def test_bench_vo_stream_form_with_a_forced_rccl_group_of_one():
     call per rank, hipGraph replay, host synchronised after every call, the 100 matches + E gathered to rank 0 per call,
     pipelined by one call) on real RCCL with one rank: every call's record arrives, E is finite, the line reports per-rank
     calls per second and what the per-call gather costs."""
-    line = _run_bench(["--workload", "vo", "--stream", "--steps", "60", "--warmup", "10"], forced=True)
+    line = _run_bench(["--workload", "vo", "--stream", "--steps", "60", "--warmup", "10", "--full"], forced=True)
     assert line["backend"] == "nccl" and line["ranks_seen"] == 1 and "STREAM form" in line["config"]["workload"]
     assert line["config"]["pairs_per_gpu_per_step"] == 1 and line["config"]["finite_essential_matrices"] == 1
     assert line["config"]["mean_valid_matches_per_pair"] > 50
@@ -810,6 +810,47 @@ def test_bench_vo_stream_form_with_a_forced_rccl_group_of_one():
     assert len(st["calls_per_sec_per_rank"]) == 1 and st["calls_per_sec_per_rank"][0] > 500
     assert st["record_bytes_per_call"] == 102 * 6 * 4 and st["ms_per_call_without_gather_rank0"] > 0
     assert abs(line["value"] - 1e3 / st["ms_per_call_with_gather"]) < 1e-6 * line["value"]
+
+
+def test_plain_bench_run_times_exactly_its_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) is the headline only: set-up, warm-up, EXACTLY --steps timed steps, the last timed step's
+    outputs under --dump-outputs, the line -- no per-kernel table, extras, CPU baseline or side workloads.  The dumped
+    arrays are the wrapper's outputs for the seeded pairs (every match inside the frame, scores in (0, 1]), and a
+    --workload run honours an explicit --steps 500 too (it used to turn 500 into its own default of 50)."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    out = tmp_path / "dump"
+    line = _run_bench(["--steps", "7", "--warmup", "2", "--dump-outputs", str(out)], forced=False)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert line["value"] == pytest.approx(448 / (line["ms_per_step"] * 1e-3))
+    assert not {"kernels", "roofline", "roofline_other", "u8_ingest", "latency", "cpu_baseline", "side_workloads"} & set(line)
+    got = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert set(got) == {"matched_keypoints0", "matched_keypoints1", "match_scores", "match_valid"}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["matched_keypoints0"].shape == (448, 100, 2) and got["match_valid"].shape == (448, 100)
+    v = got["match_valid"] > 0.5
+    assert got["match_valid"].sum() / 448 == pytest.approx(line["config"]["mean_valid_matches_per_pair"])
+    assert v.sum() > 448 * 50 and (got["match_scores"][v] > 0).all() and (got["match_scores"][v] <= 1).all()
+    for key in ("matched_keypoints0", "matched_keypoints1"):
+        yx = got[key][v]                               # keypoints are (y, x)
+        assert (yx >= 0).all() and (yx[:, 0] < 480).all() and (yx[:, 1] < 640).all()
+    okw = {k: v for k, v in bench.CFG.items() if k not in ("num_pairs", "sampling_mode")}
+    box, thr = bad_tables(512)
+    for i in (0, 447):                                 # first and last pair: the records are in pair order
+        a, b = synth_batch(1000 + i, 1, 480, 640)
+        k1, k2, p = O.match_pair(a, b, box, thr, 512, **okw)
+        mk1, mk2, sc, valid, _ = O.mnn_extract(p, k1, k2, **bench.MNN)
+        want = {(*map(float, mk1[0, j]), *map(float, mk2[0, j])): float(sc[0, j]) for j in np.nonzero(valid[0])[0]}
+        g = {(*map(float, got["matched_keypoints0"][i, j]), *map(float, got["matched_keypoints1"][i, j])):
+             float(got["match_scores"][i, j]) for j in np.nonzero(v[i])[0]}
+        assert bench.compare_match_sets(g, want, bench.MNN["max_matches"]) < 2, i
+    side = _run_bench(["--workload", "c4", "--pairs-per-gpu", "8", "--steps", "500", "--warmup", "1",
+                       "--dump-outputs", str(tmp_path / "c4")], forced=False)
+    assert side["steps"] == 500 and "kernels" not in side and "roofline" not in side
+    assert np.load(tmp_path / "c4" / "match_valid.npy").shape == (8, 100)
 
 
 def test_rccl_process_group_of_one_runs_the_gather_path(tmp_path):

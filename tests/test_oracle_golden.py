@@ -622,8 +622,10 @@ def test_torch_cpu_restatement_akaze_matches_the_reference_output():
 def test_torch_cpu_restatement_vo_model_matches_the_reference_output():
     """oracle/torch_cpu.py: TorchCpuVoPath (the reference CPU path of the visual-odometry model that bench.py times
     beside `--workload vo`) reproduces the recorded reference run of ShiTomasiAngleSparseBADSinkhornWithEssentialMatrix
-    at 640x480, K = 512: keypoints exact, P through the recorded rows / maxima / dustbins to 1e-6, E to 1e-5 of max|E|,
-    the same MNN match set."""
+    at 640x480, K = 512: keypoints exact, P through the recorded rows / maxima / dustbins to 5e-6, E to 1e-5 of max|E|,
+    the same MNN match set.  P's bound covers the host's BLAS: the cost's bmm rounds as the kernel MKL picks for the CPU
+    does -- measured against the recording: 0 on the AVX-512 kernel it was made with, up to 3.7e-6 (P_colmax) on the
+    AVX2 / AVX / SSE4.2 and reproducible-mode kernels (MKL_ENABLE_INSTRUCTIONS, MKL_CBWR), which AMD hosts run."""
     import torch
     from oracle.torch_cpu import TorchCpuVoPath
     g = load_golden("angle_vo_480x640_k512")
@@ -640,7 +642,7 @@ def test_torch_cpu_restatement_vo_model_matches_the_reference_output():
     assert np.array_equal(core.argmax(2), g["P_rowarg"]) and np.array_equal(core.argmax(1), g["P_colarg"])
     for mine, key in ((core.max(2), "P_rowmax"), (core.max(1), "P_colmax"), (pn[:, :, k], "P_dustcol"), (pn[:, k, :], "P_dustrow"),
                       (pn[:, :8], "P_rows_0_8")):
-        assert np.abs(mine - g[key]).max() <= 1e-6 * max(1.0, float(np.abs(g[key]).max())), key
+        assert np.abs(mine - g[key]).max() <= 5e-6 * max(1.0, float(np.abs(g[key]).max())), key
     assert np.abs(e.numpy() - g["E"]).max() <= 1e-5 * float(np.abs(g["E"]).max())
     mk1, mk2, sc, valid = path.mutual_matches(p, k1, k2, **cfg_of(g, "mnn_cfg"))
     want = {(tuple(x), tuple(y)) for x, y, v in zip(g["mk1"][0], g["mk2"][0], g["mvalid"][0]) if v}
