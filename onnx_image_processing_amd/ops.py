@@ -800,3 +800,96 @@ def match_pairs(image1: torch.Tensor, image2: torch.Tensor, *, block_size: int, 
            ij.data_ptr() if ij is not None else None, work.data_ptr(), wbytes, N.stream_ptr())
     out = (kp1, kp2, mk1, mk2, sc, valid)
     return out + (ij,) if want_ij else out
+
+
+# ---- K12 voxel downsampling (pointcloud/voxel_downsampling.py) ----------------------------------------------------
+
+def _leaf_array(leaf_size, batch: int, device) -> torch.Tensor:
+    """One float32 leaf per cloud on `device`.  A device tensor stays on the device (0-dim or one value: broadcast; else
+    one per cloud) -- never read back; a CPU tensor, a Python number or a sequence of numbers becomes a fill / copy."""
+    if isinstance(leaf_size, torch.Tensor):
+        if leaf_size.is_cuda:
+            lf = leaf_size.to(device=device, dtype=F32).reshape(-1)
+            if lf.numel() == 1:
+                return lf.expand(batch).contiguous() if batch > 1 else lf.contiguous()
+            if lf.numel() != batch:
+                raise RuntimeError(f"leaf_size has {lf.numel()} values for {batch} clouds")
+            return lf.contiguous()
+        leaf_size = leaf_size.reshape(-1).tolist()
+        if len(leaf_size) == 1:
+            leaf_size = leaf_size[0]
+    if isinstance(leaf_size, (list, tuple)):
+        if len(leaf_size) != batch:
+            raise RuntimeError(f"leaf_size has {len(leaf_size)} values for {batch} clouds")
+        return torch.tensor([float(x) for x in leaf_size], dtype=F32).to(device)
+    return torch.full((batch,), float(leaf_size), dtype=F32, device=device)
+
+
+def _voxel_launch(pts: torch.Tensor, offsets: torch.Tensor, batch: int, leaf: torch.Tensor):
+    total, d = pts.shape
+    if d < 3:
+        raise RuntimeError(f"points must have at least 3 columns, got {d}")
+    if total >= 2 ** 31:
+        raise RuntimeError(f"{total} points: at most 2^31 - 1 per call")
+    dev = pts.device
+    out = torch.empty((total, d), dtype=F32, device=dev)
+    mask = torch.empty((total,), dtype=torch.bool, device=dev)
+    counts = torch.empty((batch,), dtype=torch.int64, device=dev)
+    wbytes = N.load().mi_voxel_downsample_workspace_bytes(batch, total, d)
+    work = torch.empty(((wbytes + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+    N.call("mi_voxel_downsample", pts.data_ptr() if total else None, N.dev(offsets, torch.int64, "offsets"), batch, total,
+           d, N.dev(leaf, F32, "leaf_size"), out.data_ptr() if total else None, mask.data_ptr() if total else None,
+           counts.data_ptr(), work.data_ptr(), work.numel() * 8, N.stream_ptr())
+    return out, mask, counts
+
+
+def voxel_downsample(points: torch.Tensor, leaf_size) -> tuple[torch.Tensor, torch.Tensor]:
+    """VoxelDownsampling.forward (`mi_voxel_downsample`, one cloud): points (N, D) float32 on the GPU, D >= 3;
+    leaf_size a 0-dim / one-value tensor (a device tensor is read on the device) or a number.  Returns (output_points
+    (N, D): the voxel means in ascending key order then zero rows, mask (N,) bool).  N = 0 returns the reference's
+    (points.clone(), empty mask).  Capturable into a hipGraph when leaf_size is a device tensor or a number."""
+    pts = points.contiguous()
+    N.dev(pts, F32, "points")
+    if pts.dim() != 2:
+        raise RuntimeError(f"points must have shape (N, D), got {tuple(pts.shape)}")
+    if pts.shape[1] < 3:
+        raise RuntimeError(f"points must have at least 3 columns, got {pts.shape[1]}")
+    if pts.shape[0] == 0:
+        return pts.clone(), torch.ones(0, dtype=torch.bool, device=pts.device)
+    offsets = torch.arange(2, dtype=torch.int64, device=pts.device) * pts.shape[0]      # [0, N] without a host copy
+    out, mask, _ = _voxel_launch(pts, offsets, 1, _leaf_array(leaf_size, 1, pts.device))
+    return out, mask
+
+
+def voxel_downsample_batch(clouds, leaf_sizes, offsets: torch.Tensor | None = None):
+    """B clouds in one `mi_voxel_downsample` call.  clouds: a list of (N_i, D) float32 GPU tensors (empty ones allowed),
+    or one packed (total, D) tensor together with `offsets` (B+1 int64: cloud b = rows offsets[b] .. offsets[b+1]-1;
+    on the device it is used as it is).  leaf_sizes: one leaf for all clouds or one per cloud (numbers, a CPU tensor
+    or a device tensor read on the device).  Returns (output_points (total, D), mask (total,) bool, counts (B,) int64,
+    offsets (B+1,) int64 on the device): cloud b's rows of the two outputs are what voxel_downsample returns for it."""
+    if isinstance(clouds, torch.Tensor):
+        if offsets is None:
+            raise RuntimeError("a packed (total, D) tensor needs offsets")
+        pts = clouds.contiguous()
+        N.dev(pts, F32, "points")
+        offs = offsets.to(device=pts.device, dtype=torch.int64).contiguous()
+        batch = offs.numel() - 1
+    else:
+        clouds = list(clouds)
+        if not clouds:
+            raise RuntimeError("voxel_downsample_batch needs at least one cloud")
+        for k, c in enumerate(clouds):
+            N.dev(c.contiguous(), F32, f"clouds[{k}]")
+            if c.dim() != 2 or c.shape[1] != clouds[0].shape[1]:
+                raise RuntimeError(f"clouds[{k}] must have shape (N, {clouds[0].shape[1]}), got {tuple(c.shape)}")
+        pts = torch.cat([c.contiguous() for c in clouds], 0)
+        sizes = [0] + [int(c.shape[0]) for c in clouds]
+        acc = torch.tensor(sizes, dtype=torch.int64).cumsum(0)
+        offs = acc.to(pts.device)
+        batch = len(clouds)
+    if pts.dim() != 2:
+        raise RuntimeError(f"points must have shape (total, D), got {tuple(pts.shape)}")
+    if batch < 1:
+        raise RuntimeError("offsets must have at least 2 entries")
+    out, mask, counts = _voxel_launch(pts, offs, batch, _leaf_array(leaf_sizes, batch, pts.device))
+    return out, mask, counts, offs

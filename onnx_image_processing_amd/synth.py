@@ -100,3 +100,23 @@ def synth_batch_u8(
     for i in range(num_pairs):
         a[i, 0], b[i, 0] = synth_pair(first_seed + i, height, width, shift, noise)
     return a, b
+
+
+def synth_depth_cloud(seed: int, height: int = 480, width: int = 640, fx: float = 525.0, fy: float = 525.0,
+                      depth_min: float = 0.5, depth_max: float = 4.5) -> np.ndarray:
+    """float32 (height * width, 3) point cloud: a synthetic depth frame back-projected through a pinhole camera
+    (principal point at the image centre), row-major pixel order -- the input a VO / RGB-D host hands to
+    VoxelDownsampling.  Depth = a floor-to-wall ramp + 16x16-pixel blocks of hashed offsets (objects) + per-pixel
+    hashed jitter of +-2 mm; every pixel is valid, so there are exactly height * width points.  float64 arithmetic
+    on hashed integers: the same points everywhere."""
+    y = np.arange(height, dtype=np.uint64)[:, None]
+    x = np.arange(width, dtype=np.uint64)[None, :]
+    yy, xx = np.broadcast_arrays(y, x)
+    ramp = depth_min + (depth_max - depth_min) * (1.0 - yy.astype(np.float64) / max(1, height - 1)) * 0.75
+    blocks = (_hash3(seed, yy // np.uint64(16), xx // np.uint64(16), 4) % np.uint64(1001)).astype(np.float64) / 1000.0
+    jitter = (_hash3(seed, yy, xx, 5) % np.uint64(4001)).astype(np.float64) / 1e6 - 0.002
+    z = np.clip(ramp + 0.25 * (depth_max - depth_min) * blocks + jitter, depth_min, depth_max)
+    u = xx.astype(np.float64) - (width - 1) / 2.0
+    v = yy.astype(np.float64) - (height - 1) / 2.0
+    pts = np.stack([u * z / fx, v * z / fy, z], axis=-1)
+    return pts.reshape(-1, 3).astype(np.float32)
