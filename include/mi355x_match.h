@@ -3,7 +3,7 @@
  *
  * The reference (fateshelled/onnx_image_processing) has no FFI: its boundary for this
  * path is the Python nn.Module.forward() signatures under pytorch_model/{detector,utils,
- * descriptor,matching,pointcloud}.  Each entry point below is what a binding for one of those
+ * descriptor,matching,pointcloud,depth}.  Each entry point below is what a binding for one of those
  * forward()s calls; the reference interface it replaces is cited per function
  * (paths relative to the reference root).  INTEGRATION.md shows the ctypes stub.
  *
@@ -556,6 +556,55 @@ MI_API size_t mi_voxel_downsample_workspace_bytes(int batch, int64_t total, int 
 MI_API int mi_voxel_downsample(const float *points, const int64_t *offsets, int batch, int64_t total, int d,
                                const float *leaf, float *out_points, uint8_t *out_mask, int64_t *out_counts,
                                void *workspace, size_t workspace_bytes, mi_stream_t stream);
+
+/* ---- depth/depth2pointcloud.py:5-24  DepthToPointCloud.forward and depth/depth2pointcloud_with_normal.py:7-33
+ * DepthToPointCloudWithNormal.forward, for a batch of frames in one launch ---------------------------------------------
+ * depth (batch, h, w): float32 (depth_is_u16 = 0) or uint16 sensor counts (1; converted exactly).  u_tab (w) and v_tab (h)
+ * float32 on the device: u_tab[x] = ((float(x) - cx) / fx) * scale, v_tab[y] = ((float(y) - cy) / fy) * scale, and
+ * z_scale = 1.0f * scale, all float32 with IEEE division -- the three columns of the reference's `uv` buffer.
+ * out_points (batch, h, w, 3) = depth * (u_tab[x], v_tab[y], z_scale): one float32 product each, the reference's bits.
+ * out_normals (batch, h, w, 3), or NULL for points only (the points are the same bits either way):
+ *     s = X + Y + Z of a point;  dx, dy = the cross-correlation of s with [[1,0,-1],[2,0,-2],[1,0,-1]] and
+ *     [[1,2,1],[0,0,0],[-1,-2,-1]], zero outside the frame (the reference's two conv2d over the three channels, padding 1);
+ *     n = (dx, dy, -1) / sqrt(dx^2 + dy^2 + 1).
+ * The normals are computed from the 3x3 depth neighbourhood and the tables (the point image is not read back); the 18
+ * products of a tap sum are added in a fixed order, the reference's convolution adds them in an order its backend
+ * chooses: they agree to 18 * eps * (sum of |weight * coordinate| over the taps) + 4 * eps, not bit for bit.
+ * batch, h, w >= 1 and batch * h * w < 2^31 (MI_E_SHAPE otherwise); no workspace; capturable into a hipGraph. */
+MI_API int mi_depth_to_points(const void *depth, int depth_is_u16, int batch, int h, int w, const float *u_tab,
+                              const float *v_tab, float z_scale, float *out_points, float *out_normals,
+                              mi_stream_t stream);
+
+/* ---- depth/depth_align.py:63-116  DepthAlignment.forward, for a batch of frames --------------------------------------
+ * Re-renders depth (batch, h, w; float32 or uint16 as above; u_tab / v_tab / z_scale of the DEPTH camera) in the colour
+ * camera's frame: out (batch, h, w) float32.  rotation (3, 3) row-major, used as p @ rotation, and translation (3):
+ * float32 on the device.  Per source pixel (x, y) with raw depth d, float32, in exactly this order:
+ *     X = d * u_tab[x];  Y = d * v_tab[y];  Z = d * z_scale
+ *     q_j = ((X * R[0][j] + Y * R[1][j]) + Z * R[2][j]) + t[j]                    j = 0, 1, 2
+ *     px = q_0 / q_2 * rgb_fx + rgb_cx;  py = q_1 / q_2 * rgb_fy + rgb_cy;  px = py = 0 if q_2 == 0
+ *     x0 = trunc(px - 0.5), x1 = trunc(px + 0.5), y0, y1 likewise; the source offers d to the targets
+ *     (y0, x0) (y0, x1) (y1, x0) (y1, x1)
+ * which is the reference's arithmetic.  Where the reference is undefined or broken this entry defines:
+ *   - a target receives the MINIMUM over all sources that write it (the nearest surface wins), 0 if none.  The reference
+ *     forms min(align0..3) of four images filled by non-accumulating index_put_ with duplicate indices: which duplicate
+ *     survives depends on the thread schedule (1 and 8 CPU threads differ); the minimum over all writers is the one
+ *     resolution that does not depend on order, and it is never larger than what the reference returns;
+ *   - a source that projects out of frame (px < 0, px >= w, py < 0, py >= h) writes nothing (the reference sends every
+ *     such source to pixel (0, 0)); a NaN projection has no pixel and writes nothing either;
+ *   - a source whose depth is 0, negative, NaN or >= 10000.0 writes nothing: 0 is "no measurement", and the reference's
+ *     fill value 10000 turns any larger value into 0 anyway.  The comparison is on the RAW depth value, before scale: with
+ *     millimetre counts (scale 0.001) everything beyond 9999 counts is silenced too, as in the reference;
+ *   - a target with x1 == w or y1 == h is dropped (the reference raises IndexError for any source that lands in
+ *     [w - 0.5, w) or [h - 0.5, h), i.e. on ordinary camera pairs with similar fields of view).
+ * At every target written by at most one source per splat image and by none of the silenced ones the result equals the
+ * single-threaded reference bit for bit.  Positive floats order as their bit patterns, so the z-buffer is a uint32
+ * atomicMin on `out` itself (filled with a sentinel first, the sentinel replaced by 0 afterwards; `out` may hold
+ * anything on entry), taken behind a tile-local z-buffer in LDS that resolves most collisions on chip: integer atomics
+ * only, bitwise reproducible, a frame's result is the same alone or in a batch.
+ * Three launches, no workspace, capturable.  Shape rules as for mi_depth_to_points. */
+MI_API int mi_depth_align(const void *depth, int depth_is_u16, int batch, int h, int w, const float *u_tab,
+                          const float *v_tab, float z_scale, float rgb_cx, float rgb_cy, float rgb_fx, float rgb_fy,
+                          const float *rotation, const float *translation, float *out, mi_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -103,6 +103,9 @@ SIGNATURES = {
     "mi_voxel_downsample_workspace_bytes": [c_int, ctypes.c_int64, c_int],
     "mi_voxel_downsample": [c_void_p, c_void_p, c_int, ctypes.c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_void_p, c_size_t, c_void_p],
+    "mi_depth_to_points": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p],
+    "mi_depth_align": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float,
+                       c_void_p, c_void_p, c_void_p, c_void_p],
 }
 
 

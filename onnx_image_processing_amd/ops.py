@@ -893,3 +893,73 @@ def voxel_downsample_batch(clouds, leaf_sizes, offsets: torch.Tensor | None = No
         raise RuntimeError("offsets must have at least 2 entries")
     out, mask, counts = _voxel_launch(pts, offs, batch, _leaf_array(leaf_sizes, batch, pts.device))
     return out, mask, counts, offs
+
+
+# ---- K13 depth front end (depth/depth2pointcloud.py, depth2pointcloud_with_normal.py, depth_align.py) -------------
+
+U16 = torch.uint16
+
+
+def _depth_frames(depth: torch.Tensor, u_tab: torch.Tensor, v_tab: torch.Tensor, what: str):
+    """(contiguous depth, is_u16, batch, h, w, batched, trailing_one) for depth of shape (H, W), (H, W, 1), (B, H, W) or
+    (B, H, W, 1), H and W being the lengths of the two tables."""
+    if not depth.is_cuda:
+        raise RuntimeError(f"{what}: depth must live on the GPU (got device {depth.device}); this package has no CPU path")
+    if depth.dtype not in (F32, U16):
+        raise RuntimeError(f"{what}: depth must be float32 or uint16, got {depth.dtype}")
+    N.dev(u_tab, F32, "u_tab")
+    N.dev(v_tab, F32, "v_tab")
+    h, w = v_tab.numel(), u_tab.numel()
+    shape = tuple(depth.shape)
+    if shape == (h, w):
+        batched, one = False, False
+    elif shape == (h, w, 1):
+        batched, one = False, True
+    elif len(shape) == 3 and shape[1:] == (h, w):
+        batched, one = True, False
+    elif len(shape) == 4 and shape[1:] == (h, w, 1):
+        batched, one = True, True
+    else:
+        raise RuntimeError(f"{what}: depth must have shape ({h}, {w}), ({h}, {w}, 1), (B, {h}, {w}) or (B, {h}, {w}, 1), "
+                           f"got {shape}")
+    batch = shape[0] if batched else 1
+    if h < 1 or w < 1 or batch < 1:
+        raise RuntimeError(f"{what}: empty depth batch {shape}")
+    if batch * h * w >= 2 ** 31:
+        raise RuntimeError(f"{what}: {batch * h * w} pixels: at most 2^31 - 1 per call")
+    return depth.contiguous(), int(depth.dtype == U16), batch, h, w, batched, one
+
+
+def depth_to_points(depth: torch.Tensor, u_tab: torch.Tensor, v_tab: torch.Tensor, z_scale: float, normals: bool = False):
+    """DepthToPointCloud(.WithNormal).forward for a batch of frames in one launch (`mi_depth_to_points`).  depth: float32
+    or uint16 on the GPU, (H, W), (H, W, 1), (B, H, W) or (B, H, W, 1); u_tab (W,), v_tab (H,) float32 on the GPU and
+    z_scale: the columns of the reference's `uv` buffer.  Returns points (H, W, 3) / (B, H, W, 3) = depth * (u_tab[x],
+    v_tab[y], z_scale), the reference's bits, and with normals=True also the unit normals of the same shape.  Current
+    stream, no synchronisation, capturable."""
+    d, is_u16, batch, h, w, batched, _ = _depth_frames(depth, u_tab, v_tab, "depth_to_points")
+    shape = (batch, h, w, 3) if batched else (h, w, 3)
+    pts = torch.empty(shape, dtype=F32, device=d.device)
+    nrm = torch.empty(shape, dtype=F32, device=d.device) if normals else None
+    N.call("mi_depth_to_points", d.data_ptr(), is_u16, batch, h, w, u_tab.data_ptr(), v_tab.data_ptr(), float(z_scale),
+           pts.data_ptr(), nrm.data_ptr() if normals else None, N.stream_ptr())
+    return (pts, nrm) if normals else pts
+
+
+def depth_align(depth: torch.Tensor, u_tab: torch.Tensor, v_tab: torch.Tensor, z_scale: float, rgb_cx: float, rgb_cy: float,
+                rgb_fx: float, rgb_fy: float, rotation: torch.Tensor, translation: torch.Tensor) -> torch.Tensor:
+    """DepthAlignment.forward for a batch of frames (`mi_depth_align`): depth as for depth_to_points with the DEPTH
+    camera's tables; rotation (3, 3) used as p @ rotation and translation (3,), float32 on the GPU.  Returns the depth
+    re-rendered in the colour camera's frame, float32, in depth's shape: per target pixel the minimum over all sources
+    whose 2x2 splat covers it, 0 where none does (include/mi355x_match.h lists the divergences from the reference).
+    Current stream, no synchronisation, capturable."""
+    d, is_u16, batch, h, w, _, _ = _depth_frames(depth, u_tab, v_tab, "depth_align")
+    rot, tr = rotation.contiguous(), translation.contiguous()
+    N.dev(rot, F32, "rotation")
+    N.dev(tr, F32, "translation")
+    if rot.numel() != 9 or tr.numel() != 3:
+        raise RuntimeError(f"rotation must have 9 and translation 3 values, got {rot.numel()} and {tr.numel()}")
+    out = torch.empty(tuple(depth.shape), dtype=F32, device=d.device)
+    N.call("mi_depth_align", d.data_ptr(), is_u16, batch, h, w, u_tab.data_ptr(), v_tab.data_ptr(), float(z_scale),
+           float(rgb_cx), float(rgb_cy), float(rgb_fx), float(rgb_fy), rot.data_ptr(), tr.data_ptr(), out.data_ptr(),
+           N.stream_ptr())
+    return out

@@ -102,13 +102,8 @@ def synth_batch_u8(
     return a, b
 
 
-def synth_depth_cloud(seed: int, height: int = 480, width: int = 640, fx: float = 525.0, fy: float = 525.0,
-                      depth_min: float = 0.5, depth_max: float = 4.5) -> np.ndarray:
-    """float32 (height * width, 3) point cloud: a synthetic depth frame back-projected through a pinhole camera
-    (principal point at the image centre), row-major pixel order -- the input a VO / RGB-D host hands to
-    VoxelDownsampling.  Depth = a floor-to-wall ramp + 16x16-pixel blocks of hashed offsets (objects) + per-pixel
-    hashed jitter of +-2 mm; every pixel is valid, so there are exactly height * width points.  float64 arithmetic
-    on hashed integers: the same points everywhere."""
+def _depth_image64(seed: int, height: int, width: int, depth_min: float, depth_max: float):
+    """(yy, xx, z float64 (H, W)): the depth image behind synth_depth_cloud / synth_depth_frame."""
     y = np.arange(height, dtype=np.uint64)[:, None]
     x = np.arange(width, dtype=np.uint64)[None, :]
     yy, xx = np.broadcast_arrays(y, x)
@@ -116,7 +111,31 @@ def synth_depth_cloud(seed: int, height: int = 480, width: int = 640, fx: float 
     blocks = (_hash3(seed, yy // np.uint64(16), xx // np.uint64(16), 4) % np.uint64(1001)).astype(np.float64) / 1000.0
     jitter = (_hash3(seed, yy, xx, 5) % np.uint64(4001)).astype(np.float64) / 1e6 - 0.002
     z = np.clip(ramp + 0.25 * (depth_max - depth_min) * blocks + jitter, depth_min, depth_max)
+    return yy, xx, z
+
+
+def synth_depth_cloud(seed: int, height: int = 480, width: int = 640, fx: float = 525.0, fy: float = 525.0,
+                      depth_min: float = 0.5, depth_max: float = 4.5) -> np.ndarray:
+    """float32 (height * width, 3) point cloud: a synthetic depth frame back-projected through a pinhole camera
+    (principal point at the image centre), row-major pixel order -- the input a VO / RGB-D host hands to
+    VoxelDownsampling.  Depth = a floor-to-wall ramp + 16x16-pixel blocks of hashed offsets (objects) + per-pixel
+    hashed jitter of +-2 mm; every pixel is valid, so there are exactly height * width points.  float64 arithmetic
+    on hashed integers: the same points everywhere."""
+    yy, xx, z = _depth_image64(seed, height, width, depth_min, depth_max)
     u = xx.astype(np.float64) - (width - 1) / 2.0
     v = yy.astype(np.float64) - (height - 1) / 2.0
     pts = np.stack([u * z / fx, v * z / fy, z], axis=-1)
     return pts.reshape(-1, 3).astype(np.float32)
+
+
+def synth_depth_frame(seed: int, height: int = 480, width: int = 640, depth_min: float = 0.5, depth_max: float = 4.5,
+                      hole_share: float = 0.0) -> np.ndarray:
+    """float32 (height, width) depth image in metres: the frame synth_depth_cloud back-projects (its z column, row-major),
+    what a depth camera hands to DepthToPointCloud / DepthAlignment.  hole_share > 0 sets that share of the pixels,
+    chosen by a per-pixel hash, to 0 ("no measurement")."""
+    yy, xx, z = _depth_image64(seed, height, width, depth_min, depth_max)
+    d = z.astype(np.float32)
+    if hole_share > 0.0:
+        hole = (_hash3(seed, yy, xx, 6) % np.uint64(1 << 20)).astype(np.float64) < hole_share * (1 << 20)
+        d[hole] = 0.0
+    return d

@@ -8,8 +8,10 @@ MI355X implementation (the very same module objects, not copies):
     from pytorch_model.matching.outlier_filters import probability_ratio_filter
     from pytorch_model.feature_detection.shi_tomasi_sparse_bad_sinkhorn import ShiTomasiSparseBADSinkhornMatcher
     from pytorch_model.pointcloud.voxel_downsampling import VoxelDownsampling
+    from pytorch_model.depth.depth2pointcloud import DepthToPointCloud
+    from pytorch_model.depth.depth_align import DepthAlignment
 
-Sub-packages outside the mirrored set (`vo`, `depth`, ...) do not exist and raise ImportError.
+Sub-packages outside the mirrored set (`vo`, `threshold`, ...) do not exist and raise ImportError.
 """
 import importlib
 import importlib.abc
