@@ -3,7 +3,7 @@
  *
  * The reference (fateshelled/onnx_image_processing) has no FFI: its boundary for this
  * path is the Python nn.Module.forward() signatures under pytorch_model/{detector,utils,
- * descriptor,matching,pointcloud,depth}.  Each entry point below is what a binding for one of those
+ * descriptor,matching,pointcloud,depth,threshold}.  Each entry point below is what a binding for one of those
  * forward()s calls; the reference interface it replaces is cited per function
  * (paths relative to the reference root).  INTEGRATION.md shows the ctypes stub.
  *
@@ -605,6 +605,67 @@ MI_API int mi_depth_to_points(const void *depth, int depth_is_u16, int batch, in
 MI_API int mi_depth_align(const void *depth, int depth_is_u16, int batch, int h, int w, const float *u_tab,
                           const float *v_tab, float z_scale, float rgb_cx, float rgb_cy, float rgb_fx, float rgb_fy,
                           const float *rotation, const float *translation, float *out, mi_stream_t stream);
+
+/* ---- threshold/otsu.py:5-48  OtsuThreshold and threshold/multi_otsu.py:6-70  MultiOtsuThreshold, for a batch of frames ---
+ * The reference builds BINS x BINS masks (Otsu) and an (n_class, C(BINS-1, n_class-1), BINS) mask (multi-Otsu); here the
+ * histogram, an int64 prefix sum over the bins and an O(1) score per candidate do the same search.  Four entries:
+ * histogram -> threshold search (Otsu or multi-Otsu) -> apply; thresholds are int32 in device memory from the search to
+ * the apply, nothing is read back, every entry is capturable into a hipGraph and takes outputs and workspace of any prior
+ * content.  Frames: (batch, pixels) of uint8, uint16, int32 or float32 (MI_PIX_*), frame b at element b * pixels, aligned
+ * to the element size; batch >= 1, pixels >= 1 (MI_E_SHAPE), 1 <= bins <= MI_THRESHOLD_MAX_BINS.
+ * Divergences from the reference:
+ *   - min_val is honoured: bin i holds the value min_val + i (the reference indexes its histogram by the raw value and
+ *     weights bin i with min_val + i: consistent for min_val = 0 only, where the results here are the reference's);
+ *   - values outside [min_val, min_val + bins), NaN and floats beyond the int32 range are NOT counted (the reference
+ *     raises from scatter_add; nothing here synchronises to raise);
+ *   - a histogram handed to the searches is int64 counts (the reference's multi-Otsu takes float32);
+ *   - multi-Otsu scores in fp64 in a fixed order (the reference sums float32 products in an order its backend chooses). */
+enum { MI_PIX_U8 = 0, MI_PIX_U16 = 1, MI_PIX_I32 = 2, MI_PIX_F32 = 3 };
+#define MI_THRESHOLD_MAX_BINS 65536
+#define MI_THRESHOLD_MAX_CLASSES 5
+
+/* hist (batch, bins) int64: hist[b][i] = number of pixels of frame b whose integer value v has v - min_val == i; float32 is
+ * truncated toward zero first (the reference's .to(torch.int64)).  hist is cleared by the call.  bins <= 4096: workgroup-
+ * private LDS sub-histograms (replicated up to 8 times, runs of equal neighbouring values pre-aggregated) flushed with
+ * 64-bit integer atomics; above: the pre-aggregated runs go to global memory directly.  Integer atomics only: the counts
+ * are exact and bitwise reproducible.  Two launches. */
+MI_API int mi_histogram(const void *frames, int dtype, int batch, long long pixels, int min_val, int bins, int64_t *hist,
+                        mi_stream_t stream);
+
+/* Otsu's threshold of each histogram (batch, bins), bins = max_val - min_val + 1: thresh[b] int32.  For every bin t, from
+ * exact int64 prefix sums: num_bk = sum_{i<=t} hist[i], fc_bk = sum_{i<=t} (min_val + i) * hist[i], num_wh = N - num_bk,
+ * fc_wh = F - fc_bk; then in float32, IEEE division, no contraction, in this order (the reference's own op sequence):
+ *     mean_bk = (float)fc_bk / (float)num_bk;  mean_wh = (float)fc_wh / (float)num_wh;  d = mean_bk - mean_wh
+ *     var = (float)(num_bk * num_wh) * (d * d)          the int64 product first, rounded once;  NaN -> 0
+ * thresh = min_val + the FIRST index of the maximum: the reference's value exactly (for min_val = 0).  The int64 product
+ * wraps beyond 3.0e9 pixels per frame, as the reference's does.  One workgroup per frame, one launch. */
+MI_API int mi_otsu_threshold(const int64_t *hist, int batch, int bins, int min_val, int32_t *thresh, mi_stream_t stream);
+
+/* Multi-Otsu: the n_class - 1 thresholds of each histogram (batch, bins), bins = max_val - min_val (max_val exclusive, as
+ * in the reference): thresholds (batch, n_class - 1) int32.  Candidates: the C(bins-1, n_class-1) tuples
+ * 1 <= th_1 < ... < th_{n-1} <= bins-1 in lexicographic order (itertools.combinations); class i holds the bins
+ * [th_i, th_{i+1}) with th_0 = 0, th_n = bins; n_i and S_i = sum (min_val + bin) * hist[bin] exact int64.  Score, fp64:
+ *     m_i = (double)S_i / (double)n_i;  V = 0.0;  for (i, j) in (0,1), (0,2), ..., (n-2,n-1):
+ *         d = m_i - m_j;  V = V + ((double)n_i * (double)n_j) * (d * d);      V = 0 if any n_i == 0 (the reference's NaN -> 0)
+ * Result: the candidate with the largest V, the smallest rank among equal V (torch.argmax's first maximum; empty bins make
+ * exact ties); returned as min_val + th_k - 1, the inclusive upper bound of class k - 1 (the reference's threshold_indices).
+ * 2 <= n_class <= MI_THRESHOLD_MAX_CLASSES (MI_E_PARAM); n_class <= bins <= MI_THRESHOLD_MAX_BINS and
+ * C(bins-1, n_class-1) <= 2^31 - 1 (MI_E_SHAPE; mi_multi_otsu_workspace_bytes returns 0 for such a request).  The
+ * workspace (8-byte aligned, any content) holds the prefix sums and one partial per workgroup of the sweep; a shorter one
+ * is MI_E_CAPACITY.  Three launches; no floating-point atomics, no cross-workgroup waits; bitwise reproducible. */
+MI_API size_t mi_multi_otsu_workspace_bytes(int batch, int bins, int n_class);
+MI_API int mi_multi_otsu_threshold(const int64_t *hist, int batch, int bins, int min_val, int n_class, int32_t *thresholds,
+                                   void *workspace, size_t workspace_bytes, mi_stream_t stream);
+
+/* One pass over the frames with thresholds (batch, n_thresh) int32 read from the device, 1 <= n_thresh <= 4.
+ * binary = 0: out uint8 (out_dtype must be MI_PIX_U8), label = number of thresholds t_k with v > t_k.
+ * binary = 1 (n_thresh must be 1): out = low where v <= t_0 and high elsewhere (NaN: high, as torch.where(img <= thresh)),
+ *     in out_dtype MI_PIX_U8, MI_PIX_I32 or MI_PIX_F32 (low and high converted to it): OtsuThreshold's bin_img with
+ *     low = min_val, high = max_val.
+ * The comparison is made in the input's type: float32 pixels against (float)t_k; integer pixels exactly (which is the
+ * reference's own-type comparison whenever t_k is representable in that type).  MI_E_PARAM for any other combination. */
+MI_API int mi_threshold_apply(const void *frames, int dtype, int batch, long long pixels, const int32_t *thresholds,
+                              int n_thresh, int out_dtype, int binary, int low, int high, void *out, mi_stream_t stream);
 
 #ifdef __cplusplus
 }

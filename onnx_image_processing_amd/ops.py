@@ -963,3 +963,133 @@ def depth_align(depth: torch.Tensor, u_tab: torch.Tensor, v_tab: torch.Tensor, z
            float(rgb_cx), float(rgb_cy), float(rgb_fx), float(rgb_fy), rot.data_ptr(), tr.data_ptr(), out.data_ptr(),
            N.stream_ptr())
     return out
+
+
+# ---- K14 thresholds (threshold/otsu.py, threshold/multi_otsu.py) ------------------------------------------------------
+
+I32 = torch.int32
+I64 = torch.int64
+_PIX = {U8: N.MI_PIX_U8, U16: N.MI_PIX_U16, I32: N.MI_PIX_I32, F32: N.MI_PIX_F32}
+THRESHOLD_MAX_BINS = 65536
+THRESHOLD_MAX_CLASSES = 5
+
+
+def _threshold_frames(frames: torch.Tensor, what: str):
+    """(contiguous frames, MI_PIX_* code, batch, pixels, batched): a tensor of up to two dimensions is one frame, one
+    of three or more is a batch along its first dimension."""
+    if not frames.is_cuda:
+        raise RuntimeError(f"{what}: frames must live on the GPU (got device {frames.device}); this package has no CPU path")
+    if frames.dtype not in _PIX:
+        raise RuntimeError(f"{what}: frames must be uint8, uint16, int32 or float32, got {frames.dtype}")
+    batched = frames.dim() >= 3
+    batch = frames.shape[0] if batched else 1
+    if frames.numel() == 0:
+        raise RuntimeError(f"{what}: empty frames {tuple(frames.shape)}")
+    return frames.contiguous(), _PIX[frames.dtype], batch, frames.numel() // batch, batched
+
+
+def _check_bins(bins: int, what: str) -> int:
+    bins = int(bins)
+    if bins < 1 or bins > THRESHOLD_MAX_BINS:
+        raise ValueError(f"{what}: {bins} bins: between 1 and {THRESHOLD_MAX_BINS}")
+    return bins
+
+
+def _histograms(hist: torch.Tensor, what: str):
+    """(contiguous int64 histograms, batch, bins, batched) from (bins,) or (B, bins)"""
+    if hist.dim() not in (1, 2):
+        raise RuntimeError(f"{what}: hist must have shape (bins,) or (B, bins), got {tuple(hist.shape)}")
+    h = hist.contiguous()
+    N.dev(h, I64, "hist")
+    batched = h.dim() == 2
+    batch = h.shape[0] if batched else 1
+    if batch < 1:
+        raise RuntimeError(f"{what}: empty batch of histograms")
+    return h, batch, _check_bins(h.shape[-1], what), batched
+
+
+def histogram(frames: torch.Tensor, min_val: int, bins: int) -> torch.Tensor:
+    """Per-frame histogram (`mi_histogram`): int64 (bins,) for one frame (a tensor of up to two dimensions), (B, bins) for
+    a batch (B, ...).  hist[i] counts the pixels whose integer value v (float32: truncated toward zero) has
+    v - min_val == i; values outside the range and NaN are not counted.  Exact and bitwise reproducible.  Current
+    stream, no synchronisation, capturable."""
+    f, code, batch, pixels, batched = _threshold_frames(frames, "histogram")
+    bins = _check_bins(bins, "histogram")
+    hist = torch.empty((batch, bins) if batched else (bins,), dtype=I64, device=f.device)
+    N.call("mi_histogram", f.data_ptr(), code, batch, pixels, int(min_val), bins, hist.data_ptr(), N.stream_ptr())
+    return hist
+
+
+def otsu_threshold(hist: torch.Tensor, min_val: int) -> torch.Tensor:
+    """Otsu's threshold of int64 histograms (bins,) / (B, bins) whose bin i holds the value min_val + i
+    (`mi_otsu_threshold`): int32 () / (B,), on the device; the reference's float32 score and first-maximum rule."""
+    h, batch, bins, batched = _histograms(hist, "otsu_threshold")
+    thresh = torch.empty((batch,), dtype=I32, device=h.device)
+    N.call("mi_otsu_threshold", h.data_ptr(), batch, bins, int(min_val), thresh.data_ptr(), N.stream_ptr())
+    return thresh if batched else thresh.reshape(())
+
+
+def multi_otsu_combinations(bins: int, n_class: int) -> int:
+    """C(bins - 1, n_class - 1), the number of candidates; ValueError outside what `mi_multi_otsu_threshold` takes."""
+    import math
+    bins, n_class = int(bins), int(n_class)
+    if n_class < 2 or n_class > THRESHOLD_MAX_CLASSES:
+        raise ValueError(f"n_class must be between 2 and {THRESHOLD_MAX_CLASSES}, got {n_class}")
+    if bins < n_class or bins > THRESHOLD_MAX_BINS:
+        raise ValueError(f"{bins} bins for {n_class} classes: between n_class and {THRESHOLD_MAX_BINS}")
+    combos = math.comb(bins - 1, n_class - 1)
+    if combos > 2 ** 31 - 1:
+        raise ValueError(f"{combos} threshold combinations ({bins} bins, {n_class} classes): at most 2^31 - 1")
+    return combos
+
+
+def multi_otsu_threshold(hist: torch.Tensor, min_val: int, n_class: int = 3) -> torch.Tensor:
+    """The n_class - 1 multi-Otsu thresholds of int64 histograms (bins,) / (B, bins) (`mi_multi_otsu_threshold`): int32
+    (n_class - 1,) / (B, n_class - 1), on the device, each the inclusive upper bound of its class.  The fp64 argmax over
+    all C(bins - 1, n_class - 1) candidates, the first in itertools.combinations order among equals."""
+    h, batch, bins, batched = _histograms(hist, "multi_otsu_threshold")
+    multi_otsu_combinations(bins, n_class)
+    lib = N.load()
+    ws_bytes = lib.mi_multi_otsu_workspace_bytes(batch, bins, int(n_class))
+    ws = torch.empty(ws_bytes, dtype=U8, device=h.device)
+    out = torch.empty((batch, n_class - 1) if batched else (n_class - 1,), dtype=I32, device=h.device)
+    N.call("mi_multi_otsu_threshold", h.data_ptr(), batch, bins, int(min_val), int(n_class), out.data_ptr(), ws.data_ptr(),
+           ws_bytes, N.stream_ptr())
+    return out
+
+
+def threshold_apply(frames: torch.Tensor, thresholds: torch.Tensor, binary=None) -> torch.Tensor:
+    """One pass over frames (as for histogram) with int32 thresholds on the device: () / (T,) for one frame, (B,) /
+    (B, T) for a batch, T <= 4 (`mi_threshold_apply`).  binary=None: uint8 labels, the number of thresholds t with v > t.
+    binary=(low, high, dtype) with one threshold per frame: low where v <= t and high elsewhere, in dtype (uint8, int32 or
+    float32): OtsuThreshold's bin_img.  The result has the frames' shape."""
+    f, code, batch, pixels, batched = _threshold_frames(frames, "threshold_apply")
+    t = thresholds.contiguous()
+    N.dev(t, I32, "thresholds")
+    if t.numel() % batch != 0 or not 1 <= t.numel() // batch <= THRESHOLD_MAX_CLASSES - 1:
+        raise RuntimeError(f"thresholds of shape {tuple(t.shape)} for {batch} frame(s): 1 to {THRESHOLD_MAX_CLASSES - 1} each")
+    n_thresh = t.numel() // batch
+    if binary is None:
+        low, high, dtype = 0, 0, U8
+    else:
+        low, high, dtype = binary
+        if dtype not in (U8, I32, F32):
+            raise ValueError(f"bin_img dtype must be uint8, int32 or float32, got {dtype}")
+        if n_thresh != 1:
+            raise RuntimeError("a two-valued image takes one threshold per frame")
+    shape = tuple(frames.shape)
+    out = torch.empty(shape or (1,), dtype=dtype, device=f.device)
+    N.call("mi_threshold_apply", f.data_ptr(), code, batch, pixels, t.data_ptr(), n_thresh, _PIX[dtype],
+           0 if binary is None else 1, int(low), int(high), out.data_ptr(), N.stream_ptr())
+    return out if shape else out.reshape(())
+
+
+def otsu(frames: torch.Tensor, min_val: int, max_val: int, dtype: torch.dtype = I32):
+    """OtsuThreshold.forward for one frame or a batch: histogram -> threshold -> two-valued image on the current stream
+    with nothing read back in between.  Returns (thresh int32 () / (B,), bin_img in `dtype` with the frames' shape:
+    min_val where v <= thresh, max_val elsewhere).  max_val is inclusive: max_val - min_val + 1 bins."""
+    if dtype not in (U8, I32, F32):
+        raise ValueError(f"bin_img dtype must be uint8, int32 or float32, got {dtype}")
+    hist = histogram(frames, min_val, _check_bins(int(max_val) - int(min_val) + 1, "otsu"))
+    thresh = otsu_threshold(hist, min_val)
+    return thresh, threshold_apply(frames, thresh, binary=(int(min_val), int(max_val), dtype))

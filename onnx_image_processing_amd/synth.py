@@ -139,3 +139,46 @@ def synth_depth_frame(seed: int, height: int = 480, width: int = 640, depth_min:
         hole = (_hash3(seed, yy, xx, 6) % np.uint64(1 << 20)).astype(np.float64) < hole_share * (1 << 20)
         d[hole] = 0.0
     return d
+
+
+THRESHOLD_FAMILIES = ("uniform", "bimodal", "sawtooth", "constant", "trimodal", "spikes")
+
+
+def synth_threshold_frame(seed: int, height: int = 480, width: int = 640, family: str = "trimodal",
+                          levels: int = 256) -> np.ndarray:
+    """(height, width) frame with values in [0, levels) for the threshold kernels, uint8 for levels <= 256 and uint16
+    above.  Families: "uniform" (every level equally likely), "bimodal" / "trimodal" (8x8-pixel regions assigned to two
+    or three modes, triangular per-pixel spread of +-levels/10 around each), "sawtooth" (a diagonal ramp that wraps, plus
+    +-levels/32 of noise), "constant" (one level, the worst case for histogram contention) and "spikes" (three exact
+    levels, every other bin empty: exact ties between threshold candidates).  Pure integer hashes: the same frame
+    everywhere."""
+    if family not in THRESHOLD_FAMILIES:
+        raise ValueError(f"family must be one of {THRESHOLD_FAMILIES}, got {family!r}")
+    if not 2 <= levels <= 65536:
+        raise ValueError(f"levels must be between 2 and 65536, got {levels}")
+    y = np.arange(height, dtype=np.uint64)[:, None]
+    x = np.arange(width, dtype=np.uint64)[None, :]
+    yy, xx = np.broadcast_arrays(y, x)
+    L = np.int64(levels)
+
+    def h(a, b, salt, mod):
+        return (_hash3(seed, a, b, salt) % np.uint64(mod)).astype(np.int64)
+
+    if family == "uniform":
+        v = h(yy, xx, 11, levels)
+    elif family == "constant":
+        v = np.full((height, width), int(h(np.uint64(0), np.uint64(0), 12, levels)), np.int64)
+    elif family == "sawtooth":
+        spread = max(1, levels // 32)
+        v = (3 * xx.astype(np.int64) + 5 * yy.astype(np.int64)) * max(1, levels // 256) % L + h(yy, xx, 13, 2 * spread + 1) - spread
+    elif family == "spikes":
+        at = np.array([levels // 9, levels // 2 + 1, levels - 1 - levels // 7], np.int64)
+        v = at[np.minimum(h(yy, xx, 14, 10) // 3, 2)]              # shares 3 : 3 : 4
+    else:
+        centres = np.array([levels // 4, (7 * levels) // 10] if family == "bimodal"
+                           else [(3 * levels) // 20, levels // 2, (17 * levels) // 20], np.int64)
+        spread = max(1, levels // 10)
+        mode = h(yy // np.uint64(8), xx // np.uint64(8), 15, len(centres))
+        v = centres[mode] + (h(yy, xx, 16, spread + 1) + h(yy, xx, 17, spread + 1) - spread)
+    v = np.clip(v, 0, L - 1)
+    return v.astype(np.uint8 if levels <= 256 else np.uint16)

@@ -10,8 +10,11 @@ MI355X implementation (the very same module objects, not copies):
     from pytorch_model.pointcloud.voxel_downsampling import VoxelDownsampling
     from pytorch_model.depth.depth2pointcloud import DepthToPointCloud
     from pytorch_model.depth.depth_align import DepthAlignment
+    from pytorch_model.threshold.otsu import OtsuThreshold
+    from pytorch_model.threshold.multi_otsu import MultiOtsuThreshold
 
-Sub-packages outside the mirrored set (`vo`, `threshold`, ...) do not exist and raise ImportError.
+The one sub-package outside the mirrored set (`vo`, host-side numpy / OpenCV and camera drivers) does not
+exist and raises ImportError.
 """
 import importlib
 import importlib.abc
