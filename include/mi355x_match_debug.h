@@ -47,7 +47,9 @@ extern "C" {
  * key 18: the P output of mi_sinkhorn_dots / mi_sinkhorn: 1 = four rows per wave, every load issued up front (default), 0 = one row per
  * wave in a loop of dependent round trips (the same P bit for bit).
  * key 19: mi_mnn_extract with m <= 1024: 1 = row and column winners in one pass over P (default), 0 = a row kernel and a
- * column kernel (the same winners: exact maxima). */
+ * column kernel (the same winners: exact maxima).
+ * key 20: mi_nms_candidates on its fast path (w % 4 == 0) at radius 3 or 5: 0 = candidates from 4x4 block maxima, each
+ * verified against its exact window maximum (default), 1 = the dense tile kernel (the same candidate sets). */
 MI_API int mi_debug_set(int key, int value);
 /* top-k kernel phase time stamps (100 MHz clock) of workgroup 0 into `buffer` (8 x uint64, device memory); NULL = off */
 MI_API int mi_debug_topk_stamps(void *buffer);

@@ -26,6 +26,7 @@ struct MiHooks {
   std::atomic<int> mnn_pair_waves{1};          // key 17: matches from the duals, 512 < m <= 1024: 1 = two waves per row group with one chunk each, 0 = two chunks per wave
   std::atomic<int> sinkhorn_exp_rows{1};       // key 18: P of mi_sinkhorn_dots / mi_sinkhorn: 1 = four rows per wave with every load up front, 0 = one row per wave in a loop
   std::atomic<int> mnn_one_pass{1};            // key 19: mi_mnn_extract: 1 = rows and columns in one pass over P (m <= 1024), 0 = a row kernel and a column kernel
+  std::atomic<int> nms_impl{0};                // key 20: mi_nms_candidates, fast path, R = 3 / 5: 0 = candidates from 4x4 block maxima, 1 = dense tile kernel
   std::atomic<int> topk_split{-1};             // key 10: workgroups per image of the top-k histogram pass (-1 = automatic)
   std::atomic<unsigned long long *> corner_clk{nullptr};   // mi_debug_clock_probe
   std::atomic<unsigned long long *> topk_prof{nullptr};    // mi_debug_topk_stamps

@@ -37,6 +37,7 @@ MI_API int mi_debug_set(int key, int value) {
     mi_hooks.mnn_pair_waves = 1;
     mi_hooks.mnn_one_pass = 1;
     mi_hooks.sinkhorn_exp_rows = 1;
+    mi_hooks.nms_impl = 0;
     mi_hooks.corner_clk = nullptr; mi_hooks.topk_prof = nullptr;
     return MI_OK;
   }
@@ -56,6 +57,7 @@ MI_API int mi_debug_set(int key, int value) {
   if (key == 17 && (value == 0 || value == 1)) { mi_hooks.mnn_pair_waves = value; return MI_OK; }
   if (key == 19 && (value == 0 || value == 1)) { mi_hooks.mnn_one_pass = value; return MI_OK; }
   if (key == 18 && (value == 0 || value == 1)) { mi_hooks.sinkhorn_exp_rows = value; return MI_OK; }
+  if (key == 20 && (value == 0 || value == 1)) { mi_hooks.nms_impl = value; return MI_OK; }
   if (key == 11 && value >= -1 && value <= 2) { mi_hooks.sinkhorn_schedule = value; return MI_OK; }
   return MI_E_PARAM;
 }

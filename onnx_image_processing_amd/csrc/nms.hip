@@ -9,15 +9,21 @@
 // candidate buffer (4096 slots = every pixel of the tile, so it cannot overflow) with the
 // count in count[img][tile]: no global atomics, no pre-zeroed counters, and the later top-k
 // sort has a total order, so the result does not depend on the order inside a segment.
+// Candidates at radius 3 and 5 on the fast path take nms_block_kernel instead (256 threads per tile): the same row
+// pass, but the exact window maximum only at the pixels that reach the maximum of their own 4x4 block.
 #include "common.h"
+#include "hooks.h"
 
 #include <math.h>
+
+#include <cmath>
 
 namespace {
 
 constexpr int NT_W = 128, NT_H = 32;
 constexpr int SEG_CAP = NT_W * NT_H;  // slots per tile segment
 constexpr int NMS_THREADS = 512;      // fast kernel: 8 waves per 128x32 tile, 24 KB of LDS (4 workgroups = 32 waves per CU)
+constexpr int NMS_BLOCK_THREADS = 256;  // block-maxima kernel: 4 waves per tile, one 4x4 block per thread (6 workgroups per CU by LDS)
 
 __device__ __forceinline__ uint64_t make_key(float m, uint32_t lin) {
   return ((uint64_t)__float_as_uint(m) << 32) | (uint64_t)(0xFFFFFFFFu - lin);
@@ -387,6 +393,161 @@ __global__ __launch_bounds__(NTH) void nms_fast_kernel(const float *__restrict__
   }
 }
 
+// ---- candidates from block maxima (fast path, candidates mode, R >= 3) ----------------------------------------
+// A pixel's window contains the whole 4 x RPT block it lies in (RPT <= R + 1), so the window maximum M is at least
+// the block maximum B, and x -> fl(x - 1e-7f) is monotone: only pixels with s >= fl(B - 1e-7f) can pass
+// s >= fl(M - 1e-7f).  That is almost always the block's maximum alone, so the dense column pass (window maxima of
+// every pixel of a thread), one compare and one compaction round per pixel are replaced by: the maximum of the
+// thread's own 4 x RPT block (registers), a bit mask of the pixels that reach it, and for each set bit -- a loop that
+// runs as often as the fullest lane of the wave needs: once on ordinary maps, 4 * RPT times on a constant one --
+// the exact window maximum from 2R+1 row maxima of the same in-place row pass as nms_fast_kernel, the dense
+// kernel's test, and one compaction round whose slots come from a workgroup counter in LDS.  Keys and segments are
+// nms_fast_kernel's, so are the candidate sets.  With so little left per pixel a tile is 4 waves' work: 256
+// threads, one 4x4 block each, six workgroups per CU (24 KB of LDS each) instead of four with 8 waves.
+template <int R, int NTH>
+__global__ __launch_bounds__(NTH) void nms_block_kernel(const float *__restrict__ score, int h, int w, int tiles_x,
+                                                        int tiles_y, float thr_eff, float thr_next, int margin,
+                                                        uint64_t *__restrict__ cand, uint32_t *__restrict__ count) {
+  constexpr int PC = (R + 3) / 4;
+  constexpr int AW4 = NT_W / 4 + 2 * PC;
+  constexpr int LH = NT_H + 2 * R;
+  constexpr int SR = NTH / AW4;                // rows staged per round
+  constexpr int NCH = (LH + SR - 1) / SR;      // staging rounds
+  constexpr int NV = 4 * (1 + 2 * PC);
+  constexpr int B0 = 4 * PC;
+  constexpr int RPT = NT_H / (NTH / 32);       // block rows = rows per thread (2 or 4)
+  static_assert((RPT == 2 || RPT == 4) && R + 1 >= 4, "a window must contain the 4 x RPT block of its centre");
+  __shared__ float4 pa[LH][AW4];               // as in nms_fast_kernel: scores, then row maxima in place
+  __shared__ uint32_t seg_n;                   // candidates of this segment so far
+  static_assert(NT_W / 4 == 32, "a wave's row-pass items must be whole rows");
+
+  const int t = threadIdx.x;
+  const int seg_id = (int)xcd_contiguous_id(blockIdx.x, gridDim.x);
+  int bid = seg_id;
+  const int tx_tile = bid % tiles_x;
+  bid /= tiles_x;
+  const int ty_tile = bid % tiles_y;
+  const int img = bid / tiles_y;
+  const int x0 = tx_tile * NT_W, y0 = ty_tile * NT_H;
+  const float *sc = score + (size_t)img * h * w;
+  const float ninf = -INFINITY;
+  const int tx = t & 31, ty = t >> 5;
+  const int gx = x0 + 4 * tx;
+  if (t == 0) seg_n = 0;
+
+  {
+    // staging: SR whole rows of AW4 chunks per round (one division per thread, the column tests once); all loads
+    // are issued before the first LDS store
+    const int rr0 = t / AW4, cc = t - rr0 * AW4;
+    const int sgx = x0 - 4 * PC + 4 * cc;
+    const bool col_in = t < SR * AW4 && sgx >= 0 && sgx < w;
+    float4 v[NCH];
+#pragma unroll
+    for (int q = 0; q < NCH; ++q) {
+      const int rr = rr0 + q * SR, gy = y0 - R + rr;
+      v[q] = make_float4(ninf, ninf, ninf, ninf);
+      if (col_in && rr < LH && gy >= 0 && gy < h)
+        v[q] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(sc) + (uint32_t)(gy * w + sgx) * 4u);
+    }
+#pragma unroll
+    for (int q = 0; q < NCH; ++q) {
+      if (t < SR * AW4 && rr0 + q * SR < LH) (&pa[0][0])[t + q * SR * AW4] = v[q];
+    }
+  }
+  __syncthreads();
+
+  // row pass, in place as in nms_fast_kernel, but a thread takes the RPT rows of its own block (staged rows
+  // RPT * ty + R + k), whose raw scores it keeps -- the block's pixels, without a second trip to global memory --
+  // and then the 2R halo rows go round the thread rows.  In every round a wave's 64 items are still two whole rows,
+  // so every read of a row is issued by the wave that later overwrites it.
+  float sv[RPT * 4];
+  auto row_item = [&](int rr, float *raw) {
+    float v[NV];
+    {
+      typedef float f4v __attribute__((ext_vector_type(4)));
+      f4v q[NV / 4];
+#pragma unroll
+      for (int c = 0; c < NV / 4; ++c) q[c] = *reinterpret_cast<const f4v *>(&pa[rr][tx + c]);
+#pragma unroll
+      for (int c = 0; c < NV / 4; ++c) asm volatile("" : "+v"(q[c]));
+#pragma unroll
+      for (int c = 0; c < NV / 4; ++c) { v[4 * c] = q[c].x; v[4 * c + 1] = q[c].y; v[4 * c + 2] = q[c].z; v[4 * c + 3] = q[c].w; }
+    }
+    if (raw) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) raw[c] = v[B0 + c];
+    }
+    float o[4];
+    const float core = vmax_fold<2 * R - 3>(v[B0 + 3 - R], &v[B0 + 4 - R]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float ext[3];
+#pragma unroll
+      for (int e = 0; e < 3; ++e) ext[e] = (e < 3 - k) ? v[B0 + k - R + e] : v[B0 + R + 1 + (e - (3 - k))];
+      o[k] = vmax_fold<3>(core, ext);
+    }
+    pa[rr][tx + PC] = make_float4(o[0], o[1], o[2], o[3]);
+  };
+#pragma unroll
+  for (int k = 0; k < RPT; ++k) row_item(ty * RPT + R + k, &sv[4 * k]);
+#pragma unroll
+  for (int hr = 0; hr < 2 * R; hr += NTH / 32)                          // halo rows 0..R-1 and NT_H+R..NT_H+2R-1
+    if (hr + ty < 2 * R) row_item(hr + ty < R ? hr + ty : NT_H + hr + ty, nullptr);
+
+  // block maximum and the mask of the block's possible candidates: bit 4 * k + c = pixel (row k, column c).
+  // One compare per pixel: s >= max(fl(B - 1e-7f), next float above the threshold); a NaN never passes, an
+  // all-NaN block has B = NaN, which v_max_f32 drops in favour of the threshold.
+  const float bmax = vmax_fold<RPT * 4 - 1>(sv[0], &sv[1]);
+  const float bound = vmax2(bmax - 1e-7f, thr_next);
+  uint32_t m = 0;
+#pragma unroll
+  for (int q = RPT * 4 - 1; q >= 0; --q) m = (m << 1) | (sv[q] >= bound ? 1u : 0u);
+  __syncthreads();
+
+  const int lane = t & 63;
+  const float *rowmax = reinterpret_cast<const float *>(&pa[ty * RPT][tx + PC]);   // staged row ly = window row ly - R
+  uint64_t *seg = cand + (size_t)seg_id * SEG_CAP;
+  const int gy0 = y0 + ty * RPT;
+  // Decided ONCE, on the full masks: when no lane of the wave holds more than one bit, the loop runs a single round
+  // and every candidate is its block's maximum, so its score is bmax.  Otherwise every round of the wave picks the
+  // candidate's own score from the registers -- in a later round a lane's last bit need not be the block maximum
+  // (B and B - 6e-8 in one block are both candidates), and the key and the test need that pixel's bits.
+  const bool several = __ballot((m & (m - 1)) != 0) != 0;
+  while (__ballot(m != 0)) {
+    const bool act = m != 0;
+    const int q = act ? __builtin_ctz(m) : 0;
+    const int k = q >> 2, c = q & 3;
+    float s = bmax;
+    if (several) {
+      float rsel[RPT];
+#pragma unroll
+      for (int j = 0; j < RPT; ++j) rsel[j] = c & 2 ? (c & 1 ? sv[4 * j + 3] : sv[4 * j + 2]) : (c & 1 ? sv[4 * j + 1] : sv[4 * j]);
+      if constexpr (RPT == 2) s = k ? rsel[1] : rsel[0];
+      else s = k & 2 ? (k & 1 ? rsel[3] : rsel[2]) : (k & 1 ? rsel[1] : rsel[0]);
+    }
+    const float *p = rowmax + k * (AW4 * 4) + c;
+    float e[2 * R + 1];
+#pragma unroll
+    for (int j = 0; j <= 2 * R; ++j) e[j] = p[j * (AW4 * 4)];
+    const float mv = vmax_fold<2 * R>(e[0], &e[1]);
+    const int gy = gy0 + k, gxc = gx + c;
+    const bool keep = act && (s >= (mv - 1e-7f)) && (s > thr_eff) && in_border(gy, gxc, h, w, margin);   // keypoint_utils.py:43
+    const unsigned long long bal = __ballot(keep);
+    if (bal) {
+      uint32_t base = 0;
+      if (lane == 0) base = atomicAdd(&seg_n, (uint32_t)__popcll(bal));
+      base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+      if (keep) {
+        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+        seg[base + below] = make_key(s, (uint32_t)(gy * w + gxc));
+      }
+    }
+    m &= m - 1;
+  }
+  __syncthreads();
+  if (t == 0) count[seg_id] = seg_n;
+}
+
 template <int MODE>
 bool launch_fast(const float *score, int n, int h, int w, int radius, float *mask, float thr_eff, int margin,
                  uint64_t *cand, uint32_t *count, hipStream_t s) {
@@ -395,6 +556,18 @@ bool launch_fast(const float *score, int n, int h, int w, int radius, float *mas
   if (MODE == 0 && ((uintptr_t)mask % 16) != 0) return false;
   const int tiles_x = ceil_div(w, NT_W), tiles_y = ceil_div(h, NT_H);
   const dim3 grid((unsigned)(n * tiles_x * tiles_y));
+  // candidates at the radii the block form was measured faster at; debug key 20 = 1: dense
+  if (MODE == 1 && (radius == 3 || radius == 5) && MI_HOOK(nms_impl, 0) == 0) {
+    // smallest float above the threshold (thr_eff >= 0): "s > thr_eff" as "s >= thr_next"
+    const float thr_next = std::isinf(thr_eff) ? thr_eff : std::nextafterf(thr_eff, INFINITY);
+    if (radius == 3)
+      hipLaunchKernelGGL((nms_block_kernel<3, NMS_BLOCK_THREADS>), grid, dim3(NMS_BLOCK_THREADS), 0, s, score, h, w,
+                         tiles_x, tiles_y, thr_eff, thr_next, margin, cand, count);
+    else
+      hipLaunchKernelGGL((nms_block_kernel<5, NMS_BLOCK_THREADS>), grid, dim3(NMS_BLOCK_THREADS), 0, s, score, h, w,
+                         tiles_x, tiles_y, thr_eff, thr_next, margin, cand, count);
+    return true;
+  }
 #define MI_NMS_CASE(RR)                                                                                      \
   case RR:                                                                                                   \
     hipLaunchKernelGGL((nms_fast_kernel<MODE, RR, NMS_THREADS>), grid, dim3(NMS_THREADS), 0, s, score, h, w,   \

@@ -80,8 +80,17 @@ def main():
         def f():
             N.call("mi_nms_candidates", sc.data_ptr(), n, H, W, args.radius, 0.0, 7, cand.data_ptr(), count.data_ptr(),
                    N.stream_ptr())
-        ms = timeit(f, args.iters)
-        res["nms_candidates"] = (ms, 4.0 * px / ms / 1e6)
+        # candidates from block maxima (hook 20 = 0; dispatched at radius 3 and 5) against the dense tile kernel (1):
+        # the same keypoints and scores
+        ref_kp = None
+        for impl, name in ((1, "dense"), (0, "block")):
+            N.use_debug_library().mi_debug_set(20, impl)
+            got = ops.nms_topk(sc, args.radius, K, 0.0, 7)
+            assert ref_kp is None or (torch.equal(got[0], ref_kp[0]) and torch.equal(got[1], ref_kp[1])), name
+            ref_kp = got
+            ms = timeit(f, args.iters)
+            res[f"nms_candidates r{args.radius} ({name})"] = (ms, 4.0 * px / ms / 1e6)
+        N.use_debug_library().mi_debug_set(20, 0)
         ms = timeit(lambda: ops.nms_mask(sc, args.radius), args.iters)
         res["nms_mask"] = (ms, 8.0 * px / ms / 1e6)
         print("candidates per image:", float(count.float().sum(1).mean()))
