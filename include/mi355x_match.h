@@ -3,7 +3,7 @@
  *
  * The reference (fateshelled/onnx_image_processing) has no FFI: its boundary for this
  * path is the Python nn.Module.forward() signatures under pytorch_model/{detector,utils,
- * descriptor,matching,pointcloud,depth,threshold}.  Each entry point below is what a binding for one of those
+ * descriptor,matching,pointcloud,depth,threshold,vo}.  Each entry point below is what a binding for one of those
  * forward()s calls; the reference interface it replaces is cited per function
  * (paths relative to the reference root).  INTEGRATION.md shows the ctypes stub.
  *
@@ -666,6 +666,105 @@ MI_API int mi_multi_otsu_threshold(const int64_t *hist, int batch, int bins, int
  * reference's own-type comparison whenever t_k is representable in that type).  MI_E_PARAM for any other combination. */
 MI_API int mi_threshold_apply(const void *frames, int dtype, int batch, long long pixels, const int32_t *thresholds,
                               int n_thresh, int out_dtype, int binary, int low, int high, void *out, mi_stream_t stream);
+
+/* ---- relative pose (K15): vo/pose_estimation.py:53-162  estimate_pose_ransac and triangulate_points, for a batch of pairs --
+ * The reference does this step on the host with OpenCV, one pair at a time: cv2.findEssentialMat(RANSAC) (:87-94),
+ * cv2.recoverPose (:102-108) and cv2.triangulatePoints (:143-160).  Five entries here, batched over pairs, every one a
+ * pure function of its arguments: no allocation, no synchronisation, no memset, one stream, no atomics, every sum in a
+ * fixed order -- the same inputs and seed give the same bits, and every entry can be captured into a hipGraph.  Outputs
+ * and workspace may hold anything on entry; every output element is written.
+ * Correspondence i of pair b is pts1[b][i] <-> pts2[b][i], (batch, n, 2) float32 in NORMALISED image coordinates (x, y)
+ * as mi_normalise_keypoints writes them; `valid` / `mask` (batch, n) bytes select rows (non-zero = use; valid may be NULL:
+ * every row).  Rows that are not selected are never read for their coordinates.  1 <= n <= MI_POSE_MAX_N (the staged
+ * correspondences of a pair live in 36 KB of LDS), batch <= 65535 (MI_E_PARAM beyond; < 1: MI_E_SHAPE).
+ *
+ * Divergences from OpenCV, all deliberate:
+ *   - minimal samples are 8 correspondences solved linearly (Hartley-normalised 8-point + projection onto the essential
+ *     manifold), not Nister's 5-point solver: one candidate per sample, no polynomial roots;
+ *   - the best hypothesis is the one of minimum truncated cost sum min(d^2, thr^2) (MSAC), not of maximum inlier count;
+ *   - a fixed number of hypotheses, no adaptive stop from `prob`;
+ *   - the sampler is a stateless counter-based hash, not cv::RNG: results do not depend on call history;
+ *   - refinement is refine_rounds rounds of linear refit on the inliers (local optimisation), where OpenCV stops at the
+ *     best minimal solution;
+ *   - recover_pose takes a point's depths from the two-view linear equations instead of a DLT triangulation per
+ *     candidate (the same sign and magnitude for consistent correspondences).
+ *
+ * Sampling.  mix(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16 (uint32, wrapping).
+ *   draw(seed, b, h, s) = mix(mix(mix(seed + 0x9E3779B9) + b) + (8 h + s)).
+ *   Let nv be the number of valid rows of pair b, ranked 0 .. nv-1 in index order.  For slot s = 0 .. 7 in turn:
+ *   r = draw(seed, b, h, s) mod (nv - s); then for every rank q already taken, in ASCENDING order of q: if r >= q then
+ *   r = r + 1.  Slot s takes rank r (eight distinct ranks; the modulo bias is below nv / 2^32).
+ * Solve.  Per image the sample's centroid c and scale sqrt(2) / sqrt(mean |p - c|^2); rows
+ *   [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1] of normalised points; Gauss-Jordan elimination with complete pivoting
+ *   (the first maximum of |a| in (row, column) order); the sample is RANK-DEFICIENT when a pivot is not above 1e-5 times the
+ *   first pivot (or a point set has zero spread); null vector scaled to unit norm = E_hat row-major; E = T2^T E_hat T1;
+ *   projection onto singular values (s, s, 0), s the mean of the two largest (csrc/essential_math.h, shared with
+ *   mi_essential_matrix).  E is defined up to sign and satisfies x2^T E x1 = 0.
+ * Scoring.  For every valid row, with X1 = (x1, y1, 1), X2 = (x2, y2, 1): d^2 = (X2^T E X1)^2 /
+ *   ((E X1)_0^2 + (E X1)_1^2 + (E^T X2)_0^2 + (E^T X2)_1^2), +inf where the denominator is 0; inlier: d^2 <= thr^2.
+ *   count = number of inliers, cost = sum over the valid rows in index order of min(d^2, thr^2), float32.
+ * Degenerate: fewer than 8 valid rows, a rank-deficient sample or a non-finite result give cost = +inf, count = 0 and a
+ * zero matrix. */
+#define MI_POSE_MAX_N 2048
+#define MI_POSE_MAX_HYPOTHESES 65536
+#define MI_POSE_MAX_REFINE_ROUNDS 8
+
+/* H = num_hypotheses hypotheses per pair, generated and scored: e_h (batch, H, 3, 3), cost (batch, H) float32,
+ * count (batch, H) int32.  H < 1: MI_E_SHAPE; H > MI_POSE_MAX_HYPOTHESES, threshold <= 0 or not finite: MI_E_PARAM.
+ * threshold is in the units of the points (pixels / mean focal length).  One launch: ceil(H / 64) x batch waves, a lane
+ * per hypothesis. */
+MI_API int mi_essential_hypotheses(const float *pts1, const float *pts2, const uint8_t *valid, int batch, int n,
+                                   int num_hypotheses, float threshold, uint32_t seed, float *e_h, float *cost,
+                                   int32_t *count, mi_stream_t stream);
+
+/* E (batch, 3, 3) from the rows with mask != 0 (mask is required): Hartley normalisation over those rows, the 9x9 normal
+ * equations M = A^T A of the rows above, the eigenvector of M's smallest eigenvalue (6 steps of inverse iteration on the
+ * Cholesky factor of M + 2e-6 trace(M) I from the all-ones vector), denormalisation and manifold projection as above.
+ * ok (batch) bytes: 0 and a zero E for a mask with fewer than 8 rows (or no finite result), else 1.  One wave per pair. */
+MI_API int mi_essential_refit(const float *pts1, const float *pts2, const uint8_t *mask, int batch, int n, float *e,
+                              uint8_t *ok, mi_stream_t stream);
+
+/* The whole estimator: mi_essential_hypotheses into the workspace, then per pair the hypothesis of minimum cost (the
+ * lowest h among equals; h = 0 when every cost is +inf) and refine_rounds rounds r = 0 .. R-1 of local optimisation:
+ * take the inliers of the best E so far at k_r * threshold, k_r = 1 + (R - 1 - r) / 2 (R = 3: 2, 1.5, 1), refit as
+ * mi_essential_refit, score at `threshold`; the refit replaces the best E only when its cost is strictly lower (costs
+ * inside this step are summed lanes-strided, so the hypothesis' own cost is re-summed that way first).  A round whose
+ * inlier set has fewer than 8 rows changes nothing.
+ * e (batch, 3, 3); inlier (batch, n) bytes: d^2 <= threshold^2 under e, 0 for rows that are not valid; best_h (batch) the
+ * selected hypothesis; count (batch) = number of inlier bytes set.  A pair without a usable hypothesis gives a zero e, no
+ * inliers, count 0.  With refine_rounds = 0, e / count are exactly e_h[best_h] / count[best_h] of mi_essential_hypotheses.
+ * 0 <= refine_rounds <= MI_POSE_MAX_REFINE_ROUNDS (MI_E_PARAM).  workspace: mi_essential_ransac_workspace_bytes(batch, n,
+ * H) bytes (0 for an unsupported request), 16-byte aligned (MI_E_ALIGN), any content; shorter: MI_E_CAPACITY.  Two launches. */
+MI_API size_t mi_essential_ransac_workspace_bytes(int batch, int n, int num_hypotheses);
+MI_API int mi_essential_ransac(const float *pts1, const float *pts2, const uint8_t *valid, int batch, int n,
+                               int num_hypotheses, float threshold, int refine_rounds, uint32_t seed, float *e,
+                               uint8_t *inlier, int32_t *best_h, int32_t *count, void *workspace, size_t workspace_bytes,
+                               mi_stream_t stream);
+
+/* cv2.recoverPose (:102-108): r (batch, 3, 3), t (batch, 3) with x2 ~ r x1 + t, det r = +1, |t| = 1, from e (any scale
+ * and sign) and the rows with mask != 0 (NULL: every row).  E is scaled to Frobenius norm sqrt(2); t = the normalised
+ * cross product of largest norm among the column pairs (0,1), (0,2), (1,2) of E, the first among equals (the left null
+ * vector); Ra = cof(E) - [t]x E and Rb = cof(E) + [t]x E (cof: the matrix of cofactors), each followed by one step
+ * R (3 I - R^T R) / 2 towards the nearest rotation.  Candidates in this order: 0 (Ra, t), 1 (Rb, t), 2 (Ra, -t),
+ * 3 (Rb, -t).  Under a candidate a row PASSES when, with a = X2 x (R X1), c = X2 x t: z1 = -(a.c) / (a.a) (the depth in
+ * camera 1 that best satisfies X2 x (z1 R X1 + t) = 0) and z2 = z1 (R X1)_2 + t_2 are both positive and both below
+ * distance_threshold (> 0; OpenCV's recoverPose default is 50).  The candidate with the most passing rows wins, the first
+ * among equals.  pose_mask (batch, n): the rows that pass under the winner (a subset of mask); count (batch): their
+ * number; ok (batch) bytes: 1 when count >= 5 (the reference's cut at :109), else 0 with r = identity and t = 0.  A zero
+ * or non-finite e gives count 0.  One wave per pair. */
+MI_API int mi_recover_pose(const float *e, const float *pts1, const float *pts2, const uint8_t *mask, int batch, int n,
+                           float distance_threshold, float *r, float *t, uint8_t *pose_mask, int32_t *count, uint8_t *ok,
+                           mi_stream_t stream);
+
+/* cv2.triangulatePoints and the tail of triangulate_points (:143-160): proj1, proj2 (batch, 3, 4), pts1, pts2
+ * (batch, n, 2) as (x, y) in the units the projection matrices expect (pixels for K [R | t]); any n >= 1.  Per point the
+ * rows x P[2] - P[0], y P[2] - P[1] of both views, each scaled to unit norm (conditioning; OpenCV does not), and the unit
+ * right singular vector X of the smallest singular value (one-sided Jacobi, 6 sweeps).  points (batch, n, 3) = X[:3] / X[3]
+ * where |X[3]| > 1e-9 and the quotient is finite, else zeros; finite (batch, n) bytes say which.  A system of rank < 3 --
+ * the second smallest singular value not above 1e-5 times the largest: identical rays under identical cameras, where
+ * every point of the ray is a solution -- also gives zeros and finite = 0.  One thread per point. */
+MI_API int mi_triangulate(const float *proj1, const float *proj2, const float *pts1, const float *pts2, int batch, int n,
+                          float *points, uint8_t *finite, mi_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,7 @@
 // all reductions have a fixed order, so the result is deterministic.  fp32 throughout like the
 // reference; its GEMM / sum orders are BLAS's, so parity is by tolerance (|dE| ~ 1e-5 measured).
 #include "common.h"
+#include "essential_math.h"
 
 #include <math.h>
 
@@ -31,27 +32,6 @@ __device__ __forceinline__ void topk_insert(float (&top)[EM_MAXK], float x) {
     top[q] = hi;
     x = lo;
   }
-}
-
-__device__ __forceinline__ float norm3(const float *v) { return sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); }
-__device__ __forceinline__ float det3(const float (*m)[3]) {
-  return m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
-         m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
-}
-__device__ __forceinline__ float signf(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
-__device__ __forceinline__ void matvec3(const float (*a)[3], const float *v, float *out) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r) out[r] = (a[r][0] * v[0] + a[r][1] * v[1]) + a[r][2] * v[2];
-}
-__device__ __forceinline__ void unit3(float *v) {
-  const float nn = norm3(v) + 1e-8f;
-#pragma unroll
-  for (int r = 0; r < 3; ++r) v[r] = v[r] / nn;
-}
-__device__ __forceinline__ void cross3(const float *a, const float *b, float *o) {
-  o[0] = a[1] * b[2] - a[2] * b[1];
-  o[1] = a[2] * b[0] - a[0] * b[2];
-  o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
 // weighted centroid and scale of one point set by one wave (essential_matrix_estimator.py:270-283)
@@ -342,13 +322,9 @@ __device__ void em_solve(const EmShared &S, int b, int n_iter, int n_iter_manifo
     for (int c = 0; c < 3; ++c) e[r][c] = (tmp[r][0] * t1[0][c] + tmp[r][1] * t1[1][c]) + tmp[r][2] * t1[2][c];
   // ---- manifold projection (:175-248)
   float bm[3][3], bs[3][3];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) bm[r][c] = (e[0][r] * e[0][c] + e[1][r] * e[1][c]) + e[2][r] * e[2][c];
-  const float lam3 = (bm[0][0] + bm[1][1]) + bm[2][2];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) bs[r][c] = (r == c ? lam3 : 0.0f) - bm[r][c];
+  em_manifold_gram(e, bm, bs);
   const float inv_sqrt3 = 1.0f / sqrtf(3.0f);
-  float va[3] = {inv_sqrt3, inv_sqrt3, inv_sqrt3}, vc[3] = {inv_sqrt3, inv_sqrt3, inv_sqrt3}, vb[3], w3[3];
+  float va[3] = {inv_sqrt3, inv_sqrt3, inv_sqrt3}, vc[3] = {inv_sqrt3, inv_sqrt3, inv_sqrt3}, w3[3];
   {
     float bx[3][3], vx[3] = {inv_sqrt3, inv_sqrt3, inv_sqrt3};      // lane 0: bm -> va; every other lane: bs -> vc
     for (int r = 0; r < 3; ++r)
@@ -356,28 +332,12 @@ __device__ void em_solve(const EmShared &S, int b, int n_iter, int n_iter_manifo
     for (int it = 0; it < n_iter_manifold; ++it) { matvec3(bx, vx, w3); vx[0] = w3[0]; vx[1] = w3[1]; vx[2] = w3[2]; unit3(vx); }
     for (int r = 0; r < 3; ++r) { va[r] = lane_value(vx[r], 0); vc[r] = lane_value(vx[r], 1); }
   }
-  cross3(vc, va, vb);
-  unit3(vb);
-  float vm[3][3] = {{va[0], vb[0], vc[0]}, {va[1], vb[1], vc[1]}, {va[2], vb[2], vc[2]}};   // columns v1 v2 v3
-  const float sgn_v = signf(det3(vm));
-  for (int r = 0; r < 3; ++r) vm[r][2] *= sgn_v;
-  const float c0[3] = {vm[0][0], vm[1][0], vm[2][0]}, c1[3] = {vm[0][1], vm[1][1], vm[2][1]};
-  float ev0[3], ev1[3], u3[3];
-  matvec3(e, c0, ev0);
-  matvec3(e, c1, ev1);
-  const float sg1 = norm3(ev0), sg2 = norm3(ev1);
-  const float s_avg = (sg1 + sg2) / 2.0f;
-  float u1[3], u2[3];
-  for (int r = 0; r < 3; ++r) { u1[r] = ev0[r] / (sg1 + 1e-8f); u2[r] = ev1[r] / (sg2 + 1e-8f); }
-  cross3(u1, u2, u3);
-  float um[3][3] = {{u1[0], u2[0], u3[0]}, {u1[1], u2[1], u3[1]}, {u1[2], u2[2], u3[2]}};
-  const float sgn_u = signf(det3(um));
-  for (int r = 0; r < 3; ++r) um[r][2] *= sgn_u;
-  // E = U diag(s, s, 0) V^T
+  float proj[3][3];
+  em_manifold_from_vectors(e, va, vc, proj);
   float *out = e_out + (size_t)b * 9;
   if (lane == 0)
     for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) out[r * 3 + c] = (um[r][0] * s_avg) * vm[c][0] + (um[r][1] * s_avg) * vm[c][1];
+      for (int c = 0; c < 3; ++c) out[r * 3 + c] = proj[r][c];
 }
 
 template <typename SRC>

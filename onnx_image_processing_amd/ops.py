@@ -1093,3 +1093,106 @@ def otsu(frames: torch.Tensor, min_val: int, max_val: int, dtype: torch.dtype = 
     hist = histogram(frames, min_val, _check_bins(int(max_val) - int(min_val) + 1, "otsu"))
     thresh = otsu_threshold(hist, min_val)
     return thresh, threshold_apply(frames, thresh, binary=(int(min_val), int(max_val), dtype))
+
+
+# ---- relative pose (K15: vo/pose_estimation.py:53-162 on the GPU) ---------------------------------------------------------
+
+POSE_MAX_N = 2048                          # MI_POSE_MAX_N
+POSE_MAX_REFINE_ROUNDS = 8                 # MI_POSE_MAX_REFINE_ROUNDS
+
+
+def _correspondences(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, what: str):
+    """(B, N, 2) normalised (x, y) points of both views and an optional (B, N) mask, as the C ABI reads them."""
+    q1, q2 = pts1.float().contiguous(), pts2.float().contiguous()
+    if q1.dim() != 3 or q1.shape[-1] != 2 or q1.shape != q2.shape:
+        raise RuntimeError(f"{what}: points must both be (B, N, 2), got {tuple(pts1.shape)} and {tuple(pts2.shape)}")
+    b, n = int(q1.shape[0]), int(q1.shape[1])
+    if not 1 <= n <= POSE_MAX_N:
+        raise RuntimeError(f"{what}: N = {n} correspondences, supported: 1 .. {POSE_MAX_N}")
+    v = _validity_bytes(valid)
+    if v is not None and tuple(v.shape) != (b, n):
+        raise RuntimeError(f"{what}: the mask must be ({b}, {n}), got {tuple(v.shape)}")
+    N.dev(q1, F32, "pts1"), N.dev(q2, F32, "pts2")
+    return q1, q2, v, b, n
+
+
+def essential_hypotheses(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, num_hypotheses: int,
+                         threshold: float, seed: int = 0):
+    """`mi_essential_hypotheses`: H 8-point hypotheses per pair from the counter-based sampler, each scored on every valid
+    correspondence -> (E_h (B, H, 3, 3), MSAC cost (B, H) float32, inlier count (B, H) int32)."""
+    q1, q2, v, b, n = _correspondences(pts1, pts2, valid, "essential_hypotheses")
+    h = int(num_hypotheses)
+    e_h = torch.empty((b, h, 3, 3), dtype=F32, device=q1.device)
+    cost = torch.empty((b, h), dtype=F32, device=q1.device)
+    count = torch.empty((b, h), dtype=I32, device=q1.device)
+    N.call("mi_essential_hypotheses", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "valid") if v is not None else None, b, n, h,
+           float(threshold), int(seed) & 0xFFFFFFFF, e_h.data_ptr(), cost.data_ptr(), count.data_ptr(), N.stream_ptr())
+    return e_h, cost, count
+
+
+def essential_refit(pts1: torch.Tensor, pts2: torch.Tensor, mask: torch.Tensor):
+    """`mi_essential_refit`: the linear 8-point E over the masked correspondences -> (E (B, 3, 3), ok (B,) bool)."""
+    q1, q2, v, b, n = _correspondences(pts1, pts2, mask, "essential_refit")
+    if v is None:
+        raise RuntimeError("essential_refit needs a mask")
+    e = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
+    ok = torch.empty((b,), dtype=U8, device=q1.device)
+    N.call("mi_essential_refit", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "mask"), b, n, e.data_ptr(), ok.data_ptr(),
+           N.stream_ptr())
+    return e, ok.view(torch.bool)
+
+
+def essential_ransac(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, num_hypotheses: int,
+                     threshold: float, refine_rounds: int = 3, seed: int = 0):
+    """`mi_essential_ransac`: hypotheses, MSAC selection and refine_rounds rounds of refit-and-rescore in two launches ->
+    (E (B, 3, 3), inlier (B, N) bool, best_h (B,) int32, count (B,) int32)."""
+    q1, q2, v, b, n = _correspondences(pts1, pts2, valid, "essential_ransac")
+    h = int(num_hypotheses)
+    wbytes = int(N.load().mi_essential_ransac_workspace_bytes(b, n, h))
+    if wbytes == 0:
+        raise RuntimeError(f"essential_ransac: unsupported request (batch {b}, N {n}, {h} hypotheses)")
+    work = torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=q1.device)
+    e = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
+    inlier = torch.empty((b, n), dtype=U8, device=q1.device)
+    best_h = torch.empty((b,), dtype=I32, device=q1.device)
+    count = torch.empty((b,), dtype=I32, device=q1.device)
+    N.call("mi_essential_ransac", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "valid") if v is not None else None, b, n, h,
+           float(threshold), int(refine_rounds), int(seed) & 0xFFFFFFFF, e.data_ptr(), inlier.data_ptr(), best_h.data_ptr(),
+           count.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    return e, inlier.view(torch.bool), best_h, count
+
+
+def recover_pose(e: torch.Tensor, pts1: torch.Tensor, pts2: torch.Tensor, mask: torch.Tensor | None,
+                 distance_threshold: float = 50.0):
+    """`mi_recover_pose`: (R (B, 3, 3), t (B, 3), pose_mask (B, N) bool, count (B,) int32, ok (B,) bool) with
+    x2 ~ R x1 + t, det R = +1, |t| = 1; identity / zero where fewer than 5 correspondences pass the depth test."""
+    q1, q2, v, b, n = _correspondences(pts1, pts2, mask, "recover_pose")
+    ee = e.float().contiguous()
+    if tuple(ee.shape) != (b, 3, 3):
+        raise RuntimeError(f"recover_pose: E must be ({b}, 3, 3), got {tuple(e.shape)}")
+    r = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
+    t = torch.empty((b, 3), dtype=F32, device=q1.device)
+    pose_mask = torch.empty((b, n), dtype=U8, device=q1.device)
+    count = torch.empty((b,), dtype=I32, device=q1.device)
+    ok = torch.empty((b,), dtype=U8, device=q1.device)
+    N.call("mi_recover_pose", N.dev(ee, F32, "E"), q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "mask") if v is not None else None,
+           b, n, float(distance_threshold), r.data_ptr(), t.data_ptr(), pose_mask.data_ptr(), count.data_ptr(), ok.data_ptr(),
+           N.stream_ptr())
+    return r, t, pose_mask.view(torch.bool), count, ok.view(torch.bool)
+
+
+def triangulate(proj1: torch.Tensor, proj2: torch.Tensor, pts1: torch.Tensor, pts2: torch.Tensor):
+    """`mi_triangulate`: two-view DLT of (B, N, 2) points (x, y) under projection matrices (B, 3, 4) ->
+    (points (B, N, 3), finite (B, N) bool); zeros where the homogeneous coordinate vanishes."""
+    q1, q2 = pts1.float().contiguous(), pts2.float().contiguous()
+    p1, p2 = proj1.float().contiguous(), proj2.float().contiguous()
+    if q1.dim() != 3 or q1.shape[-1] != 2 or q1.shape != q2.shape or q1.shape[1] < 1:
+        raise RuntimeError(f"triangulate: points must both be (B, N, 2), got {tuple(pts1.shape)} and {tuple(pts2.shape)}")
+    b, n = int(q1.shape[0]), int(q1.shape[1])
+    if tuple(p1.shape) != (b, 3, 4) or tuple(p2.shape) != (b, 3, 4):
+        raise RuntimeError(f"triangulate: projection matrices must be ({b}, 3, 4), got {tuple(proj1.shape)}, {tuple(proj2.shape)}")
+    out = torch.empty((b, n, 3), dtype=F32, device=q1.device)
+    finite = torch.empty((b, n), dtype=U8, device=q1.device)
+    N.call("mi_triangulate", N.dev(p1, F32, "proj1"), N.dev(p2, F32, "proj2"), N.dev(q1, F32, "pts1"), N.dev(q2, F32, "pts2"),
+           b, n, out.data_ptr(), finite.data_ptr(), N.stream_ptr())
+    return out, finite.view(torch.bool)

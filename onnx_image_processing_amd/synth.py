@@ -182,3 +182,52 @@ def synth_threshold_frame(seed: int, height: int = 480, width: int = 640, family
         v = centres[mode] + (h(yy, xx, 16, spread + 1) + h(yy, xx, 17, spread + 1) - spread)
     v = np.clip(v, 0, L - 1)
     return v.astype(np.uint8 if levels <= 256 else np.uint16)
+
+
+TWO_VIEW_IMAGE = (480, 640)            # (height, width) of synth_two_view's camera; principal point at (320, 240)
+
+
+def two_view_camera(f: float = 500.0) -> np.ndarray:
+    """float64 (3, 3) camera matrix of synth_two_view: focal length f, principal point (320, 240)."""
+    return np.array([[f, 0.0, TWO_VIEW_IMAGE[1] / 2.0], [0.0, f, TWO_VIEW_IMAGE[0] / 2.0], [0.0, 0.0, 1.0]])
+
+
+def synth_two_view(seed: int, n: int, outlier_fraction: float, noise_px: float, f: float = 500.0):
+    """A two-view scene for the relative-pose kernels: (keypoints1, keypoints2, R, t, inlier).  keypoints (n, 2) float32
+    in pixel (y, x) order under two_view_camera(f); R (3, 3), t (3,) float64 with x2 ~ R x1 + t and |t| = 1; inlier (n,)
+    bool, the planted inlier mask.  n points uniform in [-2, 2] x [-1.5, 1.5] x [3, 9] in the first camera's frame; R the
+    Rodrigues rotation of a N(0, 0.08^2) vector; a baseline of 0.4 in a uniformly random direction; N(0, noise_px^2) added
+    to both views' pixels; round(outlier_fraction * n) correspondences, chosen by a hashed ranking, have their second-view
+    point replaced by a uniform draw over the image.  float64 arithmetic on hashed integers: the same scene everywhere."""
+    idx = np.arange(n, dtype=np.uint64)
+
+    def uni(salt, count=n):
+        """uniform (0, 1) float64, `count` draws"""
+        i = np.arange(count, dtype=np.uint64)
+        return ((_hash3(seed, i, np.uint64(salt) + 0 * i, 21) >> np.uint64(11)).astype(np.float64) + 0.5) / float(1 << 53)
+
+    def normal(salt, count=n):
+        return np.sqrt(-2.0 * np.log(uni(salt, count))) * np.cos(2.0 * np.pi * uni(salt + 1, count))
+
+    pts = np.stack([-2.0 + 4.0 * uni(0), -1.5 + 3.0 * uni(1), 3.0 + 6.0 * uni(2)], axis=1)
+    w = 0.08 * normal(3, 3)
+    th = float(np.linalg.norm(w))
+    k = w / th if th > 0 else np.array([0.0, 0.0, 1.0])
+    kx = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    R = np.eye(3) + np.sin(th) * kx + (1.0 - np.cos(th)) * (kx @ kx)
+    d = normal(5, 3)
+    t = d / np.linalg.norm(d)
+    K = two_view_camera(f)
+    x1 = pts
+    x2 = pts @ R.T + 0.4 * t
+    px1 = (x1 / x1[:, 2:]) @ K.T
+    px2 = (x2 / x2[:, 2:]) @ K.T
+    px1 = px1[:, :2] + noise_px * np.stack([normal(7), normal(9)], axis=1)
+    px2 = px2[:, :2] + noise_px * np.stack([normal(11), normal(13)], axis=1)
+    n_out = int(round(outlier_fraction * n))
+    order = np.argsort(_hash3(seed, idx, np.uint64(15) + 0 * idx, 21), kind="stable")
+    inlier = np.ones(n, dtype=bool)
+    inlier[order[:n_out]] = False
+    rand_px = np.stack([TWO_VIEW_IMAGE[1] * uni(16), TWO_VIEW_IMAGE[0] * uni(17)], axis=1)
+    px2[~inlier] = rand_px[~inlier]
+    return (px1[:, ::-1].astype(np.float32), px2[:, ::-1].astype(np.float32), R, t, inlier)

@@ -1,0 +1,390 @@
+"""K15 relative pose on the GPU against tests/pose_oracle.py (the fp64 numpy restatement of include/mi355x_match.h).
+
+Tolerances.  fp32 kernels against an fp64 oracle cannot agree bit for bit, so every tolerance below is the deviation of the
+SAME oracle run in float32 from its float64 run (measured on the CPU on the scenes these tests use), times the margin the
+issue sets for the different operation order (4 for values, 2 for angles):
+  - per-hypothesis parity (noisy scenes, n = 64 / 97, H = 200 and n = 64, H = 256): the float32 oracle had the float64
+    oracle's inlier count on 100 % of the hypotheses of all 18 scenes (cap to hold here: |dcount| <= 1 on >= 90 %); on
+    hypotheses of equal count its MSAC cost deviated by at most 2.96e-4 relative -> COST_RTOL = 1.2e-3;
+  - refit on the planted inliers (n = 64 / 97, noise 0 and 0.5 px): min(|E - E0|, |E + E0|) at |.|_F = sqrt(2) was at
+    most 1.54e-4 -> REFIT_TOL = 6.2e-4;
+  - ground truth (noise-free, 25 % / 40 % outliers, the 24 scenes of GROUND_TRUTH_CASES): the float32 oracle marked every
+    planted inlier with at most 1 false inlier, rotation error <= 0.0213 deg and translation-direction error <= 1.31 deg (the
+    worst cases are the scenes with a false inlier in the final refit) -> ROT_DEG = 0.043, TDIR_DEG = 2.62, at most 2 false;
+  - triangulation, points with >= 1 deg of parallax (noise 0.5 px): relative deviation <= 2.22e-6 -> TRI_RTOL = 9e-6.
+Every seed of GROUND_TRUTH_CASES has an all-inlier sample under the sampler (the test re-checks it): 0 seeds dropped."""
+import numpy as np
+import pytest
+import torch
+
+import pose_oracle as PO
+from onnx_image_processing_amd import _native as N
+from onnx_image_processing_amd import ops
+from onnx_image_processing_amd.pytorch_model.geometry import RelativePoseEstimator, triangulate_points
+from onnx_image_processing_amd.synth import synth_two_view, two_view_camera
+
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
+DEV = "cuda:0"
+K = two_view_camera()
+F = 500.0
+THR = 1.0 / F
+COST_RTOL, REFIT_TOL, ROT_DEG, TDIR_DEG, TRI_RTOL = 1.2e-3, 6.2e-4, 0.043, 2.62, 9e-6
+GROUND_TRUTH_CASES = [(64, 256, 0.25, (200, 201, 202)), (64, 256, 0.25, (203, 204, 205)), (64, 256, 0.40, (200, 201, 202)),
+                      (64, 256, 0.40, (203, 204, 205)), (96, 512, 0.25, (200, 201, 202)), (96, 512, 0.25, (203, 204, 205)),
+                      (96, 512, 0.40, (200, 201, 202)), (96, 512, 0.40, (203, 204, 205))]
+GT_SEED = 11
+
+
+def scenes(seeds, n, outliers, noise):
+    """a batch of synth_two_view scenes: keypoints (B, n, 2) float32 pixel (y, x), lists of R, t, planted inlier masks"""
+    s = [synth_two_view(seed, n, outliers, noise) for seed in seeds]
+    return (np.stack([x[0] for x in s]), np.stack([x[1] for x in s]), [x[2] for x in s], [x[3] for x in s],
+            np.stack([x[4] for x in s]))
+
+
+def normalised(k1, k2):
+    """the kernels' own float32 normalised points, on the GPU and as the numpy arrays the oracle gets"""
+    k_inv = torch.from_numpy(np.linalg.inv(K)).float().to(DEV)
+    p1 = ops.normalise_keypoints(torch.from_numpy(k1).to(DEV), k_inv)
+    p2 = ops.normalise_keypoints(torch.from_numpy(k2).to(DEV), k_inv)
+    return p1, p2, p1.cpu().numpy(), p2.cpu().numpy()
+
+
+def test_sampler_all_inlier_hypotheses_explain_every_planted_inlier():
+    """noise-free scenes: a hypothesis whose 8 sampled ranks (the oracle's restatement of the header's sampler) are all
+    planted inliers is the true E, so its count reaches the number of planted inliers -- which it can only do if the
+    kernel drew those very rows.  Pair 1 has invalid rows (ranks are over the VALID rows)."""
+    n, H, seed = 64, 200, 5
+    k1, k2, _, _, inl = scenes((10, 11, 12), n, 0.25, 0.0)
+    valid = np.ones((3, n), bool)
+    valid[1, ::5] = False
+    p1, p2, _, _ = normalised(k1, k2)
+    _, _, count = ops.essential_hypotheses(p1, p2, torch.from_numpy(valid).to(DEV), H, THR, seed)
+    count = count.cpu().numpy()
+    checked = 0
+    for b in range(3):
+        vidx = np.flatnonzero(valid[b])
+        planted = int((inl[b] & valid[b]).sum())
+        for h in range(H):
+            rows = vidx[PO.sample_ranks(seed, b, h, len(vidx))]
+            if inl[b][rows].all():
+                checked += 1
+                assert count[b, h] >= planted, (b, h, count[b, h], planted)
+    assert checked >= 20, checked
+
+
+@pytest.mark.parametrize("n,H", [(64, 200), (97, 200)])
+def test_hypotheses_match_the_oracle_per_hypothesis(n, H):
+    seed = 7
+    k1, k2, _, _, _ = scenes((100, 101, 102), n, 0.25, 0.5)
+    p1, p2, q1, q2 = normalised(k1, k2)
+    e_h, cost, count = (x.cpu().numpy() for x in ops.essential_hypotheses(p1, p2, None, H, THR, seed))
+    for b in range(3):
+        oe, oc, ok_, _ = PO.hypotheses(q1[b], q2[b], None, H, THR, seed, b)
+        dk = np.abs(count[b].astype(np.int64) - ok_)
+        same = (dk == 0) & np.isfinite(oc) & np.isfinite(cost[b])
+        rel = np.abs(cost[b][same].astype(np.float64) - oc[same]) / oc[same]
+        print(f"n={n} H={H} pair {b}: equal counts {np.mean(dk == 0):.3f}, |dcount| <= 1 {np.mean(dk <= 1):.3f}, > 2 {np.mean(dk > 2):.3f}; "
+              f"cost rel dev on equal counts max {rel.max():.2e} median {np.median(rel):.2e}; inf {np.isinf(cost[b]).sum()} / {np.isinf(oc).sum()}")
+        assert np.mean(dk <= 1) >= 0.90
+        assert rel.max() <= COST_RTOL
+        de = np.array([PO.e_distance(e_h[b, h], oe[h]) for h in np.flatnonzero(same)])
+        print(f"    |dE| on equal counts: max {de.max():.2e} median {np.median(de):.2e}")
+
+
+def test_degenerate_pairs_and_small_shapes():
+    """n = 9: 9 valid rows / 7 valid rows / no valid row; n = 8 with H = 1"""
+    k1, k2, _, _, _ = scenes((20, 21, 22), 9, 0.0, 0.0)
+    valid = np.ones((3, 9), bool)
+    valid[1, 7:] = False
+    valid[2] = False
+    p1, p2, q1, q2 = normalised(k1, k2)
+    v = torch.from_numpy(valid).to(DEV)
+    e_h, cost, count = ops.essential_hypotheses(p1, p2, v, 64, THR, 3)
+    assert torch.isinf(cost[1:]).all() and (cost[1:] > 0).all() and not count[1:].any() and not e_h[1:].any()
+    fin = torch.isfinite(cost[0])                                              # a 9-row pair: every sample is 8 of its rows
+    assert fin.float().mean() >= 0.5 and (count[0][fin] >= 8).all() and not count[0][~fin].any()
+    e, inlier, best_h, cnt = ops.essential_ransac(p1, p2, v, 64, THR, 3, 3)
+    assert not e[1:].any() and not inlier[1:].any() and cnt[1:].tolist() == [0, 0] and best_h[1:].tolist() == [0, 0]
+    assert int(cnt[0]) == 9 and inlier[0].all()
+    r, t, pm, pc, ok = ops.recover_pose(e, p1, p2, inlier)
+    assert ok.tolist() == [True, False, False] and torch.equal(r[1], torch.eye(3, device=DEV)) and not t[1:].any() and not pm[1:].any()
+    e2, ok2 = ops.essential_refit(p1, p2, v)
+    assert ok2.tolist() == [True, False, False] and not e2[1:].any()
+    k1, k2, R, t0, _ = scenes((23, 24, 25), 8, 0.0, 0.0)
+    p1, p2, q1, q2 = normalised(k1, k2)
+    e_h, cost, count = ops.essential_hypotheses(p1, p2, None, 1, THR, 0)
+    assert e_h.shape == (3, 1, 3, 3) and (count == 8).all()                    # the only possible sample: all 8 rows
+    for b in range(3):                                                         # the solution fits its own 8 rows to 0.05 px
+        d2 = PO.sampson(e_h[b, 0].cpu().numpy().astype(np.float64), q1[b].astype(np.float64), q2[b].astype(np.float64))
+        assert d2.max() < (0.05 * THR) ** 2
+
+
+@pytest.mark.parametrize("n,H", [(64, 1), (97, 64), (64, 200)])
+def test_selection_is_exact(n, H):
+    k1, k2, _, _, _ = scenes((100, 101, 102), n, 0.25, 0.5)
+    valid = np.ones((3, n), bool)
+    valid[2, 3::7] = False
+    p1, p2, q1, q2 = normalised(k1, k2)
+    v = torch.from_numpy(valid).to(DEV)
+    e_h, cost, count = ops.essential_hypotheses(p1, p2, v, H, THR, 9)
+    e, inlier, best_h, cnt = ops.essential_ransac(p1, p2, v, H, THR, 0, 9)
+    cost_np = cost.cpu().numpy()
+    for b in range(3):
+        bh = int(np.argmin(cost_np[b]))                                        # numpy: the first minimum
+        assert int(best_h[b]) == bh
+        assert torch.equal(e[b], e_h[b, bh]) and int(cnt[b]) == int(count[b, bh]) == int(inlier[b].sum())
+        assert not (inlier[b].cpu().numpy() & ~valid[b]).any()
+        d2 = PO.sampson(e[b].cpu().numpy().astype(np.float64), q1[b].astype(np.float64), q2[b].astype(np.float64))
+        clear = np.abs(d2 / THR ** 2 - 1) > 1e-3                               # not within rounding of the threshold
+        assert np.array_equal(inlier[b].cpu().numpy()[clear], ((d2 <= THR ** 2) & valid[b])[clear])
+    # refinement never makes the cost worse
+    e3, inl3, bh3, cnt3 = ops.essential_ransac(p1, p2, v, H, THR, 3, 9)
+    assert torch.equal(bh3, best_h)
+    for b in range(3):
+        c0 = PO.score(e[b].cpu().numpy().astype(np.float64), q1[b][valid[b]].astype(np.float64), q2[b][valid[b]].astype(np.float64), THR)[0]
+        c3 = PO.score(e3[b].cpu().numpy().astype(np.float64), q1[b][valid[b]].astype(np.float64), q2[b][valid[b]].astype(np.float64), THR)[0]
+        assert c3 <= c0 * (1 + COST_RTOL)
+
+
+@pytest.mark.parametrize("n,noise", [(64, 0.0), (64, 0.5), (97, 0.0), (97, 0.5)])
+def test_refit_matches_the_oracle(n, noise):
+    k1, k2, _, _, inl = scenes((100, 101, 102), n, 0.25, noise)
+    inl[1, :] &= np.arange(n) % 3 != 0                                         # a middle pair with a different mask
+    p1, p2, q1, q2 = normalised(k1, k2)
+    e, ok = ops.essential_refit(p1, p2, torch.from_numpy(inl).to(DEV))
+    assert ok.all()
+    for b in range(3):
+        ref, _ = PO.refit(q1[b], q2[b], inl[b])
+        d = PO.e_distance(e[b].cpu().numpy(), ref)
+        print(f"refit n={n} noise={noise} pair {b}: |dE| = {d:.2e}")
+        assert d <= REFIT_TOL
+    few = np.zeros((3, n), bool)
+    few[:, :7] = True
+    e, ok = ops.essential_refit(p1, p2, torch.from_numpy(few).to(DEV))
+    assert not ok.any() and not e.any()
+
+
+@pytest.mark.parametrize("n,H,outliers,seeds", GROUND_TRUTH_CASES)
+def test_ground_truth_pose_on_noise_free_scenes(n, H, outliers, seeds):
+    k1, k2, R, t, inl = scenes(seeds, n, outliers, 0.0)
+    for b in range(3):                                                         # every kept seed has an all-inlier sample
+        assert any(inl[b][PO.sample_ranks(GT_SEED, b, h, n)].all() for h in range(H)), seeds[b]
+    m = RelativePoseEstimator(torch.from_numpy(K), num_hypotheses=H, ransac_threshold=1.0, refine_rounds=3, seed=GT_SEED).to(DEV)
+    Rg, tg, mask, E, ok = m(torch.from_numpy(k1).to(DEV), torch.from_numpy(k2).to(DEV))
+    p1, p2, _, _ = normalised(k1, k2)
+    _, ransac_inl, _, _ = ops.essential_ransac(p1, p2, None, H, THR, 3, GT_SEED)
+    for b in range(3):
+        got, rin = mask[b].cpu().numpy(), ransac_inl[b].cpu().numpy()
+        rot, td = PO.rotation_angle_deg(Rg[b].cpu().numpy(), R[b]), PO.direction_angle_deg(tg[b].cpu().numpy(), t[b])
+        print(f"n={n} H={H} outliers={outliers} seed {seeds[b]}: recall {(rin & inl[b]).sum() / inl[b].sum():.3f}, false {(rin & ~inl[b]).sum()}, "
+              f"rotation {rot:.4f} deg, t direction {td:.4f} deg")
+        assert bool(ok[b]) and (rin & inl[b]).sum() == inl[b].sum() and (got & inl[b]).sum() == inl[b].sum()
+        assert (rin & ~inl[b]).sum() <= 2
+        assert rot <= ROT_DEG and td <= TDIR_DEG
+        assert abs(float(torch.linalg.det(Rg[b].double().cpu())) - 1) < 1e-5 and abs(float(tg[b].norm()) - 1) < 1e-5
+
+
+def test_noisy_scene_accuracy_is_reported():
+    """0.5 px noise, 25 % outliers, 16 scenes at n = 96, H = 256: medians and worst cases are PRINTED (DESIGN.md K15 records
+    them); 8-point RANSAC with local optimisation has a long error tail, so only ok = 1 is asserted"""
+    rots, tds, recalls = [], [], []
+    m = RelativePoseEstimator(torch.from_numpy(K), num_hypotheses=256).to(DEV)
+    for first in range(400, 416, 4):
+        k1, k2, R, t, inl = scenes(range(first, first + 4), 96, 0.25, 0.5)
+        Rg, tg, mask, _, ok = m(torch.from_numpy(k1).to(DEV), torch.from_numpy(k2).to(DEV))
+        assert ok.all()
+        for b in range(4):
+            rots.append(PO.rotation_angle_deg(Rg[b].cpu().numpy(), R[b]))
+            tds.append(PO.direction_angle_deg(tg[b].cpu().numpy(), t[b]))
+            recalls.append((mask[b].cpu().numpy() & inl[b]).sum() / inl[b].sum())
+    print(f"noisy scenes (16): rotation median {np.median(rots):.3f} worst {np.max(rots):.3f} deg; t direction median "
+          f"{np.median(tds):.2f} worst {np.max(tds):.2f} deg; inlier recall median {np.median(recalls):.3f} worst {np.min(recalls):.3f}")
+
+
+def project(X, R, t):
+    x = X @ np.asarray(R).T + np.asarray(t)
+    return (x[:, :2] / x[:, 2:]).astype(np.float32)
+
+
+def test_recover_pose_reaches_all_four_candidates():
+    """true poses of six scenes, each handed E and -E: the oracle says which of the four candidates is the true one, all
+    four occur, and the kernel returns the true R, t for every one (float32 products of O(1) values: 0.01 deg is ~100
+    roundings of 6e-8 rad-sized errors)"""
+    n = 64
+    k1, k2, R, t, _ = scenes(range(6), n, 0.0, 0.0)
+    p1, p2, q1, q2 = normalised(k1, k2)
+    E = np.stack([s * PO.essential_from_pose(R[b], t[b]) * (1.0 + b) for b in range(6) for s in (1.0, -1.0)])   # any scale
+    idx = [b for b in range(6) for _ in (0, 1)]
+    P1, P2 = p1[idx].contiguous(), p2[idx].contiguous()
+    r, tt, pm, cnt, ok = ops.recover_pose(torch.from_numpy(E).float().to(DEV), P1, P2, None)
+    cands = set()
+    for j, b in enumerate(idx):
+        _, _, opm, ocnt, ook, cand = PO.recover_pose(E[j], q1[b], q2[b], None)
+        cands.add(cand)
+        assert bool(ok[j]) and int(cnt[j]) == ocnt == n and pm[j].all()
+        assert PO.rotation_angle_deg(r[j].cpu().numpy(), R[b]) < 0.01 and PO.direction_angle_deg(tt[j].cpu().numpy(), t[b]) < 0.01
+    assert cands == {0, 1, 2, 3}
+
+
+def test_recover_pose_masks_ties_and_the_distance_cut():
+    rng = np.random.default_rng(5)
+    n = 16
+    k = np.array([0.03, -0.05, 0.02])
+    th = np.linalg.norm(k)
+    kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]]) / th
+    R = np.eye(3) + np.sin(th) * kx + (1 - np.cos(th)) * kx @ kx
+    t = np.array([0.8, 0.0, 0.6])                                              # unit baseline: depths are in baselines
+    X = np.stack([rng.uniform(-2, 2, n), rng.uniform(-1.5, 1.5, n), rng.uniform(5, 20, n)], axis=1)
+    X[3] = [1.0, 0.5, 100.0]                                                   # beyond the default cut of 50, inside 200
+    x1, x2 = project(X, np.eye(3), np.zeros(3)), project(X, R, t)
+    x2[5] = x2[5] + 0.3                                                        # a gross outlier that is IN the mask
+    E = torch.from_numpy(PO.essential_from_pose(R, t)[None]).float().to(DEV)
+    P1, P2 = torch.from_numpy(x1[None]).to(DEV), torch.from_numpy(x2[None]).to(DEV)
+    mask = np.ones((1, n), bool)
+    mask[0, 12:] = False
+    mk = torch.from_numpy(mask).to(DEV)
+    r, tt, pm, cnt, ok = ops.recover_pose(E, P1, P2, mk, 50.0)
+    opm = PO.recover_pose(E[0].cpu().numpy(), x1, x2, mask[0], 50.0)[2]
+    assert bool(ok[0]) and not (pm[0].cpu().numpy() & ~mask[0]).any() and int(cnt[0]) == int(pm[0].sum())
+    assert not bool(pm[0, 3]) and bool(pm[0, 0]) and np.array_equal(pm[0].cpu().numpy(), opm)
+    assert PO.rotation_angle_deg(r[0].cpu().numpy(), R) < 0.01 and PO.direction_angle_deg(tt[0].cpu().numpy(), t) < 0.01
+    r2, _, pm2, cnt2, _ = ops.recover_pose(E, P1, P2, mk, 200.0)
+    assert bool(pm2[0, 3]) and int(cnt2[0]) == int(cnt[0]) + 1                 # the far point passes a wider cut
+    # fewer than 5 passing rows: ok = 0, identity, zero, the count and the mask still reported
+    four = np.zeros((1, n), bool)
+    four[0, [0, 1, 2, 4]] = True
+    r, tt, pm, cnt, ok = ops.recover_pose(E, P1, P2, torch.from_numpy(four).to(DEV))
+    assert not bool(ok[0]) and int(cnt[0]) == 4 and torch.equal(r[0], torch.eye(3, device=DEV)) and not tt.any()
+    assert np.array_equal(pm[0].cpu().numpy(), four[0])
+    # a tie between all four candidates (an empty mask: 0 rows each): the first wins, nothing passes
+    r, tt, pm, cnt, ok = ops.recover_pose(E, P1, P2, torch.zeros((1, n), dtype=torch.bool, device=DEV))
+    assert not bool(ok[0]) and int(cnt[0]) == 0 and not pm.any() and torch.equal(r[0], torch.eye(3, device=DEV))
+    # a zero and a NaN matrix
+    bad = torch.zeros((2, 3, 3), device=DEV)
+    bad[1] = float("nan")
+    r, tt, pm, cnt, ok = ops.recover_pose(bad, P1.expand(2, n, 2), P2.expand(2, n, 2), None)
+    assert not ok.any() and not cnt.any() and not pm.any() and torch.equal(r, torch.eye(3, device=DEV).expand(2, 3, 3)) and not tt.any()
+
+
+def test_triangulate_matches_the_oracle():
+    k1, k2, R, t, _ = scenes((300, 301, 302), 97, 0.0, 0.5)
+    P1 = np.stack([K @ np.hstack([np.eye(3), np.zeros((3, 1))])] * 3)
+    P2 = np.stack([K @ np.hstack([R[b], 0.4 * t[b][:, None]]) for b in range(3)])
+    x1, x2 = np.ascontiguousarray(k1[..., ::-1]), np.ascontiguousarray(k2[..., ::-1])
+    pts, fin = ops.triangulate(torch.from_numpy(P1).float().to(DEV), torch.from_numpy(P2).float().to(DEV),
+                               torch.from_numpy(x1).to(DEV), torch.from_numpy(x2).to(DEV))
+    wrapped = triangulate_points(torch.from_numpy(k1).to(DEV), torch.from_numpy(k2).to(DEV), torch.eye(3), torch.zeros(3),
+                                 torch.from_numpy(np.stack(R)), torch.from_numpy(np.stack([0.4 * x for x in t])), torch.from_numpy(K))
+    single = triangulate_points(torch.from_numpy(k1[1]).to(DEV), torch.from_numpy(k2[1]).to(DEV), torch.eye(3), torch.zeros(3, 1),
+                                torch.from_numpy(R[1]), torch.from_numpy(0.4 * t[1]), torch.from_numpy(K))
+    assert single.shape == (97, 3)
+    checked = 0
+    for b in range(3):
+        ref, rfin = PO.triangulate(P1[b].astype(np.float32), P2[b].astype(np.float32), x1[b], x2[b])
+        r1 = np.concatenate([PO.normalise(k1[b], K), np.ones((97, 1))], 1)
+        r2 = np.concatenate([PO.normalise(k2[b], K), np.ones((97, 1))], 1) @ R[b]
+        par = np.array([PO.direction_angle_deg(u, v) for u, v in zip(r1, r2)]) >= 1.0
+        rel = np.linalg.norm(pts[b].cpu().numpy()[par] - ref[par], axis=1) / np.linalg.norm(ref[par], axis=1)
+        print(f"triangulate pair {b}: {par.sum()} points with >= 1 deg parallax, relative deviation max {rel.max():.2e}")
+        assert fin[b].cpu().numpy()[par].all() and rfin[par].all() and rel.max() <= TRI_RTOL
+        # the wrapper's (y, x) handling and its K [R | t], batched and unbatched: the same projection matrices up to the last
+        # bit of one float32 rounding (a float64 product here and there, possibly summed in another order), so the same
+        # points to the oracle tolerance where the parallax bounds the amplification
+        for name, w in (("batched", wrapped[b]), ("unbatched", single if b == 1 else None)):
+            if w is None:
+                continue
+            dw = ((w - pts[b]).norm(dim=-1) / pts[b].norm(dim=-1)).cpu().numpy()[par]
+            print(f"    triangulate_points ({name}) against ops.triangulate: relative deviation max {dw.max():.2e}")
+            assert dw.max() <= TRI_RTOL
+        checked += int(par.sum())
+    assert checked > 150
+    # identical rays under identical cameras: zeros, finite = 0
+    p, f = ops.triangulate(torch.from_numpy(P1).float().to(DEV), torch.from_numpy(P1).float().to(DEV),
+                           torch.from_numpy(x1).to(DEV), torch.from_numpy(x1).to(DEV))
+    assert not f.any() and not p.any()
+
+
+def _raw_calls(p1, p2, v, H, rounds, seed, fill):
+    """essential_hypotheses, essential_ransac and recover_pose through the C ABI into outputs and a workspace that were
+    filled with `fill` bytes first"""
+    b, n = p1.shape[:2]
+
+    def dirty(shape, dtype):
+        t = torch.empty(shape, dtype=dtype, device=DEV)
+        t.view(torch.uint8).fill_(fill)
+        return t
+    e_h, cost, count = dirty((b, H, 3, 3), torch.float32), dirty((b, H), torch.float32), dirty((b, H), torch.int32)
+    N.call("mi_essential_hypotheses", p1.data_ptr(), p2.data_ptr(), v.data_ptr(), b, n, H, THR, seed, e_h.data_ptr(),
+           cost.data_ptr(), count.data_ptr(), N.stream_ptr())
+    wbytes = int(N.load().mi_essential_ransac_workspace_bytes(b, n, H))
+    ws = dirty((wbytes,), torch.uint8)
+    e, inl = dirty((b, 3, 3), torch.float32), dirty((b, n), torch.uint8)
+    bh, cnt = dirty((b,), torch.int32), dirty((b,), torch.int32)
+    N.call("mi_essential_ransac", p1.data_ptr(), p2.data_ptr(), v.data_ptr(), b, n, H, THR, rounds, seed, e.data_ptr(),
+           inl.data_ptr(), bh.data_ptr(), cnt.data_ptr(), ws.data_ptr(), wbytes, N.stream_ptr())
+    r, t, pm = dirty((b, 3, 3), torch.float32), dirty((b, 3), torch.float32), dirty((b, n), torch.uint8)
+    pc, ok = dirty((b,), torch.int32), dirty((b,), torch.uint8)
+    N.call("mi_recover_pose", e.data_ptr(), p1.data_ptr(), p2.data_ptr(), inl.data_ptr(), b, n, 50.0, r.data_ptr(), t.data_ptr(),
+           pm.data_ptr(), pc.data_ptr(), ok.data_ptr(), N.stream_ptr())
+    return [e_h, cost, count, e, inl, bh, cnt, r, t, pm, pc, ok]
+
+
+def _same_bits(a, b):
+    return all(torch.equal(x.contiguous().view(torch.uint8), y.contiguous().view(torch.uint8)) for x, y in zip(a, b))
+
+
+def test_outputs_are_fully_written_reproducible_and_blind_to_invalid_rows():
+    n, H = 97, 200
+    k1, k2, _, _, _ = scenes((100, 101, 102), n, 0.25, 0.5)
+    valid = np.ones((3, n), np.uint8)
+    valid[0, 5::9] = 0
+    valid[1, :7] = 0
+    p1, p2, _, _ = normalised(k1, k2)
+    v = torch.from_numpy(valid).to(DEV)
+    a = _raw_calls(p1, p2, v, H, 3, 21, 0xFF)                                   # 0xFF bytes: NaN floats, -1 integers
+    b = _raw_calls(p1, p2, v, H, 3, 21, 0x00)
+    assert _same_bits(a, b)                                                    # every output byte written; two runs agree
+    assert not any(torch.isnan(x).any() for x in (a[0], a[1], a[3], a[7], a[8]))
+    assert set(torch.unique(a[4]).tolist()) <= {0, 1} and set(torch.unique(a[9]).tolist()) <= {0, 1}
+    assert not (a[4].bool() & ~v.bool()).any() and not (a[9].bool() & ~a[4].bool()).any()     # pose_mask <= inlier <= valid
+    q1, q2 = p1.clone(), p2.clone()
+    q1[~v.bool()] = float("nan")                                               # invalid rows: any coordinates at all
+    q2[~v.bool()] = 1e30
+    assert _same_bits(a, _raw_calls(q1, q2, v, H, 3, 21, 0xFF))
+    # the entries without a sampler do not depend on the batch position
+    perm = [2, 0, 1]
+    pv = v[perm].contiguous()
+    e_p, ok_p = ops.essential_refit(p1[perm].contiguous(), p2[perm].contiguous(), pv)
+    e_0, ok_0 = ops.essential_refit(p1, p2, v)
+    assert torch.equal(e_p, e_0[perm]) and torch.equal(ok_p, ok_0[perm])
+    out_p = ops.recover_pose(a[3][perm].contiguous(), p1[perm].contiguous(), p2[perm].contiguous(), a[4][perm].contiguous())
+    assert all(torch.equal(x, y[perm]) for x, y in zip(out_p, (a[7], a[8], a[9].bool(), a[10], a[11].bool())))
+
+
+def test_ransac_and_recover_pose_replay_from_one_graph():
+    n, H = 64, 64
+    sets = [scenes(s, n, 0.25, 0.5)[:2] for s in ((100, 101, 102), (103, 104, 105), (106, 107, 108))]
+    pts = [normalised(k1, k2)[:2] for k1, k2 in sets]
+    v = torch.ones((3, n), dtype=torch.bool, device=DEV)
+
+    def run(p1, p2):
+        e, inl, bh, cnt = ops.essential_ransac(p1, p2, v, H, THR, 3, 4)
+        return (e, inl, bh, cnt) + tuple(ops.recover_pose(e, p1, p2, inl))
+    eager = [[x.clone() for x in run(p1, p2)] for p1, p2 in pts]
+    s1, s2 = pts[0][0].clone(), pts[0][1].clone()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        run(s1, s2)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        out = run(s1, s2)
+    for i in (1, 2, 0):
+        s1.copy_(pts[i][0])
+        s2.copy_(pts[i][1])
+        g.replay()
+        torch.cuda.synchronize()
+        assert all(torch.equal(x, y) for x, y in zip(out, eager[i])), i
