@@ -127,7 +127,8 @@ MI_API int mi_corner_response(const float *image, int n, int h, int w, int block
  * uint8 frame itself: the same results as the float32 entry point on the converted frame, bit for bit, with 1 instead
  * of 4 bytes per pixel read (corner response: 5 instead of 8 B/px of HBM traffic; a pair costs 0.6 instead of
  * 2.5 MB of PCIe when frames are streamed from the host).  mi_convert_u8_f32 is that conversion on the device, for
- * the entry points that have no uint8 form. */
+ * the entry points that have no uint8 form.  The first two thirds of that host function -- colour to gray, resize to
+ * the model's resolution -- are mi_ingest_frames at the end of this header. */
 MI_API int mi_corner_response_u8(const uint8_t *image, int n, int h, int w, int block_size, float *score,
                           mi_stream_t stream);
 MI_API int mi_convert_u8_f32(const uint8_t *src, long long count, float *dst, mi_stream_t stream);
@@ -765,6 +766,46 @@ MI_API int mi_recover_pose(const float *e, const float *pts1, const float *pts2,
  * every point of the ray is a solution -- also gives zeros and finite = 0.  One thread per point. */
 MI_API int mi_triangulate(const float *proj1, const float *proj2, const float *pts1, const float *pts2, int batch, int n,
                           float *points, uint8_t *finite, mi_stream_t stream);
+
+/* ---- frame ingest (K16): sample/visual_odometry.py:65-92 load_image_from_array, sample/image_matching.py ------------
+ * What the reference's hosts do to every camera frame on the CPU before the model sees it -- cv2.cvtColor(BGR2GRAY),
+ * cv2.resize(..., (w, h), INTER_LINEAR), astype(float32) -- in one kernel on the device: the front door of the `_u8`
+ * entry points above (uint8 output) and of the float32 ones (float32 output).
+ *
+ * src: `batch` frames of src_h x src_w pixels of `channels` interleaved bytes (1, 3 or 4: HWC, as cameras and decoders
+ * deliver them), rows row_pitch bytes apart, frames frame_pitch bytes apart (a cropped view or a padded camera buffer
+ * goes in without a copy).  No alignment is required of src or of the pitches.  channel_order: MI_INGEST_BGR or
+ * MI_INGEST_RGB; the 4th of 4 channels is ignored, with 1 channel the order is ignored and the byte is the gray value.
+ * dst: (batch, 1, h, w) contiguous, uint8 or -- dst_is_f32 != 0 -- float32 holding exactly the uint8 values.  Only
+ * the bytes of src that belong to pixels are used, but the kernel reads whole aligned 16-byte blocks around them.
+ *
+ * THE ARITHMETIC, in integers (C's >> on non-negative int32; everything fits int32):
+ *   gray   g = (3735 B + 19235 G + 9798 R + 16384) >> 15
+ *   taps   along each axis, for destination index d, with scale = (double)src / (double)dst:
+ *            f = (float)((d + 0.5) * scale - 0.5);  s = floor(f);  f -= s;        (f: float32)
+ *            if (s < 0) { s = 0; f = 0; }    if (s >= src - 1) { s = src - 1; f = 0; }
+ *            second tap min(s + 1, src - 1);  w1 = rint(f * 2048), w0 = rint((1 - f) * 2048)
+ *            (float32 products, round to nearest even; nothing fused)
+ *   rows   r = g[s] * a0 + g[s + 1] * a1                       (horizontal pass, weights a of the x axis)
+ *   out    = (((b0 * (r_top >> 4)) >> 16) + ((b1 * (r_bot >> 4)) >> 16) + 2) >> 2      (weights b of the y axis)
+ * Gray is taken at the taps only, which equals gray-then-resize.  With src == dst sizes the formula is the identity on
+ * the gray image, and the kernel skips the blend there.
+ *
+ * This is OpenCV 4's 8-bit path (cvtColor's fixed-point BGR2GRAY, resize's INTER_LINEAR with 11-bit weights) restated
+ * from its sources AS REMEMBERED: no cv2 build was available to compare against, so agreement with cv2 is UNMEASURED.
+ * One known difference: OpenCV switches an exact 2x INTER_LINEAR downscale to its area path (the mean of 2 x 2 pixels);
+ * this entry keeps the formula above at every ratio.  The contract is the arithmetic stated here, not cv2.
+ *
+ * Checks before any launch: NULL src / dst -> MI_E_NULL; batch, src_h, src_w, h, w < 1 -> MI_E_SHAPE; channels not in
+ * {1, 3, 4}, channel_order not one of the two, any of the five extents > MI_INGEST_MAX_DIM, row_pitch < src_w * channels,
+ * row_pitch > 2^40, frame_pitch < row_pitch * src_h or frame_pitch > 2^48 -> MI_E_PARAM.  One launch; no allocation, no
+ * memset, no host synchronisation, no coefficient table copied to the device (the taps are computed in the kernel):
+ * capturable like the rest of the library. */
+enum { MI_INGEST_BGR = 0, MI_INGEST_RGB = 1 };
+#define MI_INGEST_MAX_DIM 16384
+MI_API int mi_ingest_frames(const uint8_t *src, int batch, int src_h, int src_w, int channels, long long row_pitch,
+                            long long frame_pitch, int channel_order, void *dst, int dst_is_f32, int h, int w,
+                            mi_stream_t stream);
 
 #ifdef __cplusplus
 }

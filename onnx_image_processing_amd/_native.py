@@ -121,6 +121,8 @@ SIGNATURES = {
     "mi_recover_pose": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                         c_void_p, c_void_p],
     "mi_triangulate": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "mi_ingest_frames": [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_longlong, ctypes.c_longlong, c_int, c_void_p, c_int,
+                         c_int, c_int, c_void_p],
 }
 
 
@@ -152,6 +154,7 @@ _RESTYPE = {"mi_essential_matrix_workspace_bytes": c_size_t, "mi_sinkhorn_dots_s
 MI_BAD_RAW, MI_BAD_SOFT, MI_BAD_HARD = 0, 1, 2
 MI_DIST_L2, MI_DIST_L1 = 0, 1
 MI_PIX_U8, MI_PIX_U16, MI_PIX_I32, MI_PIX_F32 = 0, 1, 2, 3
+MI_INGEST_BGR, MI_INGEST_RGB = 0, 1
 
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_debug.so")
 

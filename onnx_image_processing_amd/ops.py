@@ -1196,3 +1196,43 @@ def triangulate(proj1: torch.Tensor, proj2: torch.Tensor, pts1: torch.Tensor, pt
     N.call("mi_triangulate", N.dev(p1, F32, "proj1"), N.dev(p2, F32, "proj2"), N.dev(q1, F32, "pts1"), N.dev(q2, F32, "pts2"),
            b, n, out.data_ptr(), finite.data_ptr(), N.stream_ptr())
     return out, finite.view(torch.bool)
+
+
+# ---- K16 frame ingest (sample/visual_odometry.py:65-92 load_image_from_array) ------------------------------------------
+
+INGEST_MAX_DIM = 16384             # include/mi355x_match.h MI_INGEST_MAX_DIM
+_CHANNEL_ORDERS = {"bgr": N.MI_INGEST_BGR, "rgb": N.MI_INGEST_RGB}
+
+
+def ingest_frames(frames: torch.Tensor, height: int, width: int, *, channel_order: str = "bgr",
+                  out_dtype: torch.dtype = U8) -> torch.Tensor:
+    """Colour camera frames -> gray model frames in one launch (`mi_ingest_frames`): what the reference's hosts do on the
+    CPU with cv2.cvtColor(BGR2GRAY) + cv2.resize(INTER_LINEAR) + astype(float32), in the integer arithmetic the header
+    states.  frames: uint8 (B, Hs, Ws, C) or (Hs, Ws, C) with C in {1, 3, 4} (HWC; the 4th channel is ignored); a view
+    whose pixels are dense and whose rows / frames are pitched (a crop, a padded camera buffer) goes in by its strides
+    without a copy, anything else is made contiguous first.  -> (B, 1, height, width) of out_dtype (torch.uint8 for the
+    `_u8` entry points, torch.float32 holding the same values for the others)."""
+    if channel_order not in _CHANNEL_ORDERS:
+        raise ValueError(f"channel_order must be 'bgr' or 'rgb', got {channel_order!r}")
+    if out_dtype not in (U8, F32):
+        raise ValueError(f"out_dtype must be torch.uint8 or torch.float32, got {out_dtype}")
+    if frames.dim() == 3:
+        frames = frames.unsqueeze(0)
+    if frames.dim() != 4 or frames.shape[-1] not in (1, 3, 4):
+        raise RuntimeError(f"frames must have shape (B, Hs, Ws, C) or (Hs, Ws, C) with C in (1, 3, 4), got {tuple(frames.shape)}")
+    if not frames.is_cuda:
+        raise RuntimeError(f"frames must live on the GPU (got device {frames.device}); this package has no CPU path")
+    if frames.dtype != U8:
+        raise RuntimeError(f"frames must be torch.uint8, got {frames.dtype}")
+    b, hs, ws, c = frames.shape
+    height, width = int(height), int(width)
+    if min(b, hs, ws, height, width) < 1 or max(b, hs, ws, height, width) > INGEST_MAX_DIM:
+        raise RuntimeError(f"frame extents must be in 1 .. {INGEST_MAX_DIM}, got {tuple(frames.shape)} -> ({height}, {width})")
+    pitched = (frames.stride(3) == 1 and frames.stride(2) == c and frames.stride(1) >= ws * c
+               and frames.stride(0) >= hs * frames.stride(1))
+    if not pitched:
+        frames = frames.contiguous()
+    out = torch.empty((b, 1, height, width), dtype=out_dtype, device=frames.device)
+    N.call("mi_ingest_frames", frames.data_ptr(), b, hs, ws, c, frames.stride(1), frames.stride(0),
+           _CHANNEL_ORDERS[channel_order], out.data_ptr(), int(out_dtype == F32), height, width, N.stream_ptr())
+    return out

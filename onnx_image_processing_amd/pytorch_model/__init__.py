@@ -3,5 +3,6 @@
 Same class names, constructor arguments, defaults, ValueErrors, buffer names and forward()
 signatures as reference pytorch_model/{detector,utils,descriptor,matching,feature_detection,pointcloud,depth,threshold};
 the arithmetic runs in the hand-written gfx950 kernels behind include/mi355x_match.h.
-Inputs must be GPU tensors (there is no CPU fallback).
+Inputs must be GPU tensors (there is no CPU fallback).  `geometry.relative_pose` and `ingest` have no module in the
+reference: they are its hosts' OpenCV steps (pose from matches; colour frame to gray model frame) on the device.
 """

@@ -231,3 +231,23 @@ def synth_two_view(seed: int, n: int, outlier_fraction: float, noise_px: float, 
     rand_px = np.stack([TWO_VIEW_IMAGE[1] * uni(16), TWO_VIEW_IMAGE[0] * uni(17)], axis=1)
     px2[~inlier] = rand_px[~inlier]
     return (px1[:, ::-1].astype(np.float32), px2[:, ::-1].astype(np.float32), R, t, inlier)
+
+
+def synth_colour_frame(seed: int, height: int, width: int, channels: int = 3) -> np.ndarray:
+    """uint8 (height, width, channels) interleaved colour frame with structure, what a camera hands to the frame ingest:
+    synth_image(seed) at half the size, upsampled 2x by pixel repetition (so that its corners survive an ingest to half
+    the size), times a per-channel gain (0.9, 1.0, 0.8, then 1.0) plus +-6 of per-byte hashed noise.  A 4th channel is
+    filled like the others (the ingest ignores it).  The same frame everywhere."""
+    if channels not in (1, 3, 4):
+        raise ValueError(f"channels must be 1, 3 or 4, got {channels}")
+    small = synth_image(seed, (height + 1) // 2, (width + 1) // 2).astype(np.int64)
+    base = np.repeat(np.repeat(small, 2, axis=0), 2, axis=1)[:height, :width]
+    y = np.arange(height, dtype=np.uint64)[:, None]
+    x = np.arange(width, dtype=np.uint64)[None, :]
+    yy, xx = np.broadcast_arrays(y, x)
+    gains = (9, 10, 8, 10)
+    out = np.empty((height, width, channels), np.uint8)
+    for c in range(channels):
+        noise = (_hash3(seed, yy, xx, 40 + c) % np.uint64(13)).astype(np.int64) - 6
+        out[:, :, c] = np.clip(base * gains[c if channels > 1 else 1] // 10 + noise, 0, 255)
+    return out

@@ -12,6 +12,7 @@ MI355X implementation (the very same module objects, not copies):
     from pytorch_model.depth.depth_align import DepthAlignment
     from pytorch_model.threshold.otsu import OtsuThreshold
     from pytorch_model.threshold.multi_otsu import MultiOtsuThreshold
+    from pytorch_model.ingest import FrameIngest, scale_intrinsics      (no counterpart in the reference: its hosts' CPU step)
 
 The one sub-package outside the mirrored set (`vo`, host-side numpy / OpenCV and camera drivers) does not
 exist and raises ImportError.
