@@ -807,6 +807,105 @@ MI_API int mi_ingest_frames(const uint8_t *src, int batch, int src_h, int src_w,
                             long long frame_pitch, int channel_order, void *dst, int dst_is_f32, int h, int w,
                             mi_stream_t stream);
 
+/* ---- metric RGB-D pose (K17): matched keypoints + aligned depth -> the rigid motion between two frames, in the depth's units --
+ * K15 ends at a translation of unit length.  With a depth frame per image (aligned to the colour camera, mi_depth_align)
+ * the matched keypoints lift to 3-D points, and the motion X2 = R X1 + t follows with its scale from three correspondences.
+ * The reference has no such step (its odometry sample sums unit translations).  Five entries, batched over pairs, under the
+ * contract of the K15 section: pure functions of their arguments, no allocation, no synchronisation, no memset, one stream,
+ * no atomics, every sum in a fixed order (the same inputs and seed give the same bits), capturable into a hipGraph; outputs
+ * and workspace may hold anything on entry and every output element is written; MI_E_* before any launch.
+ * Row i of pair b is pts1[b][i] <-> pts2[b][i], (batch, n, 3) float32 points in the two camera frames; `valid` / `mask`
+ * (batch, n) bytes select rows (non-zero = use; valid may be NULL: every row).  Rows that are not selected are never read for
+ * their coordinates.  1 <= n <= MI_RIGID_MAX_N (a staged row is 24 bytes: 48 KB of rows and 4 KB of indices in LDS, three
+ * one-wave workgroups per CU for mi_rigid_hypotheses and mi_rigid_refit; the second kernel of mi_rigid_ransac adds 4 KB of
+ * flags and holds two), batch <= 65535 (MI_E_PARAM beyond; < 1: MI_E_SHAPE).
+ *
+ * Divergences from the usual host implementations (Open3D's RANSAC registration, OpenCV's estimateAffine3D), all deliberate:
+ *   - the model is a rotation and a translation (no scale, no shear), solved in closed form by Horn's unit-quaternion method;
+ *     the eigenvector is taken by a FIXED number of cyclic Jacobi sweeps, not by an iterative LAPACK routine;
+ *   - the best hypothesis is the one of minimum truncated cost sum min(d^2, thr^2) (MSAC), not of maximum inlier count;
+ *   - a fixed number of hypotheses, no adaptive stop; the sampler is K15's stateless counter-based hash;
+ *   - refinement is refine_rounds rounds of refit on the inliers (local optimisation), no ICP, no per-point weights;
+ *   - depth is read at the NEAREST pixel, never interpolated (interpolating across an occlusion edge invents surfaces).
+ *
+ * Sampling.  K15's draw(seed, b, h, s), unchanged (the counter is still 8 h + s), for the slots s = 0, 1, 2, with the same
+ *   without-replacement rule over the ranks of the valid rows: three distinct ranks.
+ * Solve.  For the sample's rows a_k (frame 1), b_k (frame 2), k = 0, 1, 2: centroids ca = ((a_0 + a_1) + a_2) / 3, cb
+ *   likewise; S[i][j] = sum over k in order of (a_k - ca)_i (b_k - cb)_j; Horn's symmetric matrix
+ *       N = [ Sxx+Syy+Szz   Syz-Szy        Szx-Sxz        Sxy-Syx     ]
+ *           [     .         Sxx-Syy-Szz    Sxy+Syx        Szx+Sxz     ]
+ *           [     .             .         -Sxx+Syy-Szz    Syz+Szy     ]
+ *           [     .             .              .         -Sxx-Syy+Szz ]
+ *   the unit eigenvector q = (q0, qx, qy, qz) of N's largest eigenvalue by cyclic Jacobi: 6 sweeps over the pairs (0,1) (0,2)
+ *   (0,3) (1,2) (1,3) (2,3) in this order, each pair rotated by the angle that zeroes its off-diagonal element (skipped when
+ *   that element is exactly 0), the eigenvalue lambda_m being the first maximum of the final diagonal and q column m of the
+ *   accumulated rotations V (the kernels' arithmetic run on the CPU returns the same bits for 4 to 12 sweeps on the test
+ *   scenes; 3 sweeps leave 0.18 deg).  Then ONE correction against N itself: w = N q - lambda_m q with float64 products,
+ *   q = q + sum over j != m of ((v_j . w) / (lambda_m - lambda_j)) v_j.  Three points span a plane, so N's eigenvalues come
+ *   in +- pairs and the two largest of a slim triangle lie within a percent of each other; the rotations' accumulated
+ *   roundings (a few eps |N|) then turn into 4e-3 deg, which this step takes back to 3.5e-4 deg, the level of LAPACK's
+ *   float32 eigh (3.1e-4 deg on the same 192 samples).  q is scaled to unit length and negated when q0 < 0; R is the
+ *   rotation matrix of q; t = cb - R ca.
+ * Degenerate sample.  With e1 = p_1 - p_0 and e2 = p_2 - p_0, a sample is degenerate in a frame when
+ *   |e1 x e2|^2 <= 1e-6 |e1|^2 |e2|^2 (collinear or repeated points).  Degeneracy in either frame, fewer than 3 valid rows
+ *   or a non-finite result give cost = +inf, count = 0 and zeros in rt_h.
+ * Score.  For every valid row u = ((R X1) + t) - X2, each component ((R_j0 x + R_j1 y) + R_j2 z) + t_j - X2_j in this order,
+ *   d^2 = (u_0^2 + u_1^2) + u_2^2; inlier: d^2 <= thr^2; count = number of inliers, cost = sum over the valid rows in index
+ *   order of min(d^2, thr^2), float32. */
+#define MI_RIGID_MAX_N 2048
+
+/* keypoints (batch, n, 2) pixel (y, x) + depth (batch, h, w) -> points (batch, n, 3) float32 in the camera frame and valid
+ * (batch, n) bytes; one thread per keypoint.  depth: float32 (depth_is_u16 = 0) or uint16 counts (1; converted exactly), as
+ * in mi_depth_to_points, ALREADY aligned to the camera of k_inv (3x3 row-major inverse camera matrix, device memory).
+ *     xn = (x k_inv[0] + y k_inv[1]) + k_inv[2];  yn = (x k_inv[3] + y k_inv[4]) + k_inv[5]      mi_normalise_keypoints' bits
+ *     px = floorf(x + 0.5f);  py = floorf(y + 0.5f);  d = depth[b][py][px];  Z = d * z_scale       one float32 product
+ *     point = (xn * Z, yn * Z, Z)
+ * A row is valid when valid_in (batch, n; NULL: every row) is non-zero, the keypoint is finite, 0 <= px < w, 0 <= py < h,
+ * d is finite and min_depth <= Z <= max_depth.  Invalid rows get a zero point and a zero byte; their depth is not read
+ * when the pixel is outside the frame.  batch, n, h, w < 1: MI_E_SHAPE; min_depth <= 0, max_depth < min_depth or not
+ * finite, z_scale <= 0 or not finite: MI_E_PARAM.  One launch. */
+MI_API int mi_lift_keypoints(const float *keypoints, const void *depth, int depth_is_u16, int batch, int n, int h, int w,
+                             const float *k_inv, float z_scale, float min_depth, float max_depth, const uint8_t *valid_in,
+                             float *points, uint8_t *valid, mi_stream_t stream);
+
+/* H = num_hypotheses hypotheses per pair, generated and scored: rt_h (batch, H, 12) = R row-major, then t; cost (batch, H)
+ * float32, count (batch, H) int32.  H < 1: MI_E_SHAPE; H > MI_POSE_MAX_HYPOTHESES, threshold <= 0 or not finite:
+ * MI_E_PARAM.  threshold is in the units of the points.  One launch: ceil(H / 64) x batch waves, a lane per hypothesis. */
+MI_API int mi_rigid_hypotheses(const float *pts1, const float *pts2, const uint8_t *valid, int batch, int n,
+                               int num_hypotheses, float threshold, uint32_t seed, float *rt_h, float *cost, int32_t *count,
+                               mi_stream_t stream);
+
+/* r (batch, 3, 3), t (batch, 3) from the rows with mask != 0 (mask is required), in two passes: the centroids ca, cb (sums
+ * lanes-strided, then / m for m rows), then the centred products S = sum (a - ca)(b - cb)^T, Ca = sum (a - ca)(a - ca)^T and
+ * Cb likewise; the solve of the section above from S.  The set is DEGENERATE when the second largest eigenvalue of Ca or of
+ * Cb (cyclic Jacobi as above on the 3x3 matrix, pairs (0,1) (0,2) (1,2)) is not above 1e-6 times the largest: the points
+ * of that frame lie on a line or in one place.  ok (batch) bytes: 0 with r = identity and t = 0 for fewer than 3 rows, a
+ * degenerate set or a non-finite result, else 1.  One wave per pair. */
+MI_API int mi_rigid_refit(const float *pts1, const float *pts2, const uint8_t *mask, int batch, int n, float *r, float *t,
+                          uint8_t *ok, mi_stream_t stream);
+
+/* The whole estimator: mi_rigid_hypotheses into the workspace, then per pair the hypothesis of minimum cost (the lowest h
+ * among equals; h = 0 when every cost is +inf) and refine_rounds rounds r = 0 .. R-1 of local optimisation: take the
+ * inliers of the best motion so far at k_r * threshold, k_r = 1 + (R - 1 - r) / 2, refit as mi_rigid_refit, score at
+ * `threshold`; the refit replaces the best motion only when its cost is strictly lower.  Inside this step a
+ * cost is held as (number of valid rows beyond the threshold, float32 sum of the inliers' d^2, summed lanes-strided) and
+ * compared as k thr^2 + s in float64, the hypothesis' own cost re-formed that way first: in one float32 sum a handful of
+ * truncated rows (thr^2 each) absorbs any improvement of a small inlier residual (0.0325 + 1e-11 == 0.0325), and the
+ * refit of clean data would never replace its minimal sample.  A round whose inlier set has fewer than 3 rows
+ * (or is degenerate) changes nothing.
+ * r (batch, 3, 3), t (batch, 3); inlier (batch, n) bytes: d^2 <= threshold^2 under (r, t), 0 for rows that are not valid;
+ * best_h (batch) the selected hypothesis; count (batch) = number of inlier bytes set; rmse (batch) float32 = sqrt of the
+ * mean d^2 over the inliers (summed lanes-strided); ok (batch) bytes = 1 when a usable hypothesis exists and count >= 3.
+ * Where ok = 0: r = identity, t = 0, no inliers, count = 0, rmse = 0.  With refine_rounds = 0 and ok = 1, r / t / count are
+ * exactly rt_h[best_h] / count[best_h] of mi_rigid_hypotheses.
+ * 0 <= refine_rounds <= MI_POSE_MAX_REFINE_ROUNDS (MI_E_PARAM).  workspace: mi_rigid_ransac_workspace_bytes(batch, n, H)
+ * bytes (0 for an unsupported request), 16-byte aligned (MI_E_ALIGN), any content; shorter: MI_E_CAPACITY.  Two launches. */
+MI_API size_t mi_rigid_ransac_workspace_bytes(int batch, int n, int num_hypotheses);
+MI_API int mi_rigid_ransac(const float *pts1, const float *pts2, const uint8_t *valid, int batch, int n, int num_hypotheses,
+                           float threshold, int refine_rounds, uint32_t seed, float *r, float *t, uint8_t *inlier,
+                           int32_t *best_h, int32_t *count, float *rmse, uint8_t *ok, void *workspace, size_t workspace_bytes,
+                           mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

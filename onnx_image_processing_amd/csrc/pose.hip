@@ -21,6 +21,7 @@
 // fp32 throughout; built with -ffp-contract=off; no atomics; every reduction has a fixed order: bitwise reproducible.
 #include "common.h"
 #include "essential_math.h"
+#include "pose_sampler.h"      // po_mix, po_draw, po_sample_ranks (header: "Sampling")
 
 #include <math.h>
 
@@ -33,19 +34,6 @@ constexpr float PO_RANK_TOL = 1e-5f;      // a pivot at or below this fraction o
 constexpr int PO_SQUARINGS = 14;          // manifold projection: B^(2^14) in place of 16384 power-iteration steps
 constexpr int PO_INVERSE_ITERS = 6;       // refit: inverse-iteration steps
 constexpr int PO_JACOBI_SWEEPS = 6;       // triangulate: one-sided Jacobi sweeps over the 6 column pairs
-
-// ---- the sampler (header: "Sampling") ------------------------------------------------------------------------------------
-__host__ __device__ inline uint32_t po_mix(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x85EBCA6Bu;
-  x ^= x >> 13;
-  x *= 0xC2B2AE35u;
-  x ^= x >> 16;
-  return x;
-}
-__host__ __device__ inline uint32_t po_draw(uint32_t seed, uint32_t b, uint32_t h, uint32_t slot) {
-  return po_mix(po_mix(po_mix(seed + 0x9E3779B9u) + b) + (h * 8u + slot));
-}
 
 // ---- staging: the pair's selected correspondences, compacted in index order (one wave) ---------------------------------------
 struct PoStage {
@@ -249,23 +237,8 @@ __global__ __launch_bounds__(64) void po_hyp_kernel(const float *__restrict__ pt
   bool ok = nv >= 8;
   if (ok) {
     // 8 distinct ranks among the nv valid correspondences
-    int sorted[8], pick[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) sorted[s] = 0x7fffffff;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      int r = (int)(po_draw(seed, (uint32_t)b, (uint32_t)h, (uint32_t)s) % (uint32_t)(nv - s));
-#pragma unroll
-      for (int j = 0; j < 8; ++j) r += (j < s && r >= sorted[j]) ? 1 : 0;      // skip the ranks already taken (ascending)
-      pick[s] = r;
-      int x = r;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int lo = min(sorted[j], x), hi = max(sorted[j], x);
-        sorted[j] = lo;
-        x = hi;
-      }
-    }
+    int pick[8];
+    po_sample_ranks<8>(seed, (uint32_t)b, (uint32_t)h, nv, pick);
     float4 q[8];
 #pragma unroll
     for (int s = 0; s < 8; ++s) q[s] = S.st.p[pick[s]];

@@ -1198,6 +1198,109 @@ def triangulate(proj1: torch.Tensor, proj2: torch.Tensor, pts1: torch.Tensor, pt
     return out, finite.view(torch.bool)
 
 
+# ---- K17 metric RGB-D pose (include/mi355x_match.h, "metric RGB-D pose") ---------------------------------------------------
+
+RIGID_MAX_N = 2048                         # MI_RIGID_MAX_N
+
+
+def lift_keypoints(keypoints: torch.Tensor, depth: torch.Tensor, k_inv: torch.Tensor, z_scale: float = 1.0,
+                   min_depth: float = 0.1, max_depth: float = 10.0, valid: torch.Tensor | None = None):
+    """`mi_lift_keypoints`: keypoints (B, N, 2) in pixel (y, x) and depth (B, H, W), float32 or uint16, aligned to the camera
+    of k_inv (3, 3) -> (points (B, N, 3) float32 = depth at the nearest pixel times the keypoint's ray, valid (B, N) bool).
+    A row is valid when `valid` (optional, (B, N)) selects it, its pixel is inside the frame and min_depth <= depth *
+    z_scale <= max_depth; the other rows are zero.  Current stream, no synchronisation, capturable."""
+    if not depth.is_cuda:
+        raise RuntimeError(f"lift_keypoints: depth must live on the GPU (got device {depth.device}); this package has no CPU path")
+    if depth.dtype not in (F32, U16):
+        raise RuntimeError(f"lift_keypoints: depth must be float32 or uint16, got {depth.dtype}")
+    kp = keypoints.float().contiguous()
+    if kp.dim() != 3 or kp.shape[-1] != 2 or kp.shape[1] < 1:
+        raise RuntimeError(f"lift_keypoints: keypoints must be (B, N, 2), got {tuple(keypoints.shape)}")
+    b, n = int(kp.shape[0]), int(kp.shape[1])
+    if depth.dim() != 3 or depth.shape[0] != b or depth.shape[1] < 1 or depth.shape[2] < 1:
+        raise RuntimeError(f"lift_keypoints: depth must be ({b}, H, W), got {tuple(depth.shape)}")
+    if not min_depth > 0 or not max_depth >= min_depth or not z_scale > 0:
+        raise RuntimeError(f"lift_keypoints: need 0 < min_depth <= max_depth and z_scale > 0, got {min_depth}, {max_depth}, {z_scale}")
+    d = depth.contiguous()
+    ki = k_inv.float().contiguous()
+    if tuple(ki.shape) != (3, 3):
+        raise RuntimeError(f"lift_keypoints: K_inv must be (3, 3), got {tuple(k_inv.shape)}")
+    v = _validity_bytes(valid)
+    if v is not None and tuple(v.shape) != (b, n):
+        raise RuntimeError(f"lift_keypoints: the mask must be ({b}, {n}), got {tuple(v.shape)}")
+    pts = torch.empty((b, n, 3), dtype=F32, device=d.device)
+    ok = torch.empty((b, n), dtype=U8, device=d.device)
+    N.call("mi_lift_keypoints", N.dev(kp, F32, "keypoints"), d.data_ptr(), int(d.dtype == U16), b, n, int(d.shape[1]),
+           int(d.shape[2]), N.dev(ki, F32, "K_inv"), float(z_scale), float(min_depth), float(max_depth),
+           N.dev(v, U8, "valid") if v is not None else None, pts.data_ptr(), ok.data_ptr(), N.stream_ptr())
+    return pts, ok.view(torch.bool)
+
+
+def _point_pairs(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, what: str):
+    """(B, N, 3) points of both frames and an optional (B, N) mask, as the C ABI reads them."""
+    q1, q2 = pts1.float().contiguous(), pts2.float().contiguous()
+    if q1.dim() != 3 or q1.shape[-1] != 3 or q1.shape != q2.shape:
+        raise RuntimeError(f"{what}: points must both be (B, N, 3), got {tuple(pts1.shape)} and {tuple(pts2.shape)}")
+    b, n = int(q1.shape[0]), int(q1.shape[1])
+    if not 1 <= n <= RIGID_MAX_N:
+        raise RuntimeError(f"{what}: N = {n} rows, supported: 1 .. {RIGID_MAX_N}")
+    v = _validity_bytes(valid)
+    if v is not None and tuple(v.shape) != (b, n):
+        raise RuntimeError(f"{what}: the mask must be ({b}, {n}), got {tuple(v.shape)}")
+    N.dev(q1, F32, "pts1"), N.dev(q2, F32, "pts2")
+    return q1, q2, v, b, n
+
+
+def rigid_hypotheses(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, num_hypotheses: int,
+                     threshold: float, seed: int = 0):
+    """`mi_rigid_hypotheses`: H 3-point rigid motions per pair from the counter-based sampler, each scored on every valid
+    row -> (rt_h (B, H, 12): R row-major then t, MSAC cost (B, H) float32, inlier count (B, H) int32)."""
+    q1, q2, v, b, n = _point_pairs(pts1, pts2, valid, "rigid_hypotheses")
+    h = int(num_hypotheses)
+    rt_h = torch.empty((b, h, 12), dtype=F32, device=q1.device)
+    cost = torch.empty((b, h), dtype=F32, device=q1.device)
+    count = torch.empty((b, h), dtype=I32, device=q1.device)
+    N.call("mi_rigid_hypotheses", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "valid") if v is not None else None, b, n, h,
+           float(threshold), int(seed) & 0xFFFFFFFF, rt_h.data_ptr(), cost.data_ptr(), count.data_ptr(), N.stream_ptr())
+    return rt_h, cost, count
+
+
+def rigid_refit(pts1: torch.Tensor, pts2: torch.Tensor, mask: torch.Tensor):
+    """`mi_rigid_refit`: Horn's closed-form motion over the masked rows -> (R (B, 3, 3), t (B, 3), ok (B,) bool)."""
+    q1, q2, v, b, n = _point_pairs(pts1, pts2, mask, "rigid_refit")
+    if v is None:
+        raise RuntimeError("rigid_refit needs a mask")
+    r = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
+    t = torch.empty((b, 3), dtype=F32, device=q1.device)
+    ok = torch.empty((b,), dtype=U8, device=q1.device)
+    N.call("mi_rigid_refit", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "mask"), b, n, r.data_ptr(), t.data_ptr(),
+           ok.data_ptr(), N.stream_ptr())
+    return r, t, ok.view(torch.bool)
+
+
+def rigid_ransac(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, num_hypotheses: int, threshold: float,
+                 refine_rounds: int = 3, seed: int = 0):
+    """`mi_rigid_ransac`: hypotheses, MSAC selection and refine_rounds rounds of refit-and-rescore in two launches ->
+    (R (B, 3, 3), t (B, 3), inlier (B, N) bool, best_h (B,) int32, count (B,) int32, rmse (B,) float32, ok (B,) bool)."""
+    q1, q2, v, b, n = _point_pairs(pts1, pts2, valid, "rigid_ransac")
+    h = int(num_hypotheses)
+    wbytes = int(N.load().mi_rigid_ransac_workspace_bytes(b, n, h))
+    if wbytes == 0:
+        raise RuntimeError(f"rigid_ransac: unsupported request (batch {b}, N {n}, {h} hypotheses)")
+    work = torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=q1.device)
+    r = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
+    t = torch.empty((b, 3), dtype=F32, device=q1.device)
+    inlier = torch.empty((b, n), dtype=U8, device=q1.device)
+    best_h = torch.empty((b,), dtype=I32, device=q1.device)
+    count = torch.empty((b,), dtype=I32, device=q1.device)
+    rmse = torch.empty((b,), dtype=F32, device=q1.device)
+    ok = torch.empty((b,), dtype=U8, device=q1.device)
+    N.call("mi_rigid_ransac", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "valid") if v is not None else None, b, n, h,
+           float(threshold), int(refine_rounds), int(seed) & 0xFFFFFFFF, r.data_ptr(), t.data_ptr(), inlier.data_ptr(),
+           best_h.data_ptr(), count.data_ptr(), rmse.data_ptr(), ok.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    return r, t, inlier.view(torch.bool), best_h, count, rmse, ok.view(torch.bool)
+
+
 # ---- K16 frame ingest (sample/visual_odometry.py:65-92 load_image_from_array) ------------------------------------------
 
 INGEST_MAX_DIM = 16384             # include/mi355x_match.h MI_INGEST_MAX_DIM

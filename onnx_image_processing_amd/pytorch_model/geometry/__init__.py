@@ -1,4 +1,5 @@
 from .essential_matrix_estimator import EssentialMatrixEstimator
 from .relative_pose import RelativePoseEstimator, triangulate_points
+from .rgbd_pose import RgbdPoseEstimator
 
-__all__ = ["EssentialMatrixEstimator", "RelativePoseEstimator", "triangulate_points"]
+__all__ = ["EssentialMatrixEstimator", "RelativePoseEstimator", "RgbdPoseEstimator", "triangulate_points"]

@@ -233,6 +233,100 @@ def synth_two_view(seed: int, n: int, outlier_fraction: float, noise_px: float, 
     return (px1[:, ::-1].astype(np.float32), px2[:, ::-1].astype(np.float32), R, t, inlier)
 
 
+RGBD_BASELINE = 0.4                   # metres between the two views of synth_rgbd_pair
+
+
+def rgbd_camera(height: int = 480, width: int = 640) -> np.ndarray:
+    """float64 (3, 3) camera matrix of synth_rgbd_pair: two_view_camera() at 480 x 640, scaled with the width otherwise."""
+    f = 500.0 * width / TWO_VIEW_IMAGE[1]
+    return np.array([[f, 0.0, width / 2.0], [0.0, f, height / 2.0], [0.0, 0.0, 1.0]])
+
+
+def synth_rgbd_pair(seed: int, n: int, outlier_fraction: float, noise_px: float, depth_noise: float, height: int = 480,
+                    width: int = 640):
+    """An RGB-D pair for the metric pose kernels: (keypoints1, keypoints2, depth1, depth2, R, t, inlier).  keypoints (n, 2)
+    float32 in pixel (y, x) order under rgbd_camera(height, width); depth (height, width) float32 in metres, ZERO except at
+    the rounded keypoint pixels (floor(v + 0.5)), where it holds the point's Z in that view; R (3, 3), t (3,) float64 with
+    X2 = R X1 + t and |t| = RGBD_BASELINE metres; inlier (n,) bool, the planted inlier mask.
+
+    synth_two_view's geometry with a metric baseline: points uniform in [-2, 2] x [-1.5, 1.5] x [3, 9] m in the first
+    camera's frame, R the Rodrigues rotation of a N(0, 0.08^2) vector, the baseline in a uniformly random direction;
+    N(0, noise_px^2) on both views' pixels and N(0, (depth_noise z^2)^2) on both depths (a stereo sensor's error grows with
+    z^2).  round(outlier_fraction * n) rows, chosen by a hashed ranking, are outliers: their second-view pixel is uniform over
+    the image and both their depths are uniform in [3, 9] m.  A row whose pixel falls outside the frame in either view, or
+    rounds to a pixel that an earlier row (or an earlier candidate of the same attempt) already holds in that view, is
+    RE-DRAWN whole from a hashed attempt counter until it fits: within a view no two keypoints share a depth pixel.
+    float64 arithmetic on hashed integers: the same scene everywhere."""
+    K = rgbd_camera(height, width)
+
+    def uni(rows, attempt, salt):
+        """uniform (0, 1) float64 per row for this attempt"""
+        r = np.asarray(rows, dtype=np.uint64)
+        return ((_hash3(seed, r, np.uint64(attempt) * np.uint64(64) + np.uint64(salt) + 0 * r, 23) >> np.uint64(11)).astype(np.float64)
+                + 0.5) / float(1 << 53)
+
+    def normal(rows, attempt, salt):
+        return np.sqrt(-2.0 * np.log(uni(rows, attempt, salt))) * np.cos(2.0 * np.pi * uni(rows, attempt, salt + 1))
+
+    three = np.arange(3)
+    w = 0.08 * normal(three, 0, 40)
+    th = float(np.linalg.norm(w))
+    k = w / th if th > 0 else np.array([0.0, 0.0, 1.0])
+    kx = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    R = np.eye(3) + np.sin(th) * kx + (1.0 - np.cos(th)) * (kx @ kx)
+    d = normal(three, 0, 42)
+    t = RGBD_BASELINE * d / np.linalg.norm(d)
+    idx = np.arange(n, dtype=np.uint64)
+    n_out = int(round(outlier_fraction * n))
+    order = np.argsort(_hash3(seed, idx, np.uint64(15) + 0 * idx, 23), kind="stable")
+    inlier = np.ones(n, dtype=bool)
+    inlier[order[:n_out]] = False
+
+    kp1, kp2 = np.zeros((n, 2)), np.zeros((n, 2))              # pixel (x, y)
+    z1, z2 = np.zeros(n), np.zeros(n)
+    taken = [np.zeros(height * width, bool), np.zeros(height * width, bool)]
+    pending, attempt = np.arange(n), 0
+    while pending.size:
+        if attempt >= 1024:
+            raise ValueError(f"synth_rgbd_pair: {pending.size} of {n} keypoints found no free pixel in a {height} x {width} frame")
+        rows = pending
+        x1 = np.stack([-2.0 + 4.0 * uni(rows, attempt, 0), -1.5 + 3.0 * uni(rows, attempt, 1), 3.0 + 6.0 * uni(rows, attempt, 2)], axis=1)
+        x2 = x1 @ R.T + t
+        p1 = ((x1 / x1[:, 2:]) @ K.T)[:, :2] + noise_px * np.stack([normal(rows, attempt, 4), normal(rows, attempt, 6)], axis=1)
+        p2 = ((x2 / x2[:, 2:]) @ K.T)[:, :2] + noise_px * np.stack([normal(rows, attempt, 8), normal(rows, attempt, 10)], axis=1)
+        za = x1[:, 2] + depth_noise * x1[:, 2] ** 2 * normal(rows, attempt, 12)
+        zb = x2[:, 2] + depth_noise * x2[:, 2] ** 2 * normal(rows, attempt, 14)
+        out = ~inlier[rows]
+        p2[out] = np.stack([width * uni(rows, attempt, 16), height * uni(rows, attempt, 17)], axis=1)[out]
+        za[out] = (3.0 + 6.0 * uni(rows, attempt, 18))[out]
+        zb[out] = (3.0 + 6.0 * uni(rows, attempt, 19))[out]
+        p1, p2 = p1.astype(np.float32), p2.astype(np.float32)          # what the caller gets: round THESE
+        ok = np.ones(rows.size, bool)
+        pix = []
+        for p in (p1, p2):
+            q = np.floor(p + np.float32(0.5)).astype(np.int64)
+            ok &= (q[:, 0] >= 0) & (q[:, 0] < width) & (q[:, 1] >= 0) & (q[:, 1] < height)
+            pix.append(np.clip(q[:, 1], 0, height - 1) * width + np.clip(q[:, 0], 0, width - 1))
+        for view in (0, 1):
+            ok &= ~taken[view][pix[view]]
+            cand = np.flatnonzero(ok)
+            first = np.zeros(rows.size, bool)
+            first[cand[np.unique(pix[view][cand], return_index=True)[1]]] = True      # the lowest row among equal pixels
+            ok &= first
+        acc = rows[ok]
+        kp1[acc], kp2[acc], z1[acc], z2[acc] = p1[ok], p2[ok], za[ok], zb[ok]
+        taken[0][pix[0][ok]] = True
+        taken[1][pix[1][ok]] = True
+        pending = rows[~ok]
+        attempt += 1
+    kp1, kp2 = kp1.astype(np.float32), kp2.astype(np.float32)
+    depth1, depth2 = np.zeros((height, width), np.float32), np.zeros((height, width), np.float32)
+    for kp, z, depth in ((kp1, z1, depth1), (kp2, z2, depth2)):
+        q = np.floor(kp + np.float32(0.5)).astype(np.int64)
+        depth[q[:, 1], q[:, 0]] = z.astype(np.float32)
+    return (np.ascontiguousarray(kp1[:, ::-1]), np.ascontiguousarray(kp2[:, ::-1]), depth1, depth2, R, t, inlier)
+
+
 def synth_colour_frame(seed: int, height: int, width: int, channels: int = 3) -> np.ndarray:
     """uint8 (height, width, channels) interleaved colour frame with structure, what a camera hands to the frame ingest:
     synth_image(seed) at half the size, upsampled 2x by pixel repetition (so that its corners survive an ingest to half

@@ -1,0 +1,231 @@
+"""numpy restatement of the K17 metric RGB-D pose algorithm (include/mi355x_match.h, "metric RGB-D pose"), written from the
+header's definitions: the lift of keypoints through depth, the counter-based sampler (pose_oracle's hash, 3 slots), Horn's
+closed-form alignment with the quaternion from numpy.linalg.eigh (the kernels use a fixed number of Jacobi sweeps), the
+degeneracy rules, the point-to-point MSAC score, the refit and the RANSAC loop.  Every function takes `dtype`: float64 is the
+oracle, float32 the same arithmetic at the kernels' precision -- its deviation from float64 is what the GPU tests take their
+tolerances from.  Host only; shared by tests/test_rigid_host.py and tests/test_gpu_rigid*.py."""
+import numpy as np
+
+import pose_oracle as PO
+
+DEGENERATE = 1e-6
+
+
+def sample_ranks(seed, b, h, nv):
+    """the 3 distinct ranks (among the valid rows, index order) of hypothesis h of pair b"""
+    taken, out = [], []
+    for s in range(3):
+        r = PO.draw(seed, b, h, s) % (nv - s)
+        for q in sorted(taken):
+            if r >= q:
+                r += 1
+        taken.append(r)
+        out.append(r)
+    return out
+
+
+def lift_f32(kp_yx, depth, k_inv, z_scale, min_depth, max_depth, valid_in=None):
+    """mi_lift_keypoints in the header's float32 arithmetic, one frame: (points (n, 3) float32, valid (n,) bool)"""
+    f = np.float32
+    kp = np.asarray(kp_yx, f)
+    ki = np.asarray(k_inv, f).ravel()
+    y, x = kp[:, 0], kp[:, 1]
+    h, w = depth.shape
+    with np.errstate(invalid="ignore", over="ignore"):
+        xn = (x * ki[0] + y * ki[1]) + ki[2]
+        yn = (x * ki[3] + y * ki[4]) + ki[5]
+        px, py = np.floor(x + f(0.5)), np.floor(y + f(0.5))
+        ok = (px >= 0) & (px < w) & (py >= 0) & (py < h)
+        if valid_in is not None:
+            ok &= np.asarray(valid_in) != 0
+        d = np.zeros(len(kp), f)
+        d[ok] = depth[py[ok].astype(np.int64), px[ok].astype(np.int64)].astype(f)
+        z = d * f(z_scale)
+        ok &= np.isfinite(d) & (z >= f(min_depth)) & (z <= f(max_depth))
+        pts = np.stack([xn * z, yn * z, z], axis=1).astype(f)
+    pts[~ok] = 0
+    return pts, ok
+
+
+def lift(kp_yx, depth, K, z_scale=1.0, min_depth=0.1, max_depth=10.0):
+    """the same lift in float64 (for scenes, not for bit parity)"""
+    kp = np.asarray(kp_yx, np.float64)
+    ki = np.linalg.inv(np.asarray(K, np.float64))
+    q = np.floor(kp + 0.5).astype(np.int64)
+    h, w = depth.shape
+    ok = (q[:, 0] >= 0) & (q[:, 0] < h) & (q[:, 1] >= 0) & (q[:, 1] < w)
+    z = np.zeros(len(kp))
+    z[ok] = depth[q[ok, 0], q[ok, 1]].astype(np.float64) * z_scale
+    ok &= (z >= min_depth) & (z <= max_depth)
+    ray = np.stack([kp[:, 1], kp[:, 0], np.ones(len(kp))], axis=1) @ ki.T
+    pts = ray * z[:, None]
+    pts[~ok] = 0
+    return pts, ok
+
+
+def degenerate3(p):
+    e1, e2 = p[1] - p[0], p[2] - p[0]
+    c = np.cross(e1, e2)
+    return not (c @ c > p.dtype.type(DEGENERATE) * (e1 @ e1) * (e2 @ e2))
+
+
+def horn(s, ca, cb, dtype):
+    """(R, t) from S = sum (a - ca)(b - cb)^T; None when not finite"""
+    n = np.array([[s[0, 0] + s[1, 1] + s[2, 2], s[1, 2] - s[2, 1], s[2, 0] - s[0, 2], s[0, 1] - s[1, 0]],
+                  [0, s[0, 0] - s[1, 1] - s[2, 2], s[0, 1] + s[1, 0], s[2, 0] + s[0, 2]],
+                  [0, 0, -s[0, 0] + s[1, 1] - s[2, 2], s[1, 2] + s[2, 1]],
+                  [0, 0, 0, -s[0, 0] - s[1, 1] + s[2, 2]]], dtype)
+    n = n + np.triu(n, 1).T
+    if not np.isfinite(n).all():
+        return None
+    _, vec = np.linalg.eigh(n)
+    q = vec[:, 3].astype(dtype)
+    q = q / np.sqrt((q * q).sum())
+    if q[0] < 0:
+        q = -q
+    q0, qx, qy, qz = q
+    R = np.array([[q0 * q0 + qx * qx - qy * qy - qz * qz, 2 * (qx * qy - q0 * qz), 2 * (qx * qz + q0 * qy)],
+                  [2 * (qy * qx + q0 * qz), q0 * q0 - qx * qx + qy * qy - qz * qz, 2 * (qy * qz - q0 * qx)],
+                  [2 * (qz * qx - q0 * qy), 2 * (qz * qy + q0 * qx), q0 * q0 - qx * qx - qy * qy + qz * qz]], dtype)
+    t = (cb - R @ ca).astype(dtype)
+    return (R, t) if np.isfinite(R).all() and np.isfinite(t).all() else None
+
+
+def solve_minimal(a, b, dtype=np.float64):
+    """(R, t) from three rows a (3, 3) <-> b (3, 3); None for a degenerate sample"""
+    a, b = a.astype(dtype), b.astype(dtype)
+    if degenerate3(a) or degenerate3(b):
+        return None
+    ca, cb = ((a[0] + a[1]) + a[2]) / dtype(3), ((b[0] + b[1]) + b[2]) / dtype(3)
+    return horn(((a - ca).T @ (b - cb)).astype(dtype), ca, cb, dtype)
+
+
+def dist2(R, t, x1, x2):
+    u = (x1 @ R.T + t) - x2
+    return (u * u).sum(axis=1).astype(R.dtype)
+
+
+def score(R, t, x1, x2, thr):
+    d2 = dist2(R, t, x1, x2)
+    t2 = R.dtype.type(thr) * R.dtype.type(thr)
+    return R.dtype.type(np.minimum(d2, t2).sum(dtype=R.dtype)), int((d2 <= t2).sum()), d2
+
+
+def hypotheses(x1, x2, valid, num_hyp, thr, seed, b=0, dtype=np.float64):
+    """one pair: (rt_h (H, 12), cost (H,), count (H,), ranks (H, 3)); x1, x2 (n, 3), valid (n,) or None"""
+    sel = np.arange(len(x1)) if valid is None else np.flatnonzero(valid)
+    q1, q2 = x1[sel].astype(dtype), x2[sel].astype(dtype)
+    nv = len(sel)
+    rt_h = np.zeros((num_hyp, 12), dtype)
+    cost = np.full(num_hyp, np.inf, dtype)
+    count = np.zeros(num_hyp, np.int32)
+    ranks = np.zeros((num_hyp, 3), np.int64)
+    if nv < 3:
+        return rt_h, cost, count, ranks
+    for h in range(num_hyp):
+        ranks[h] = sample_ranks(seed, b, h, nv)
+        m = solve_minimal(q1[ranks[h]], q2[ranks[h]], dtype)
+        if m is None:
+            continue
+        c, k, _ = score(m[0], m[1], q1, q2, thr)
+        if np.isfinite(c):
+            rt_h[h], cost[h], count[h] = np.concatenate([m[0].ravel(), m[1]]), c, k
+    return rt_h, cost, count, ranks
+
+
+def scatter_degenerate(c):
+    w = np.linalg.eigvalsh(c)
+    return not (w[1] > c.dtype.type(DEGENERATE) * w[2])
+
+
+def refit(x1, x2, mask, dtype=np.float64):
+    """(R, t, ok) from the masked rows: two passes, Horn; identity / zero / False for < 3 rows or a collinear set"""
+    sel = np.flatnonzero(mask)
+    ident = (np.eye(3, dtype=dtype), np.zeros(3, dtype), False)
+    if len(sel) < 3:
+        return ident
+    a, b = x1[sel].astype(dtype), x2[sel].astype(dtype)
+    ca, cb = a.sum(axis=0, dtype=dtype) / dtype(len(sel)), b.sum(axis=0, dtype=dtype) / dtype(len(sel))
+    da, db = a - ca, b - cb
+    if not (np.isfinite(da).all() and np.isfinite(db).all()):
+        return ident
+    if scatter_degenerate((da.T @ da).astype(dtype)) or scatter_degenerate((db.T @ db).astype(dtype)):
+        return ident
+    m = horn((da.T @ db).astype(dtype), ca, cb, dtype)
+    return ident if m is None else (m[0], m[1], True)
+
+
+def ransac(x1, x2, valid, num_hyp, thr, rounds, seed, b=0, dtype=np.float64, cost64=False):
+    """one pair: (R, t, inlier (n,) bool, best_h, count, rmse, ok).  cost64: the header's rule for the costs inside the
+    refinement step -- (valid rows beyond the threshold) thr^2 + the inliers' sum of d^2 (summed in `dtype`), combined in
+    float64 -- instead of one MSAC sum in `dtype`; the two agree in float64, and differ in float32 where truncated rows
+    absorb a small inlier residual"""
+    n = len(x1)
+    vmask = np.ones(n, bool) if valid is None else np.asarray(valid, bool)
+    rt_h, cost, _, _ = hypotheses(x1, x2, valid, num_hyp, thr, seed, b, dtype)
+    best_h = int(np.argmin(cost)) if np.isfinite(cost).any() else 0
+    fail = (np.eye(3, dtype=dtype), np.zeros(3, dtype), np.zeros(n, bool), best_h, 0, dtype(0), False)
+    if not np.isfinite(cost[best_h]):
+        return fail
+    q1, q2 = np.where(vmask[:, None], x1, 0).astype(dtype), np.where(vmask[:, None], x2, 0).astype(dtype)
+    R, t = rt_h[best_h, :9].reshape(3, 3), rt_h[best_h, 9:]
+
+    def step_cost(Rc, tc):
+        d2 = dist2(Rc, tc, q1[vmask], q2[vmask])
+        t2 = dtype(thr) * dtype(thr)
+        if not cost64:
+            return dtype(np.minimum(d2, t2).sum(dtype=dtype))
+        inl = d2 <= t2
+        return float(int((~inl).sum())) * float(t2) + float(d2[inl].sum(dtype=dtype))
+    cur = step_cost(R, t) if cost64 else cost[best_h]
+    for r in range(rounds):
+        kr = 1.0 + 0.5 * (rounds - 1 - r)
+        d2 = dist2(R, t, q1, q2)
+        R2, t2, ok = refit(q1, q2, vmask & (d2 <= dtype(kr * thr) ** 2), dtype)
+        if not ok:
+            continue
+        c2 = step_cost(R2, t2)
+        if c2 < cur:
+            R, t, cur = R2, t2, c2
+    d2 = dist2(R, t, q1, q2)
+    inlier = vmask & (d2 <= dtype(thr) ** 2)
+    cnt = int(inlier.sum())
+    if cnt < 3:
+        return fail
+    return R, t, inlier, best_h, cnt, dtype(np.sqrt(d2[inlier].mean(dtype=dtype))), True
+
+
+def translation_error(t, t0):
+    return float(np.linalg.norm(np.asarray(t, np.float64) - np.asarray(t0, np.float64)))
+
+
+# ---- the scenes the host and GPU tests share --------------------------------------------------------------------------------
+THR = 0.05                       # metres: RgbdPoseEstimator's default distance_threshold
+MIN_DEPTH, MAX_DEPTH = 0.1, 10.0
+
+
+def scenes(seeds, n, outliers, noise_px, depth_noise):
+    """a batch of synth_rgbd_pair scenes at 480 x 640: keypoints (B, n, 2) x 2, depth (B, 480, 640) x 2, lists of R and t,
+    planted inlier masks (B, n)"""
+    from onnx_image_processing_amd.synth import synth_rgbd_pair
+    s = [synth_rgbd_pair(seed, n, outliers, noise_px, depth_noise) for seed in seeds]
+    return (np.stack([x[0] for x in s]), np.stack([x[1] for x in s]), np.stack([x[2] for x in s]), np.stack([x[3] for x in s]),
+            [x[4] for x in s], [x[5] for x in s], np.stack([x[6] for x in s]))
+
+
+def lifted(k1, k2, d1, d2, K):
+    """the scenes' points as mi_lift_keypoints produces them (float32, the header's arithmetic): x1, x2 (B, n, 3), valid"""
+    ki = np.linalg.inv(np.asarray(K, np.float64)).astype(np.float32)
+    a = [lift_f32(k, d, ki, 1.0, MIN_DEPTH, MAX_DEPTH) for k, d in zip(k1, d1)]
+    b = [lift_f32(k, d, ki, 1.0, MIN_DEPTH, MAX_DEPTH) for k, d in zip(k2, d2)]
+    return (np.stack([x[0] for x in a]), np.stack([x[0] for x in b]), np.stack([x[1] & y[1] for x, y in zip(a, b)]))
+
+
+def sample_ranks_batch(seed, batch, num_hyp, nv):
+    """sample_ranks for every (b, h) at once: (batch, num_hyp, 3) int64 (the first 3 slots of K15's batch sampler differ from
+    it only in the modulus, so this restates them)"""
+    out = np.zeros((batch, num_hyp, 3), np.int64)
+    for b in range(batch):
+        for h in range(num_hyp):
+            out[b, h] = sample_ranks(seed, b, h, nv)
+    return out
