@@ -906,6 +906,88 @@ MI_API int mi_rigid_ransac(const float *pts1, const float *pts2, const uint8_t *
                            int32_t *best_h, int32_t *count, float *rmse, uint8_t *ok, void *workspace, size_t workspace_bytes,
                            mi_stream_t stream);
 
+/* ---- dense RGB-D refinement (K18): two aligned depth frames + a starting pose -> the pose refined against every pixel -------
+ * K17's pose rests on a few hundred matches, each reading depth at one pixel.  This section refines such a pose (or the
+ * identity, for a frame with too few matches) by projective point-to-plane ICP over the whole of both depth frames, and
+ * returns the 6x6 information matrix of the result.  Four entries, batched over pairs, under the contract of the K15 / K17
+ * sections: pure functions of their arguments, no allocation, no synchronisation, no memset, one stream, no atomics, every
+ * sum in a fixed order, capturable into a hipGraph; outputs and workspace may hold anything on entry and every output
+ * element is written; MI_E_* before any launch.  A pair's result is the same bits alone or inside a batch, and from run to
+ * run.  Motion convention: X2 = R X1 + t.  Per-pixel arithmetic is float32 with nothing fused, the solve and the pose float64.
+ *
+ * Surfel maps (mi_surfel_maps), per frame: two records of 4 float32 per pixel, (batch, h, w, 4) each.
+ *   vertex  (vx, vy, vz, f): for the integer pixel (x, y): xn = (x k_inv[0] + y k_inv[1]) + k_inv[2], yn = (x k_inv[3] +
+ *     y k_inv[4]) + k_inv[5] (mi_lift_keypoints' ray), Z = d * z_scale, v = (xn * Z, yn * Z, Z); valid (f = 1) when d is finite
+ *     and min_depth <= Z <= max_depth, else zeros.
+ *   normal  (nx, ny, nz, f): a = v(x+1, y) - v(x-1, y), b = v(x, y+1) - v(x, y-1), m = a x b with each component as
+ *     a_i b_j - a_j b_i, |m|^2 = (m_0^2 + m_1^2) + m_2^2, n = m / sqrt(|m|^2), negated when (n_0 v_0 + n_1 v_1) + n_2 v_2 > 0
+ *     (it faces the camera).  Valid (f = 1) only when the centre and all four neighbours are valid and in the frame, every
+ *     neighbour's |Z - Z_centre| <= normal_max_jump, and |m|^2 is positive and finite; else zeros.  Border pixels have none.
+ *   These are surface normals; the normals of mi_depth_to_points_normals are the reference's Sobel-of-(X+Y+Z) maps.
+ *
+ * One linearisation at pose (R, t), float32, and source stride s: over the pixels (y, x) of frame 1 with y % s == 0 and
+ *   x % s == 0 whose normal is valid, with v1, n1 of frame 1:
+ *     q_j = ((R_j0 v1_0 + R_j1 v1_1) + R_j2 v1_2) + t_j;   m_j = (R_j0 n1_0 + R_j1 n1_1) + R_j2 n1_2
+ *     u = fx * (q_0 / q_2) + cx, v = fy * (q_1 / q_2) + cy;  px = floorf(u + 0.5f), py = floorf(v + 0.5f)   (nearest pixel:
+ *     no interpolation, by K17's argument about occlusion edges)
+ *   rejected when q_2 <= 0, (px, py) is outside the frame, frame 2 has no valid normal there, or with v2, n2 of that pixel
+ *   and e = q - v2:  (e_0^2 + e_1^2) + e_2^2 > distance_threshold^2  or  (m_0 n2_0 + m_1 n2_1) + m_2 n2_2 < cos(angle_threshold)
+ *   (the cosine taken in float64 on the host and rounded to float32).  For a survivor r = (n2_0 e_0 + n2_1 e_1) + n2_2 e_2 and
+ *   J = [q x n2, n2] (the cross product's components as q_i n2_j - q_j n2_i).  29 sums: the 21 entries of the upper triangle
+ *   of A = sum J^T J in row-major order, the 6 of b = sum J r, sum r^2, the count.
+ *   Order of the sums.  The sampled pixels are numbered row-major over the ceil(h / s) x ceil(w / s) grid and cut into slabs
+ *   of 2048 consecutive numbers: a function of (h, w, s) alone.  Inside a slab, lane l of 256 adds its samples l, l + 256, ...
+ *   in this order in float32 (a rejected pixel adds zeros); each of the 4 waves folds its 64 lanes by wave_sum_dpp's tree
+ *   (csrc/common.h); the 4 wave totals are added in wave order in float64; the slabs are added in slab order in float64.
+ *   The count is an integer sum.
+ *
+ * Step.  A x = -b in float64 by LDL^T without pivoting.  The pair is DEGENERATE when count < min_correspondences, when a
+ *   pivot is not above 1e-6 * max diag(A), or when a sum, the solution or the new pose is not finite.  Otherwise, with
+ *   x = (omega, tau): R <- Exp(omega) R, t <- Exp(omega) t + tau, Exp by Rodrigues in float64 (I + [omega]x below
+ *   |omega| = 1e-8).  The pose lives in float64 in the workspace between iterations; each linearisation reads it rounded
+ *   to float32, and the outputs are that rounding.  A degenerate pair is FROZEN: its pose stays the one before the failed
+ *   solve, later iterations do nothing for it (the kernels read a per-pair state word and return), ok = 0.
+ * Schedule.  stages (1 .. MI_ICP_MAX_STAGES) of (stride in {1, 2, 4, 8}, iterations >= 0), at most MI_ICP_MAX_ITERATIONS
+ *   iterations in all, run as given: no adaptive stop.  After the last update ONE more linearisation at the last stage's
+ *   stride, for every pair (frozen ones at their frozen pose), gives count, rmse = sqrt(sum r^2 / count) (0 for count = 0)
+ *   and information = A as a full symmetric 6x6 in (omega, tau) order.  ok = 1 when no solve failed and that count is at
+ *   least min_correspondences.  With no iterations at all the result is the initial pose (its bits) with those statistics. */
+#define MI_ICP_MAX_STAGES 4
+#define MI_ICP_MAX_ITERATIONS 64
+
+/* depth (batch, h, w), float32 (depth_is_u16 = 0) or uint16 counts (1), ALREADY aligned to the camera of k_inv (3x3
+ * row-major inverse camera matrix, device memory) -> vertex_out, normal_out (batch, h, w, 4) float32, 16-byte aligned
+ * (MI_E_ALIGN).  batch < 1, h or w < 3, batch * h * w >= 2^31: MI_E_SHAPE; batch > 65535, min_depth <= 0, max_depth <
+ * min_depth or not finite, z_scale or normal_max_jump <= 0 or not finite: MI_E_PARAM.  One launch, one thread per pixel. */
+MI_API int mi_surfel_maps(const void *depth, int depth_is_u16, int batch, int h, int w, const float *k_inv, float z_scale,
+                          float min_depth, float max_depth, float normal_max_jump, float *vertex_out, float *normal_out,
+                          mi_stream_t stream);
+
+/* bytes of workspace for mi_icp_linearise / mi_icp_refine (0 for an unsupported shape): the float64 poses, the state and
+ * step words and one 256-byte record of partial sums per slab of the stride-1 grid and pair. */
+MI_API size_t mi_icp_workspace_bytes(int batch, int h, int w);
+
+/* One linearisation: the maps of both frames, r (batch, 3, 3) and t (batch, 3) float32 per pair -> sums (batch, 29)
+ * float64 in the order above (the count as a float64).  stride not in {1, 2, 4, 8}, fx or fy or distance_threshold <= 0 or
+ * not finite, cx or cy not finite, angle_threshold (radians) outside (0, pi]: MI_E_PARAM; maps or workspace not 16-byte
+ * aligned: MI_E_ALIGN; workspace shorter than mi_icp_workspace_bytes: MI_E_CAPACITY.  Two launches. */
+MI_API int mi_icp_linearise(const float *vertex1, const float *normal1, const float *vertex2, const float *normal2,
+                            const float *r, const float *t, int batch, int h, int w, float fx, float fy, float cx, float cy,
+                            int stride, float distance_threshold, float angle_threshold, double *sums, void *workspace,
+                            size_t workspace_bytes, mi_stream_t stream);
+
+/* The whole refinement from r0 (batch, 3, 3), t0 (batch, 3).  strides / iterations: HOST arrays of `stages` entries, read
+ * before the call returns.  Outputs: r (batch, 3, 3), t (batch, 3), information (batch, 36) float32, rmse (batch) float32,
+ * count (batch) int32, steps (batch) int32 = the number of updates applied, ok (batch) bytes.  The checks of
+ * mi_icp_linearise, and stages outside 1 .. MI_ICP_MAX_STAGES, an iteration count below 0, more than
+ * MI_ICP_MAX_ITERATIONS in all, min_correspondences < 1: MI_E_PARAM.  1 + 2 (iterations + 1) launches, enqueued back to back. */
+MI_API int mi_icp_refine(const float *vertex1, const float *normal1, const float *vertex2, const float *normal2,
+                         const float *r0, const float *t0, int batch, int h, int w, float fx, float fy, float cx, float cy,
+                         const int32_t *strides, const int32_t *iterations, int stages, float distance_threshold,
+                         float angle_threshold, int min_correspondences, float *r, float *t, float *information, float *rmse,
+                         int32_t *count, int32_t *steps, uint8_t *ok, void *workspace, size_t workspace_bytes,
+                         mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,14 @@ SIGNATURES = {
     "mi_rigid_ransac_workspace_bytes": [c_int, c_int, c_int],
     "mi_rigid_ransac": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_uint32, c_void_p, c_void_p, c_void_p,
                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    "mi_surfel_maps": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p,
+                       c_void_p],
+    "mi_icp_workspace_bytes": [c_int, c_int, c_int],
+    "mi_icp_linearise": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
+                         c_float, c_float, c_int, c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p],
+    "mi_icp_refine": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float,
+                      c_float, c_void_p, c_void_p, c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
 }
 
 
@@ -157,7 +165,8 @@ SIGNATURES["mi_match_pairs_u8"] = SIGNATURES["mi_match_pairs"]
 _RESTYPE = {"mi_essential_matrix_workspace_bytes": c_size_t, "mi_sinkhorn_dots_status_word": c_void_p, "mi_match_pairs_workspace_bytes": c_size_t, "mi_error_string": c_char_p, "mi_sinkhorn_workspace_bytes": c_size_t, "mi_bad_plan_bytes": c_size_t,
             "mi_sinkhorn_dots_workspace_bytes": c_size_t, "mi_mnn_duals_workspace_bytes": c_size_t,
             "mi_voxel_downsample_workspace_bytes": c_size_t, "mi_multi_otsu_workspace_bytes": c_size_t,
-            "mi_essential_ransac_workspace_bytes": c_size_t, "mi_rigid_ransac_workspace_bytes": c_size_t}
+            "mi_essential_ransac_workspace_bytes": c_size_t, "mi_rigid_ransac_workspace_bytes": c_size_t,
+            "mi_icp_workspace_bytes": c_size_t}
 
 MI_BAD_RAW, MI_BAD_SOFT, MI_BAD_HARD = 0, 1, 2
 MI_DIST_L2, MI_DIST_L1 = 0, 1

@@ -1,0 +1,361 @@
+// K18 dense RGB-D refinement (include/mi355x_match.h, "dense RGB-D refinement"): projective point-to-plane ICP between two
+// depth frames, batched over pairs under K17's contract.  The arithmetic is icp_math.h's.
+//
+// K18m  icp_surfel_kernel   one thread per pixel: the vertex (the ray of mi_lift_keypoints times depth) and the normal from
+//       the four axis neighbours, whose vertices the thread forms itself from their depths (5 depth reads, cached);
+//       two 16-byte records per pixel: (vx, vy, vz, vertex valid) and (nx, ny, nz, normal valid).
+// K18r  icp_reduce_kernel   grid (slabs, pairs), 256 threads.  A slab is ICP_SLAB = 2048 consecutive SAMPLED pixels of the
+//       stride's grid (row-major over ceil(h / s) x ceil(w / s)): a function of (h, w, s) only.  Lane l of the workgroup takes
+//       the samples l, l + 256, ... of its slab in this order (8 of them) into 28 float32 accumulators and an integer count:
+//       the streamed records are read unconditionally, the gathered ones at a clamped address, and a rejected pixel adds
+//       zeros, so the 8 iterations carry no branch and their loads overlap.  Then the DPP tree of wave_sum_dpp per
+//       accumulator, the 4 waves through LDS in wave order in float64, and 29 float64 partials stored with plain stores
+//       into the slab's 256-byte record.  No atomics.
+// K18s  icp_solve_kernel    one wave per pair: lane c < 29 adds column c of the pair's slab records in slab order
+//       (float64); lane 0 then solves (LDL^T) and updates the pose in the workspace (mode STEP), or writes the 29 sums
+//       (mode SUMS) or the outputs (mode FINAL).
+// K18i  icp_init_kernel     r0 / t0 -> the float64 pose, state and step words of the workspace.
+// A pair whose solve failed is frozen: its state word is set, and K18r / K18s return at once for it in later iterations.
+// Built with -ffp-contract=off; every sum has a fixed order: bitwise reproducible, alone or in a batch.
+#include "common.h"
+#include "icp_math.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int ICP_THREADS = 256;
+constexpr int ICP_PER_LANE = 8;
+constexpr int ICP_SLAB = ICP_THREADS * ICP_PER_LANE;       // sampled pixels per workgroup
+constexpr int ICP_REC = 32;                                // doubles per slab record (29 used)
+
+// ---- K18m ------------------------------------------------------------------------------------------------------------------
+template <typename D>
+__global__ __launch_bounds__(256) void icp_surfel_kernel(const D *__restrict__ depth, int h, int w, long long total,
+                                                         const float *__restrict__ k_inv, float z_scale, float min_depth,
+                                                         float max_depth, float max_jump, float4 *__restrict__ vertex,
+                                                         float4 *__restrict__ normal) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int hw = h * w;
+  const int p = (int)(i % hw), y = p / w, x = p - y * w;
+  float ki[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) ki[k] = k_inv[k];
+  float c[3], n[3] = {0.0f, 0.0f, 0.0f};
+  const bool vok = icp_vertex((float)depth[i], (float)x, (float)y, ki, z_scale, min_depth, max_depth, c);
+  bool nok = vok && x >= 1 && x <= w - 2 && y >= 1 && y <= h - 2;
+  if (nok) {                                                 // the four neighbours are inside the frame
+    float l[3], r[3], u[3], d[3];
+    nok = icp_vertex((float)depth[i - 1], (float)(x - 1), (float)y, ki, z_scale, min_depth, max_depth, l);
+    nok = icp_vertex((float)depth[i + 1], (float)(x + 1), (float)y, ki, z_scale, min_depth, max_depth, r) && nok;
+    nok = icp_vertex((float)depth[i - w], (float)x, (float)(y - 1), ki, z_scale, min_depth, max_depth, u) && nok;
+    nok = icp_vertex((float)depth[i + w], (float)x, (float)(y + 1), ki, z_scale, min_depth, max_depth, d) && nok;
+    nok = nok && icp_normal(c, l, r, u, d, max_jump, n);
+  }
+  vertex[i] = make_float4(c[0], c[1], c[2], vok ? 1.0f : 0.0f);
+  normal[i] = nok ? make_float4(n[0], n[1], n[2], 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// ---- K18i ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void icp_init_kernel(const float *__restrict__ r0, const float *__restrict__ t0, int batch,
+                                                      double *__restrict__ pose, int *__restrict__ state, int *__restrict__ steps) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= batch) return;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) pose[(size_t)b * 12 + k] = (double)r0[(size_t)b * 9 + k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) pose[(size_t)b * 12 + 9 + k] = (double)t0[(size_t)b * 3 + k];
+  state[b] = 0;
+  steps[b] = 0;
+}
+
+// ---- K18r ------------------------------------------------------------------------------------------------------------------
+struct IcpCam {
+  float fx, fy, cx, cy;
+};
+
+// The pose comes from r / t (float32, mi_icp_linearise) or, when pose64 is given, from the workspace's float64 pose
+// rounded to float32 (mi_icp_refine).
+__global__ __launch_bounds__(ICP_THREADS) void icp_reduce_kernel(const float4 *__restrict__ vertex1, const float4 *__restrict__ normal1,
+                                                                 const float4 *__restrict__ vertex2, const float4 *__restrict__ normal2,
+                                                                 const float *__restrict__ r, const float *__restrict__ t,
+                                                                 const double *__restrict__ pose64, const int *__restrict__ state,
+                                                                 int h, int w, int stride, int ws, int samples, int max_slabs,
+                                                                 IcpCam cam, float thr2, float cos_thr, double *__restrict__ slabs) {
+  __shared__ double part[4][ICP_REC];
+  const int b = blockIdx.y, slab = blockIdx.x, tid = threadIdx.x;
+  if (state && state[b] != 0) return;                        // frozen pair (uniform over the workgroup)
+  float R[9], T[3];
+  if (pose64) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = (float)pose64[(size_t)b * 12 + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) T[k] = (float)pose64[(size_t)b * 12 + 9 + k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = r[(size_t)b * 9 + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) T[k] = t[(size_t)b * 3 + k];
+  }
+  const size_t frame = (size_t)b * (size_t)h * (size_t)w;
+  float acc[28];
+#pragma unroll
+  for (int k = 0; k < 28; ++k) acc[k] = 0.0f;
+  int count = 0;
+#pragma unroll
+  for (int it = 0; it < ICP_PER_LANE; ++it) {
+    const int s = slab * ICP_SLAB + it * ICP_THREADS + tid;
+    const bool in = s < samples;
+    const int sc = in ? s : 0;                               // a clamped, always valid address
+    const int ys = sc / ws, xs = sc - ys * ws;
+    const size_t i1 = frame + (size_t)(ys * stride) * (size_t)w + (size_t)(xs * stride);
+    const float4 n1 = normal1[i1], v1 = vertex1[i1];
+    const float p1[3] = {v1.x, v1.y, v1.z}, m1[3] = {n1.x, n1.y, n1.z};
+    float q[3], rn[3], px, py;
+    icp_rotate(R, p1, q);
+    q[0] += T[0]; q[1] += T[1]; q[2] += T[2];
+    icp_rotate(R, m1, rn);
+    bool ok = in && n1.w != 0.0f;
+    ok = icp_project(q, cam.fx, cam.fy, cam.cx, cam.cy, w, h, &px, &py) && ok;
+    const int ix = ok ? (int)px : 0, iy = ok ? (int)py : 0;   // inside the frame when ok
+    const size_t i2 = frame + (size_t)iy * (size_t)w + (size_t)ix;
+    const float4 n2 = normal2[i2], v2 = vertex2[i2];
+    const float p2[3] = {v2.x, v2.y, v2.z}, m2[3] = {n2.x, n2.y, n2.z};
+    float J[6], res;
+    ok = icp_row(q, rn, p2, m2, thr2, cos_thr, J, &res) && ok && n2.w != 0.0f;
+    if (!ok) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) J[k] = 0.0f;
+      res = 0.0f;
+    }
+    icp_accumulate(J, res, acc);
+    count += ok ? 1 : 0;
+  }
+  const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int k = 0; k < 28; ++k) {
+    const float sum = wave_sum_dpp(acc[k]);
+    if (lane == 0) part[wave][k] = (double)sum;
+  }
+  int c = count;                                             // integers: exact in any order
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if (lane == 0) part[wave][28] = (double)c;
+  __syncthreads();
+  if (tid < ICP_SUMS)
+    slabs[((size_t)b * max_slabs + slab) * ICP_REC + tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+}
+
+// ---- K18s ------------------------------------------------------------------------------------------------------------------
+enum { ICP_MODE_STEP = 0, ICP_MODE_SUMS = 1, ICP_MODE_FINAL = 2 };
+
+struct IcpOut {
+  float *r, *t, *information, *rmse;
+  int *count, *steps;
+  uint8_t *ok;
+  double *sums;
+};
+
+__global__ __launch_bounds__(64) void icp_solve_kernel(const double *__restrict__ slabs, int nslabs, int max_slabs, int mode,
+                                                       int min_count, double *__restrict__ pose, int *__restrict__ state,
+                                                       int *__restrict__ steps, IcpOut out) {
+  __shared__ double s[ICP_REC];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (mode == ICP_MODE_STEP && state[b] != 0) return;        // frozen pair
+  if (lane < ICP_SUMS) {
+    double a = 0.0;
+    for (int k = 0; k < nslabs; ++k) a += slabs[((size_t)b * max_slabs + k) * ICP_REC + lane];
+    s[lane] = a;
+    if (mode == ICP_MODE_SUMS) out.sums[(size_t)b * ICP_SUMS + lane] = a;
+  }
+  __syncthreads();
+  if (mode == ICP_MODE_SUMS || lane != 0) return;
+  if (mode == ICP_MODE_STEP) {
+    double x[6], ratio;
+    if (icp_solve(s, min_count, x, &ratio)) {
+      double p[12];
+#pragma unroll
+      for (int k = 0; k < 12; ++k) p[k] = pose[(size_t)b * 12 + k];
+      icp_update_pose(p, x);
+      bool finite = true;
+#pragma unroll
+      for (int k = 0; k < 12; ++k) finite = finite && fabs(p[k]) < INFINITY;
+      if (finite) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) pose[(size_t)b * 12 + k] = p[k];
+        steps[b] += 1;
+        return;
+      }
+    }
+    state[b] = 1;
+    return;
+  }
+  // FINAL: the statistics of the returned pose
+  const int cnt = (int)s[28];
+  bool finite = true;
+  for (int k = 0; k < ICP_SUMS; ++k) finite = finite && fabs(s[k]) < INFINITY;
+  const bool good = finite && state[b] == 0 && cnt >= min_count;
+  for (int k = 0; k < 9; ++k) out.r[(size_t)b * 9 + k] = (float)pose[(size_t)b * 12 + k];
+  for (int k = 0; k < 3; ++k) out.t[(size_t)b * 3 + k] = (float)pose[(size_t)b * 12 + 9 + k];
+  int k = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) {
+      const float v = finite ? (float)s[k] : 0.0f;
+      out.information[(size_t)b * 36 + i * 6 + j] = v;
+      out.information[(size_t)b * 36 + j * 6 + i] = v;
+      ++k;
+    }
+  out.rmse[b] = (finite && cnt > 0) ? (float)sqrt(s[27] / (double)cnt) : 0.0f;
+  out.count[b] = finite ? cnt : 0;
+  out.steps[b] = steps[b];
+  out.ok[b] = good ? 1 : 0;
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------
+int icp_shape_status(int batch, int h, int w) {
+  if (batch < 1 || h < 3 || w < 3) return MI_E_SHAPE;
+  if (batch > 65535) return MI_E_PARAM;
+  if ((long long)batch * h * w >= 0x80000000LL) return MI_E_SHAPE;
+  return MI_OK;
+}
+bool icp_stride_ok(int s) { return s == 1 || s == 2 || s == 4 || s == 8; }
+bool icp_positive(float v) { return v > 0.0f && v < INFINITY; }
+int icp_gate_status(float fx, float fy, float cx, float cy, float distance_threshold, float angle_threshold) {
+  if (!icp_positive(fx) || !icp_positive(fy) || !(fabsf(cx) < INFINITY) || !(fabsf(cy) < INFINITY) ||
+      !icp_positive(distance_threshold) || !(angle_threshold > 0.0f) || !(angle_threshold <= 3.14159274f))
+    return MI_E_PARAM;
+  return MI_OK;
+}
+int icp_samples(int h, int w, int s, int *ws) {
+  *ws = (w + s - 1) / s;
+  return ((h + s - 1) / s) * *ws;
+}
+
+struct IcpWork {
+  double *pose, *slabs;
+  int *state, *steps;
+  int max_slabs;
+  size_t total;
+};
+IcpWork icp_carve(void *ws, int batch, int h, int w) {
+  char *base = static_cast<char *>(ws);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { char *q = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
+  IcpWork k;
+  k.max_slabs = ceil_div(h * w, ICP_SLAB);                   // stride 1
+  k.pose = reinterpret_cast<double *>(take((size_t)batch * 12 * sizeof(double)));
+  k.slabs = reinterpret_cast<double *>(take((size_t)batch * k.max_slabs * ICP_REC * sizeof(double)));
+  k.state = reinterpret_cast<int *>(take((size_t)batch * sizeof(int)));
+  k.steps = reinterpret_cast<int *>(take((size_t)batch * sizeof(int)));
+  k.total = off;
+  return k;
+}
+
+// one linearisation: K18r over the slabs of `stride`, then K18s in `mode`
+int icp_linearise_launch(const float4 *v1, const float4 *n1, const float4 *v2, const float4 *n2, const float *r, const float *t,
+                         bool from_workspace, int batch, int h, int w, int stride, IcpCam cam, float thr2, float cos_thr,
+                         int mode, int min_count, const IcpWork &k, IcpOut out, hipStream_t s) {
+  int ws;
+  const int samples = icp_samples(h, w, stride, &ws), nslabs = ceil_div(samples, ICP_SLAB);
+  hipLaunchKernelGGL(icp_reduce_kernel, dim3((unsigned)nslabs, (unsigned)batch), dim3(ICP_THREADS), 0, s, v1, n1, v2, n2, r, t,
+                     from_workspace ? k.pose : nullptr, (from_workspace && mode == ICP_MODE_STEP) ? k.state : nullptr, h, w, stride,
+                     ws, samples, k.max_slabs, cam, thr2, cos_thr, k.slabs);
+  MI_CHECK_LAUNCH();
+  hipLaunchKernelGGL(icp_solve_kernel, dim3((unsigned)batch), dim3(64), 0, s, k.slabs, nslabs, k.max_slabs, mode, min_count,
+                     k.pose, k.state, k.steps, out);
+  return mi_launch_status();
+}
+
+}  // namespace
+
+extern "C" int mi_surfel_maps(const void *depth, int depth_is_u16, int batch, int h, int w, const float *k_inv, float z_scale,
+                              float min_depth, float max_depth, float normal_max_jump, float *vertex_out, float *normal_out,
+                              mi_stream_t stream) {
+  MI_ENTER();
+  if (!depth || !k_inv || !vertex_out || !normal_out) return MI_E_NULL;
+  if (const int s = icp_shape_status(batch, h, w)) return s;
+  if (!(min_depth > 0.0f) || !(max_depth >= min_depth) || !(max_depth < INFINITY) || !icp_positive(z_scale) ||
+      !icp_positive(normal_max_jump))
+    return MI_E_PARAM;
+  if (((uintptr_t)vertex_out % 16) != 0 || ((uintptr_t)normal_out % 16) != 0) return MI_E_ALIGN;
+  const long long total = (long long)batch * h * w;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  float4 *v = reinterpret_cast<float4 *>(vertex_out), *n = reinterpret_cast<float4 *>(normal_out);
+  if (depth_is_u16)
+    hipLaunchKernelGGL(icp_surfel_kernel<uint16_t>, grid, dim3(256), 0, (hipStream_t)stream, static_cast<const uint16_t *>(depth),
+                       h, w, total, k_inv, z_scale, min_depth, max_depth, normal_max_jump, v, n);
+  else
+    hipLaunchKernelGGL(icp_surfel_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, static_cast<const float *>(depth), h, w,
+                       total, k_inv, z_scale, min_depth, max_depth, normal_max_jump, v, n);
+  return mi_launch_status();
+}
+
+extern "C" size_t mi_icp_workspace_bytes(int batch, int h, int w) {
+  if (icp_shape_status(batch, h, w) != MI_OK) return 0;
+  return icp_carve(nullptr, batch, h, w).total;
+}
+
+extern "C" int mi_icp_linearise(const float *vertex1, const float *normal1, const float *vertex2, const float *normal2,
+                                const float *r, const float *t, int batch, int h, int w, float fx, float fy, float cx, float cy,
+                                int stride, float distance_threshold, float angle_threshold, double *sums, void *workspace,
+                                size_t workspace_bytes, mi_stream_t stream) {
+  MI_ENTER();
+  if (!vertex1 || !normal1 || !vertex2 || !normal2 || !r || !t || !sums || !workspace) return MI_E_NULL;
+  if (const int s = icp_shape_status(batch, h, w)) return s;
+  if (!icp_stride_ok(stride)) return MI_E_PARAM;
+  if (const int s = icp_gate_status(fx, fy, cx, cy, distance_threshold, angle_threshold)) return s;
+  if (((uintptr_t)workspace % 16) != 0 || ((uintptr_t)vertex1 % 16) != 0 || ((uintptr_t)normal1 % 16) != 0 ||
+      ((uintptr_t)vertex2 % 16) != 0 || ((uintptr_t)normal2 % 16) != 0)
+    return MI_E_ALIGN;
+  if (workspace_bytes < mi_icp_workspace_bytes(batch, h, w)) return MI_E_CAPACITY;
+  const IcpWork k = icp_carve(workspace, batch, h, w);
+  IcpOut out = {};
+  out.sums = sums;
+  return icp_linearise_launch(reinterpret_cast<const float4 *>(vertex1), reinterpret_cast<const float4 *>(normal1),
+                              reinterpret_cast<const float4 *>(vertex2), reinterpret_cast<const float4 *>(normal2), r, t, false,
+                              batch, h, w, stride, IcpCam{fx, fy, cx, cy}, distance_threshold * distance_threshold,
+                              (float)cos((double)angle_threshold), ICP_MODE_SUMS, 0, k, out, (hipStream_t)stream);
+}
+
+extern "C" int mi_icp_refine(const float *vertex1, const float *normal1, const float *vertex2, const float *normal2,
+                             const float *r0, const float *t0, int batch, int h, int w, float fx, float fy, float cx, float cy,
+                             const int32_t *strides, const int32_t *iterations, int stages, float distance_threshold,
+                             float angle_threshold, int min_correspondences, float *r, float *t, float *information, float *rmse,
+                             int32_t *count, int32_t *steps, uint8_t *ok, void *workspace, size_t workspace_bytes,
+                             mi_stream_t stream) {
+  MI_ENTER();
+  if (!vertex1 || !normal1 || !vertex2 || !normal2 || !r0 || !t0 || !strides || !iterations || !r || !t || !information ||
+      !rmse || !count || !steps || !ok || !workspace)
+    return MI_E_NULL;
+  if (const int s = icp_shape_status(batch, h, w)) return s;
+  if (stages < 1 || stages > MI_ICP_MAX_STAGES || min_correspondences < 1) return MI_E_PARAM;
+  int all = 0;
+  for (int i = 0; i < stages; ++i) {
+    if (!icp_stride_ok(strides[i]) || iterations[i] < 0 || iterations[i] > MI_ICP_MAX_ITERATIONS) return MI_E_PARAM;
+    all += iterations[i];
+  }
+  if (all > MI_ICP_MAX_ITERATIONS) return MI_E_PARAM;
+  if (const int s = icp_gate_status(fx, fy, cx, cy, distance_threshold, angle_threshold)) return s;
+  if (((uintptr_t)workspace % 16) != 0 || ((uintptr_t)vertex1 % 16) != 0 || ((uintptr_t)normal1 % 16) != 0 ||
+      ((uintptr_t)vertex2 % 16) != 0 || ((uintptr_t)normal2 % 16) != 0)
+    return MI_E_ALIGN;
+  if (workspace_bytes < mi_icp_workspace_bytes(batch, h, w)) return MI_E_CAPACITY;
+  const IcpWork k = icp_carve(workspace, batch, h, w);
+  hipStream_t s = (hipStream_t)stream;
+  const float4 *v1 = reinterpret_cast<const float4 *>(vertex1), *n1 = reinterpret_cast<const float4 *>(normal1);
+  const float4 *v2 = reinterpret_cast<const float4 *>(vertex2), *n2 = reinterpret_cast<const float4 *>(normal2);
+  const IcpCam cam{fx, fy, cx, cy};
+  const float thr2 = distance_threshold * distance_threshold, cos_thr = (float)cos((double)angle_threshold);
+  hipLaunchKernelGGL(icp_init_kernel, dim3((unsigned)ceil_div(batch, 64)), dim3(64), 0, s, r0, t0, batch, k.pose, k.state, k.steps);
+  MI_CHECK_LAUNCH();
+  IcpOut out = {};
+  for (int st = 0; st < stages; ++st)
+    for (int it = 0; it < iterations[st]; ++it)
+      if (const int e = icp_linearise_launch(v1, n1, v2, n2, nullptr, nullptr, true, batch, h, w, strides[st], cam, thr2, cos_thr,
+                                             ICP_MODE_STEP, min_correspondences, k, out, s))
+        return e;
+  out.r = r; out.t = t; out.information = information; out.rmse = rmse; out.count = count; out.steps = steps; out.ok = ok;
+  return icp_linearise_launch(v1, n1, v2, n2, nullptr, nullptr, true, batch, h, w, strides[stages - 1], cam, thr2, cos_thr,
+                              ICP_MODE_FINAL, min_correspondences, k, out, s);
+}

@@ -1301,6 +1301,101 @@ def rigid_ransac(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | N
     return r, t, inlier.view(torch.bool), best_h, count, rmse, ok.view(torch.bool)
 
 
+# ---- K18 dense RGB-D refinement (include/mi355x_match.h, "dense RGB-D refinement") ------------------------------------------
+
+ICP_MAX_STAGES = 4                         # MI_ICP_MAX_STAGES
+ICP_MAX_ITERATIONS = 64                    # MI_ICP_MAX_ITERATIONS
+ICP_STRIDES = (1, 2, 4, 8)
+ICP_SUMS = 29
+
+
+def surfel_maps(depth: torch.Tensor, k_inv: torch.Tensor, z_scale: float = 1.0, min_depth: float = 0.1, max_depth: float = 10.0,
+                normal_max_jump: float = 0.1):
+    """`mi_surfel_maps`: depth (B, H, W), float32 or uint16, aligned to the camera of k_inv (3, 3) -> (vertex, normal), each
+    (B, H, W, 4) float32: the camera-frame point and the camera-facing surface normal of every pixel, with 1 / 0 in the
+    fourth component for valid / invalid (invalid records are zero).  Current stream, no synchronisation, capturable."""
+    if not depth.is_cuda:
+        raise RuntimeError(f"surfel_maps: depth must live on the GPU (got device {depth.device}); this package has no CPU path")
+    if depth.dtype not in (F32, U16):
+        raise RuntimeError(f"surfel_maps: depth must be float32 or uint16, got {depth.dtype}")
+    if depth.dim() != 3 or depth.shape[1] < 3 or depth.shape[2] < 3 or depth.shape[0] < 1:
+        raise RuntimeError(f"surfel_maps: depth must be (B, H, W) with H, W >= 3, got {tuple(depth.shape)}")
+    if not min_depth > 0 or not max_depth >= min_depth or not z_scale > 0 or not normal_max_jump > 0:
+        raise RuntimeError(f"surfel_maps: need 0 < min_depth <= max_depth, z_scale > 0 and normal_max_jump > 0, got {min_depth}, "
+                           f"{max_depth}, {z_scale}, {normal_max_jump}")
+    d = depth.contiguous()
+    ki = k_inv.float().contiguous()
+    if tuple(ki.shape) != (3, 3):
+        raise RuntimeError(f"surfel_maps: K_inv must be (3, 3), got {tuple(k_inv.shape)}")
+    b, h, w = (int(x) for x in d.shape)
+    vertex = torch.empty((b, h, w, 4), dtype=F32, device=d.device)
+    normal = torch.empty((b, h, w, 4), dtype=F32, device=d.device)
+    N.call("mi_surfel_maps", d.data_ptr(), int(d.dtype == U16), b, h, w, N.dev(ki, F32, "K_inv"), float(z_scale), float(min_depth),
+           float(max_depth), float(normal_max_jump), vertex.data_ptr(), normal.data_ptr(), N.stream_ptr())
+    return vertex, normal
+
+
+def _icp_inputs(maps1, maps2, r: torch.Tensor, t: torch.Tensor, camera, what: str):
+    v1, n1 = maps1
+    v2, n2 = maps2
+    if not v1.is_cuda:
+        raise RuntimeError(f"{what}: the maps must live on the GPU (got device {v1.device}); this package has no CPU path")
+    if v1.dim() != 4 or v1.shape[-1] != 4 or any(x.shape != v1.shape or x.dtype != F32 for x in (n1, v2, n2)):
+        raise RuntimeError(f"{what}: the four maps must be float32 (B, H, W, 4) of one shape, got {tuple(v1.shape)}, "
+                           f"{tuple(n1.shape)}, {tuple(v2.shape)}, {tuple(n2.shape)}")
+    b, h, w = int(v1.shape[0]), int(v1.shape[1]), int(v1.shape[2])
+    rr, tt = r.float().contiguous(), t.float().contiguous()
+    if tuple(rr.shape) != (b, 3, 3) or tuple(tt.shape) != (b, 3):
+        raise RuntimeError(f"{what}: the pose must be ({b}, 3, 3) and ({b}, 3), got {tuple(r.shape)} and {tuple(t.shape)}")
+    keep = tuple(x.contiguous() for x in (v1, n1, v2, n2))
+    maps = tuple(N.dev(x, F32, "maps") for x in keep)
+    fx, fy, cx, cy = (float(x) for x in camera)
+    wbytes = int(N.load().mi_icp_workspace_bytes(b, h, w))
+    if wbytes == 0:
+        raise RuntimeError(f"{what}: unsupported request (batch {b}, {h} x {w})")
+    work = torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=v1.device)
+    return keep, maps, rr, tt, (fx, fy, cx, cy), b, h, w, work, wbytes
+
+
+def icp_linearise(maps1, maps2, r: torch.Tensor, t: torch.Tensor, camera, stride: int = 1, distance_threshold: float = 0.1,
+                  angle_threshold: float = 0.5235987755982988):
+    """`mi_icp_linearise`: one point-to-plane linearisation of frame 1's surfels (maps1 = (vertex, normal) of `surfel_maps`)
+    against frame 2's at the pose r (B, 3, 3), t (B, 3), camera = (fx, fy, cx, cy), over every stride-th source pixel ->
+    sums (B, 29) float64: A's upper triangle row-major (21), b (6), sum r^2, count.  angle_threshold in radians."""
+    keep, maps, rr, tt, cam, b, h, w, work, wbytes = _icp_inputs(maps1, maps2, r, t, camera, "icp_linearise")
+    sums = torch.empty((b, ICP_SUMS), dtype=torch.float64, device=rr.device)
+    N.call("mi_icp_linearise", *maps, N.dev(rr, F32, "r"), N.dev(tt, F32, "t"), b, h, w, *cam, int(stride),
+           float(distance_threshold), float(angle_threshold), sums.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    return sums
+
+
+def icp_refine(maps1, maps2, r0: torch.Tensor, t0: torch.Tensor, camera, schedule=((4, 4), (2, 4), (1, 6)),
+               distance_threshold: float = 0.1, angle_threshold: float = 0.5235987755982988, min_correspondences: int = 64):
+    """`mi_icp_refine`: projective point-to-plane ICP from (r0, t0) over the schedule's (stride, iterations) stages ->
+    (R (B, 3, 3), t (B, 3), information (B, 6, 6) float32, rmse (B,) float32, count (B,) int32, steps (B,) int32,
+    ok (B,) bool).  X2 = R X1 + t.  A pair whose system is degenerate keeps the pose before the failed solve, ok = False."""
+    import ctypes
+    keep, maps, rr, tt, cam, b, h, w, work, wbytes = _icp_inputs(maps1, maps2, r0, t0, camera, "icp_refine")
+    sched = [(int(s), int(i)) for s, i in schedule]
+    if not 1 <= len(sched) <= ICP_MAX_STAGES:
+        raise RuntimeError(f"icp_refine: the schedule needs 1 .. {ICP_MAX_STAGES} stages, got {len(sched)}")
+    strides = (ctypes.c_int32 * len(sched))(*[s for s, _ in sched])
+    iters = (ctypes.c_int32 * len(sched))(*[i for _, i in sched])
+    dev = rr.device
+    r = torch.empty((b, 3, 3), dtype=F32, device=dev)
+    t = torch.empty((b, 3), dtype=F32, device=dev)
+    info = torch.empty((b, 6, 6), dtype=F32, device=dev)
+    rmse = torch.empty((b,), dtype=F32, device=dev)
+    count = torch.empty((b,), dtype=I32, device=dev)
+    steps = torch.empty((b,), dtype=I32, device=dev)
+    ok = torch.empty((b,), dtype=U8, device=dev)
+    N.call("mi_icp_refine", *maps, N.dev(rr, F32, "r0"), N.dev(tt, F32, "t0"), b, h, w, *cam,
+           ctypes.cast(strides, ctypes.c_void_p), ctypes.cast(iters, ctypes.c_void_p), len(sched), float(distance_threshold),
+           float(angle_threshold), int(min_correspondences), r.data_ptr(), t.data_ptr(), info.data_ptr(), rmse.data_ptr(),
+           count.data_ptr(), steps.data_ptr(), ok.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    return r, t, info, rmse, count, steps, ok.view(torch.bool)
+
+
 # ---- K16 frame ingest (sample/visual_odometry.py:65-92 load_image_from_array) ------------------------------------------
 
 INGEST_MAX_DIM = 16384             # include/mi355x_match.h MI_INGEST_MAX_DIM

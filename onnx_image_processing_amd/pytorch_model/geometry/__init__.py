@@ -1,5 +1,6 @@
+from .dense_rgbd import DenseRgbdRefiner
 from .essential_matrix_estimator import EssentialMatrixEstimator
 from .relative_pose import RelativePoseEstimator, triangulate_points
 from .rgbd_pose import RgbdPoseEstimator
 
-__all__ = ["EssentialMatrixEstimator", "RelativePoseEstimator", "RgbdPoseEstimator", "triangulate_points"]
+__all__ = ["DenseRgbdRefiner", "EssentialMatrixEstimator", "RelativePoseEstimator", "RgbdPoseEstimator", "triangulate_points"]

@@ -345,3 +345,58 @@ def synth_colour_frame(seed: int, height: int, width: int, channels: int = 3) ->
         noise = (_hash3(seed, yy, xx, 40 + c) % np.uint64(13)).astype(np.int64) - 6
         out[:, :, c] = np.clip(base * gains[c if channels > 1 else 1] // 10 + noise, 0, 255)
     return out
+
+
+def synth_depth_room(seed: int, height: int, width: int, rotation_deg: float = 2.0, translation: float = 0.05,
+                     sphere: bool = True):
+    """Two dense depth frames of one room for the dense refinement kernels: (depth1, depth2, R, t).  depth (height, width)
+    float32 in metres, the Z of the nearest surface along the ray of every integer pixel under rgbd_camera(height, width),
+    ray-cast analytically in float64; R (3, 3), t (3,) float64 with X2 = R X1 + t.
+
+    The room, in the first camera's frame (y down): the floor y = 0.9, two walls n . X = c with n = (+-sqrt(.5), 0, sqrt(.5))
+    and c = 3 sqrt(.5) + 0.3 and 3 sqrt(.5) - 0.1 (a corner ahead of the camera) and, with `sphere`, a sphere of radius 0.4
+    at (0.3, 0.4, 2.2).  Without the sphere the scene is three planes, whose registration is ill-conditioned at coarse
+    strides: use it only where degeneracy is the point.  The second view is rotated by rotation_deg about a seeded random
+    axis and moved by `translation` metres in a seeded random direction.  Every pixel of both frames has a depth."""
+    K = rgbd_camera(height, width)
+    three = np.arange(3, dtype=np.uint64)
+
+    def normal3(salt):
+        u1 = ((_hash3(seed, three, np.uint64(salt) + 0 * three, 29) >> np.uint64(11)).astype(np.float64) + 0.5) / float(1 << 53)
+        u2 = ((_hash3(seed, three, np.uint64(salt + 1) + 0 * three, 29) >> np.uint64(11)).astype(np.float64) + 0.5) / float(1 << 53)
+        return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+
+    k = normal3(0)
+    k = k / np.linalg.norm(k)
+    th = np.deg2rad(rotation_deg)
+    kx = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    R = np.eye(3) + np.sin(th) * kx + (1.0 - np.cos(th)) * (kx @ kx)
+    d = normal3(2)
+    t = translation * d / np.linalg.norm(d)
+    s5 = np.sqrt(0.5)
+    planes = [(np.array([0.0, 1.0, 0.0]), 0.9), (np.array([s5, 0.0, s5]), 3.0 * s5 + 0.3), (np.array([-s5, 0.0, s5]), 3.0 * s5 - 0.1)]
+    centre, radius = np.array([0.3, 0.4, 2.2]), 0.4
+    ys, xs = np.meshgrid(np.arange(height, dtype=np.float64), np.arange(width, dtype=np.float64), indexing="ij")
+    rays = np.stack([(xs - K[0, 2]) / K[0, 0], (ys - K[1, 2]) / K[1, 1], np.ones_like(xs)], axis=-1)
+
+    def cast(origin, rot):
+        """depth along rays `rot @ ray` from `origin`, both in the first camera's frame; the ray's own z is 1, so the ray
+        parameter is the depth in the casting camera"""
+        dirs = rays @ rot.T
+        best = np.full(xs.shape, np.inf)
+        for n, c in planes:
+            den = dirs @ n
+            with np.errstate(divide="ignore", invalid="ignore"):
+                s = (c - origin @ n) / den
+            best = np.where((den > 1e-12) & (s > 0) & (s < best), s, best)
+        if sphere:
+            oc = origin - centre
+            a = (dirs * dirs).sum(-1)
+            bq = dirs @ oc
+            disc = bq * bq - a * (oc @ oc - radius * radius)
+            with np.errstate(invalid="ignore"):
+                s = (-bq - np.sqrt(disc)) / a
+            best = np.where((disc > 0) & (s > 0) & (s < best), s, best)
+        return np.where(np.isfinite(best), best, 0.0).astype(np.float32)
+
+    return cast(np.zeros(3), np.eye(3)), cast(-R.T @ t, R.T), R, t
