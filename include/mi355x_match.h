@@ -988,6 +988,79 @@ MI_API int mi_icp_refine(const float *vertex1, const float *normal1, const float
                          int32_t *count, int32_t *steps, uint8_t *ok, void *workspace, size_t workspace_bytes,
                          mi_stream_t stream);
 
+/* ---- TSDF fusion (K19): depth frames -> a fused signed distance volume -> a synthetic surfel map for K18 -----------------------
+ * K17 and K18 estimate each pose against ONE noisy depth frame.  This section accumulates depth frames into a truncated
+ * signed distance volume and raycasts the volume, at a predicted pose, into a surfel map in exactly mi_surfel_maps' record
+ * layout and validity convention, which mi_icp_linearise / mi_icp_refine take as `vertex1` / `normal1` unchanged: frame-to-model
+ * tracking.  The reference has no counterpart.  Four entries, batched over volumes, under the contract of the K15 / K17 / K18
+ * sections: pure functions of their arguments, no allocation, no synchronisation, no memset, no atomics, one stream,
+ * capturable into a hipGraph; every output element is written whatever the buffers held on entry; MI_E_* before any launch;
+ * a volume's result is the same bits alone or inside a batch, and from run to run.  Per-voxel and per-sample arithmetic is
+ * float32 with nothing fused.
+ *
+ * Volume.  (batch, nz, ny, nx) voxels, x fastest; a voxel is a record of two float32 (tsdf, weight), 8 bytes; the base is
+ *   16-byte aligned (MI_E_ALIGN).  origin (x, y, z), voxel_size and truncation are host parameters shared by the batch.  The
+ *   centre of voxel (i, j, k) is ((i + 0.5f) * voxel_size) + origin_x, and likewise for j, k with origin_y, origin_z.  An empty
+ *   voxel is (1, 0).  Poses are world (the volume's frame) to camera, X_c = R X_w + t: K17 / K18's X2 = R X1 + t with the volume
+ *   as frame 1.
+ * Checks common to the volume entries: batch < 1, a dimension < 2, batch * nz * ny * nx >= 2^31: MI_E_SHAPE; batch > 65535,
+ *   an origin component not finite, voxel_size or truncation <= 0 or not finite: MI_E_PARAM.
+ *
+ * Integration, per voxel with centre p, for the frames f = 0 .. frames-1 in order (a frame whose `active` byte is 0 is left out):
+ *     q_j = ((R_j0 p_0 + R_j1 p_1) + R_j2 p_2) + t_j                                      skip when q_2 <= 0
+ *     px = floorf((fx * (q_0 / q_2) + cx) + 0.5f), py = floorf((fy * (q_1 / q_2) + cy) + 0.5f)   skip outside the w x h frame
+ *     d = depth[py][px], Z = d * z_scale                         skip unless d is finite and min_depth <= Z <= max_depth
+ *     sdf = Z - q_2                                              skip when sdf < -truncation
+ *     f = fminf(1, sdf / truncation);  tsdf <- (tsdf * weight + f) / (weight + 1);  weight <- fminf(weight + 1, max_weight)
+ *   The volume makes ONE pass through memory however many frames: a voxel is read once, updated in registers by every frame,
+ *   written once (8 bytes in, 8 bytes out).  Frames given in one call and the same frames given one per call give the same bits.
+ *
+ * Raycast, per integer pixel (x, y): xn = (x k_inv[0] + y k_inv[1]) + k_inv[2], yn = (x k_inv[3] + y k_inv[4]) + k_inv[5], the
+ *   ray of mi_surfel_maps.  Samples lie on a FIXED grid of camera depths s_k = ((float)k * step) + min_depth, step =
+ *   step_fraction * truncation (one float32 product), k = 0 .. ceilf((max_depth - min_depth) / step) (float32).  A kernel may
+ *   leave out ranges of k whose samples lie outside the volume's box (they are invalid); it may not move the grid.
+ *   Sample at depth s: c = (xn * s - t_0, yn * s - t_1, s - t_2); X_w,j = (R_0j c_0 + R_1j c_1) + R_2j c_2 (R^T c);
+ *     g_j = (X_w,j - origin_j) / voxel_size - 0.5f, the grid coordinate (voxel centres at the integers).  With b = floorf(g) and
+ *     a = g - b per axis the sample is the trilinear interpolation of tsdf over the eight corners b + {0, 1}^3, along x, then y,
+ *     then z, each step as u + a * (v - u).  It is VALID only when the eight corners exist (0 <= b_j <= n_j - 2 on every axis)
+ *     and all eight have weight > 0.
+ *   The march ends at the first valid sample with f <= 0; it is a HIT only if the sample before it on the grid (k - 1) was valid
+ *     with f_prev > 0: s* = s_prev + step * (f_prev / (f_prev - f)), vertex = (xn * s*, yn * s*, s*, 1).
+ *   Normal: with g* the grid coordinate of the depth s* (formed as for a sample), G_j = F(g* + e_j) - F(g* - e_j) for the three
+ *     axes, F the trilinear sample and e_j one voxel (the coordinate g*_j + 1.0f or g*_j - 1.0f); all six samples must be valid.
+ *     m_j = (R_j0 G_0 + R_j1 G_1) + R_j2 G_2, |m|^2 = (m_0^2 + m_1^2) + m_2^2, n = m / sqrt(|m|^2), negated when
+ *     (n_0 v_0 + n_1 v_1) + n_2 v_2 > 0; normal = (n, 1) when |m|^2 is positive and finite, else zeros (the vertex stays).
+ *   No hit: both records are zeros. */
+
+/* (1, 0) into every voxel of volume (batch, nz, ny, nx, 2).  One launch. */
+MI_API int mi_tsdf_reset(float *volume, int batch, int nz, int ny, int nx, mi_stream_t stream);
+
+/* depth (batch, frames, h, w), float32 (depth_is_u16 = 0) or uint16 counts (1), ALREADY aligned to the camera (fx, fy, cx, cy);
+ * r (batch, frames, 3, 3), t (batch, frames, 3) float32; active (batch, frames) bytes in device memory, read by the kernel
+ * (non-zero = integrate; NULL: every frame), so that a tracker's `ok` gates the integration without a host synchronisation.
+ * frames < 1, h or w < 3, batch * frames * h * w >= 2^31: MI_E_SHAPE; max_weight, fx, fy or z_scale <= 0 or not finite, cx or
+ * cy not finite, min_depth <= 0, max_depth < min_depth or not finite: MI_E_PARAM.  One launch, a wave per x-row of the volume. */
+MI_API int mi_tsdf_integrate(float *volume, int batch, int nz, int ny, int nx, float origin_x, float origin_y, float origin_z,
+                             float voxel_size, float truncation, float max_weight, const void *depth, int depth_is_u16, int frames,
+                             int h, int w, float fx, float fy, float cx, float cy, float z_scale, float min_depth, float max_depth,
+                             const float *r, const float *t, const uint8_t *active, mi_stream_t stream);
+
+/* volume + one pose per volume, r (batch, 3, 3), t (batch, 3) -> vertex_out, normal_out (batch, h, w, 4) float32, 16-byte
+ * aligned (MI_E_ALIGN), in the camera frame.  k_inv: 3x3 row-major inverse camera matrix, device memory.  h or w < 3,
+ * batch * h * w >= 2^31: MI_E_SHAPE; step_fraction <= 0, > 1 or not finite, min_depth <= 0, max_depth < min_depth or not finite,
+ * 2^24 or more samples on a ray: MI_E_PARAM.  One launch, a wave per 8 x 8 pixel tile. */
+MI_API int mi_tsdf_raycast(const float *volume, int batch, int nz, int ny, int nx, float origin_x, float origin_y, float origin_z,
+                           float voxel_size, float truncation, float step_fraction, const float *r, const float *t, int h, int w,
+                           const float *k_inv, float min_depth, float max_depth, float *vertex_out, float *normal_out,
+                           mi_stream_t stream);
+
+/* (ra, ta) o (rb, tb) per item: r = ra rb, t = ra tb + ta, (batch, 3, 3) and (batch, 3) float32.  Every product in float64,
+ * every sum as (a + b) + c (+ ta_i) in float64, rounded once to float32: composing the identity returns the other pose's bits.
+ * A tracked pose (mi_icp_refine's result onto the prediction) then needs no host arithmetic and stays capturable.  The outputs
+ * may not alias the inputs.  batch < 1: MI_E_SHAPE.  One launch. */
+MI_API int mi_pose_compose(const float *ra, const float *ta, const float *rb, const float *tb, int batch, float *r, float *t,
+                           mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,6 +139,13 @@ SIGNATURES = {
     "mi_icp_refine": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float,
                       c_float, c_void_p, c_void_p, c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    "mi_tsdf_reset": [c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "mi_tsdf_integrate": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p,
+                          c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p,
+                          c_void_p, c_void_p, c_void_p],
+    "mi_tsdf_raycast": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p,
+                        c_void_p, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p],
+    "mi_pose_compose": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
 }
 
 

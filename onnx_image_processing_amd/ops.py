@@ -1396,6 +1396,106 @@ def icp_refine(maps1, maps2, r0: torch.Tensor, t0: torch.Tensor, camera, schedul
     return r, t, info, rmse, count, steps, ok.view(torch.bool)
 
 
+# ---- K19 TSDF fusion (include/mi355x_match.h, "TSDF fusion") ------------------------------------------------------------------
+
+def _tsdf_volume(volume: torch.Tensor, what: str):
+    if not volume.is_cuda:
+        raise RuntimeError(f"{what}: the volume must live on the GPU (got device {volume.device}); this package has no CPU path")
+    if volume.dtype != F32 or volume.dim() != 5 or volume.shape[-1] != 2 or min(volume.shape[:4]) < 1 or min(volume.shape[1:4]) < 2:
+        raise RuntimeError(f"{what}: the volume must be float32 (B, NZ, NY, NX, 2) with NZ, NY, NX >= 2, got {volume.dtype} "
+                           f"{tuple(volume.shape)}")
+    return N.dev(volume, F32, "volume"), tuple(int(x) for x in volume.shape[:4])
+
+
+def _tsdf_grid(origin, voxel_size: float, truncation: float, what: str):
+    o = tuple(float(x) for x in origin)
+    if len(o) != 3 or not voxel_size > 0 or not truncation > 0:
+        raise RuntimeError(f"{what}: need an origin of 3 values, voxel_size > 0 and truncation > 0, got {origin}, {voxel_size}, "
+                           f"{truncation}")
+    return (*o, float(voxel_size), float(truncation))
+
+
+def tsdf_reset(volume: torch.Tensor) -> torch.Tensor:
+    """`mi_tsdf_reset`: (tsdf, weight) = (1, 0) into every voxel of volume (B, NZ, NY, NX, 2) float32, in place."""
+    ptr, dims = _tsdf_volume(volume, "tsdf_reset")
+    N.call("mi_tsdf_reset", ptr, *dims, N.stream_ptr())
+    return volume
+
+
+def tsdf_integrate(volume: torch.Tensor, depth: torch.Tensor, r: torch.Tensor, t: torch.Tensor, camera, origin, voxel_size: float,
+                   truncation: float, max_weight: float = 64.0, z_scale: float = 1.0, min_depth: float = 0.1,
+                   max_depth: float = 10.0, active: torch.Tensor | None = None) -> torch.Tensor:
+    """`mi_tsdf_integrate`: depth (B, F, H, W), float32 or uint16, aligned to camera = (fx, fy, cx, cy), with the world-to-camera
+    poses r (B, F, 3, 3), t (B, F, 3), fused into volume (B, NZ, NY, NX, 2) in place, the frames in order, in one pass over the
+    volume.  active (B, F) bool / uint8 on the GPU (None: every frame) is read by the kernel: no synchronisation."""
+    ptr, dims = _tsdf_volume(volume, "tsdf_integrate")
+    if not depth.is_cuda:
+        raise RuntimeError(f"tsdf_integrate: depth must live on the GPU (got device {depth.device}); this package has no CPU path")
+    if depth.dtype not in (F32, U16):
+        raise RuntimeError(f"tsdf_integrate: depth must be float32 or uint16, got {depth.dtype}")
+    b = dims[0]
+    if depth.dim() != 4 or depth.shape[0] != b or depth.shape[1] < 1 or depth.shape[2] < 3 or depth.shape[3] < 3:
+        raise RuntimeError(f"tsdf_integrate: depth must be ({b}, F, H, W) with F >= 1 and H, W >= 3, got {tuple(depth.shape)}")
+    d = depth.contiguous()
+    f, h, w = (int(x) for x in d.shape[1:])
+    rr, tt = r.float().contiguous(), t.float().contiguous()
+    if tuple(rr.shape) != (b, f, 3, 3) or tuple(tt.shape) != (b, f, 3):
+        raise RuntimeError(f"tsdf_integrate: the poses must be ({b}, {f}, 3, 3) and ({b}, {f}, 3), got {tuple(r.shape)} and "
+                           f"{tuple(t.shape)}")
+    act = None
+    if active is not None:
+        if active.dtype not in (torch.bool, U8) or tuple(active.shape) != (b, f):
+            raise RuntimeError(f"tsdf_integrate: active must be bool or uint8 ({b}, {f}), got {active.dtype} {tuple(active.shape)}")
+        act = active.contiguous().view(U8)
+    grid = _tsdf_grid(origin, voxel_size, truncation, "tsdf_integrate")
+    fx, fy, cx, cy = (float(x) for x in camera)
+    N.call("mi_tsdf_integrate", ptr, *dims, *grid, float(max_weight), d.data_ptr(), int(d.dtype == U16), f, h, w, fx, fy, cx, cy,
+           float(z_scale), float(min_depth), float(max_depth), N.dev(rr, F32, "r"), N.dev(tt, F32, "t"),
+           N.dev(act, U8, "active") if act is not None else None, N.stream_ptr())
+    return volume
+
+
+def tsdf_raycast(volume: torch.Tensor, r: torch.Tensor, t: torch.Tensor, k_inv: torch.Tensor, size, origin, voxel_size: float,
+                 truncation: float, step_fraction: float = 0.5, min_depth: float = 0.1, max_depth: float = 10.0):
+    """`mi_tsdf_raycast`: volume (B, NZ, NY, NX, 2) seen from the world-to-camera poses r (B, 3, 3), t (B, 3) through the camera
+    of k_inv (3, 3) at size = (H, W) -> (vertex, normal), each (B, H, W, 4) float32 in the camera frame, in `surfel_maps`'
+    layout: what `icp_linearise` / `icp_refine` take as maps1."""
+    ptr, dims = _tsdf_volume(volume, "tsdf_raycast")
+    b = dims[0]
+    h, w = (int(x) for x in size)
+    if h < 3 or w < 3:
+        raise RuntimeError(f"tsdf_raycast: size must be (H, W) with H, W >= 3, got {size}")
+    rr, tt = r.float().contiguous(), t.float().contiguous()
+    if tuple(rr.shape) != (b, 3, 3) or tuple(tt.shape) != (b, 3):
+        raise RuntimeError(f"tsdf_raycast: the pose must be ({b}, 3, 3) and ({b}, 3), got {tuple(r.shape)} and {tuple(t.shape)}")
+    ki = k_inv.float().contiguous()
+    if tuple(ki.shape) != (3, 3):
+        raise RuntimeError(f"tsdf_raycast: K_inv must be (3, 3), got {tuple(k_inv.shape)}")
+    grid = _tsdf_grid(origin, voxel_size, truncation, "tsdf_raycast")
+    vertex = torch.empty((b, h, w, 4), dtype=F32, device=volume.device)
+    normal = torch.empty((b, h, w, 4), dtype=F32, device=volume.device)
+    N.call("mi_tsdf_raycast", ptr, *dims, *grid, float(step_fraction), N.dev(rr, F32, "r"), N.dev(tt, F32, "t"), h, w,
+           N.dev(ki, F32, "K_inv"), float(min_depth), float(max_depth), vertex.data_ptr(), normal.data_ptr(), N.stream_ptr())
+    return vertex, normal
+
+
+def pose_compose(ra: torch.Tensor, ta: torch.Tensor, rb: torch.Tensor, tb: torch.Tensor):
+    """`mi_pose_compose`: (ra, ta) o (rb, tb) = (ra rb, ra tb + ta) per item, (B, 3, 3) and (B, 3) float32, formed in float64 and
+    rounded once."""
+    if not ra.is_cuda:
+        raise RuntimeError(f"pose_compose: the poses must live on the GPU (got device {ra.device}); this package has no CPU path")
+    a, at, c, ct = (x.float().contiguous() for x in (ra, ta, rb, tb))
+    b = int(a.shape[0]) if a.dim() == 3 else 0
+    if b < 1 or any(tuple(x.shape) != (b, 3, 3) for x in (a, c)) or any(tuple(x.shape) != (b, 3) for x in (at, ct)):
+        raise RuntimeError(f"pose_compose: the poses must be (B, 3, 3) and (B, 3), got {tuple(ra.shape)}, {tuple(ta.shape)}, "
+                           f"{tuple(rb.shape)}, {tuple(tb.shape)}")
+    r = torch.empty((b, 3, 3), dtype=F32, device=a.device)
+    t = torch.empty((b, 3), dtype=F32, device=a.device)
+    N.call("mi_pose_compose", N.dev(a, F32, "ra"), N.dev(at, F32, "ta"), N.dev(c, F32, "rb"), N.dev(ct, F32, "tb"), b,
+           r.data_ptr(), t.data_ptr(), N.stream_ptr())
+    return r, t
+
+
 # ---- K16 frame ingest (sample/visual_odometry.py:65-92 load_image_from_array) ------------------------------------------
 
 INGEST_MAX_DIM = 16384             # include/mi355x_match.h MI_INGEST_MAX_DIM

@@ -2,5 +2,7 @@ from .dense_rgbd import DenseRgbdRefiner
 from .essential_matrix_estimator import EssentialMatrixEstimator
 from .relative_pose import RelativePoseEstimator, triangulate_points
 from .rgbd_pose import RgbdPoseEstimator
+from .tsdf_volume import TsdfVolume
 
-__all__ = ["DenseRgbdRefiner", "EssentialMatrixEstimator", "RelativePoseEstimator", "RgbdPoseEstimator", "triangulate_points"]
+__all__ = ["DenseRgbdRefiner", "EssentialMatrixEstimator", "RelativePoseEstimator", "RgbdPoseEstimator", "TsdfVolume",
+           "triangulate_points"]
