@@ -1061,6 +1061,64 @@ MI_API int mi_tsdf_raycast(const float *volume, int batch, int nz, int ny, int n
 MI_API int mi_pose_compose(const float *ra, const float *ta, const float *rb, const float *tb, int batch, float *r, float *t,
                            mi_stream_t stream);
 
+/* ---- TSDF surface extraction (K20): the fused volume -> an indexed triangle mesh with normals, or a point cloud --------------------
+ * The zero level set of a K19 volume by marching tetrahedra over the Kuhn split of every cell (no ambiguous faces: the mesh is
+ * closed wherever the volume is observed), what KinectFusion-style systems call extraction (Open3D: extract_triangle_mesh,
+ * extract_point_cloud).  The reference has no counterpart.  One pass over the volume, batched over volumes under the contract of
+ * the K19 section: no allocation, no synchronisation, no memset, no atomics, one stream, capturable; every output element is
+ * written; MI_E_* before any launch; a volume's result is the same bits alone or inside a batch, from run to run and under graph
+ * replay.  Arithmetic is float32 with nothing fused.  The volume, its origin and voxel_size are K19's.
+ *
+ * Observed and inside.  A voxel is OBSERVED iff weight >= min_weight (min_weight > 0; 1 is K19's weight > 0 for integrated
+ *   volumes).  An observed voxel is INSIDE iff !(tsdf > 0): the raycast's f <= 0, and NaN counts as inside.
+ * Cells and corners.  Cell (i, j, k), 0 <= i <= nx-2 and likewise j, k, has corners m = 0..7; corner m is voxel
+ *   (i + (m & 1), j + ((m >> 1) & 1), k + ((m >> 2) & 1)).
+ * Tetrahedra.  A cell is six tetrahedra around the diagonal 0-7, in this order, the corners of each in this path order
+ *   (t0, t1, t2, t3):  (0,1,3,7) (0,1,5,7) (0,2,3,7) (0,2,6,7) (0,4,5,7) (0,4,6,7).
+ * Edges.  Every tetrahedron edge joins corners p < q with q = p | e; e = q - p in 1..7 is the edge's class (1 = x, 2 = y, 3 = xy,
+ *   4 = z, 5 = xz, 6 = yz, 7 = xyz).  The edge is owned by the voxel at its lower end p: a voxel owns at most seven edges.
+ * Vertices.  A vertex exists on an edge iff both end voxels are observed and exactly one of them is inside (the two ends only:
+ *   neighbouring cells agree).  Its id is its rank in the order (owner's linear index (k ny + j) nx + i, then class ascending)
+ *   within its volume.  With f_p, f_q the ends' tsdf, a = f_p / (f_p - f_q).  The position is in the WORLD frame (the volume's):
+ *   on each axis the edge moves along, ((index_p + 0.5f) * voxel_size + origin) + a * voxel_size, on the others the centre of
+ *   index_p itself; the record is (x, y, z, 1).
+ * Normals.  At the grid coordinate g = ((float)index_p + a on the axes the edge moves along, (float)index_p on the others):
+ *   G_j = F(g + e_j) - F(g - e_j), F K19's trilinear sample (valid only over eight corners of weight > 0), all six samples valid;
+ *   len = sqrtf((G_0^2 + G_1^2) + G_2^2); the record is (G / len, 1), or zeros where a sample is invalid or len is not positive
+ *   and finite.  The normal points to the positive (free-space) side; it is not flipped.
+ * Triangles.  A tetrahedron emits triangles iff all four corners are observed; its case is the mask with bit s set iff t_s is
+ *   inside.  One corner s on its own side (1 or 3 inside): one triangle on the edges (s,u1), (s,u2), (s,u3), u1 < u2 < u3 the
+ *   other path positions.  Two inside, A < B, two outside, C < D (positions): (AC, AD, BD) then (AC, BD, BC).  Orientation: with
+ *   every vertex at its edge's midpoint in the unit cell, a triangle whose (v1 - v0) x (v2 - v0) points from the inside corners'
+ *   mean towards the outside corners' mean stays as it is; otherwise its last two vertices are swapped.  That is a fixed 6 x 16
+ *   table (csrc/surface_math.h generates it from this rule at compile time).  Triangles are ordered by (cell linear index
+ *   (k (ny-1) + j) (nx-1) + i, tetrahedron 0..5, triangle 0..1); each is three int32 vertex ids.
+ *   A node whose tsdf is exactly 0 gives a = 0 or 1 on its edges: their vertices coincide and the triangles between them have
+ *   zero area.  They are kept, so that the topology does not depend on it.
+ *
+ * Outputs, per volume: vertex_out (max_vertices, 4) float32; normal_out likewise, or NULL; triangle_out (max_triangles, 3) int32,
+ *   or NULL with max_triangles = 0 (a point cloud: no triangle is formed); counts_out (2) int32 = the TRUE totals (vertices,
+ *   triangles), even where they exceed the capacities.  Only vertices with id < max_vertices and triangles with ordinal <
+ *   max_triangles are written, the triangles with the true ids: a caller compares counts with capacities to detect an incomplete
+ *   mesh.  Rows from the count up to the capacity are written too: zeros for vertices and normals, (-1, -1, -1) for triangles.
+ *   With both capacities 0 the call is a sizing pass that writes the counts only: every output may be NULL, and an output
+ *   pointer that is given all the same (normal_out included) is checked for alignment and otherwise left alone. */
+
+/* bytes of workspace for mi_tsdf_surface (0 for a shape it refuses): one byte per voxel and 16 bytes per x-row. */
+MI_API size_t mi_tsdf_surface_workspace_bytes(int batch, int nz, int ny, int nx);
+
+/* volume (batch, nz, ny, nx, 2) -> vertex_out, normal_out (batch, max_vertices, 4), triangle_out (batch, max_triangles, 3),
+ * counts_out (batch, 2).  volume, vertex_out, normal_out and workspace 16-byte aligned, triangle_out and counts_out 4-byte
+ * (MI_E_ALIGN).  NULL volume, counts_out or workspace, NULL vertex_out with max_vertices != 0, NULL triangle_out with
+ * max_triangles != 0: MI_E_NULL.  K19's volume checks, 12 * nz * ny * nx >= 2^31 (ids must fit int32), batch * max_vertices or
+ * batch * max_triangles >= 2^31: MI_E_SHAPE.  batch > 65535, min_weight or voxel_size <= 0 or not finite, an origin component
+ * not finite, a capacity < 0: MI_E_PARAM.  workspace shorter than mi_tsdf_surface_workspace_bytes, of any content:
+ * MI_E_CAPACITY.  normal_out is optional at any capacity.  Three launches (two for the sizing pass). */
+MI_API int mi_tsdf_surface(const float *volume, int batch, int nz, int ny, int nx, float origin_x, float origin_y, float origin_z,
+                           float voxel_size, float min_weight, int max_vertices, int max_triangles, float *vertex_out,
+                           float *normal_out, int32_t *triangle_out, int32_t *counts_out, void *workspace, size_t workspace_bytes,
+                           mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

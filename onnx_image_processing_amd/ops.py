@@ -1496,6 +1496,56 @@ def pose_compose(ra: torch.Tensor, ta: torch.Tensor, rb: torch.Tensor, tb: torch
     return r, t
 
 
+# ---- K20 TSDF surface extraction (include/mi355x_match.h, "TSDF surface extraction") --------------------------------------------
+
+def _tsdf_surface_call(volume: torch.Tensor, origin, voxel_size: float, min_weight: float, max_vertices: int, max_triangles: int,
+                       normals: bool, triangles: bool, what: str):
+    ptr, dims = _tsdf_volume(volume, what)
+    o = tuple(float(x) for x in origin)
+    if len(o) != 3 or not voxel_size > 0 or not min_weight > 0:
+        raise RuntimeError(f"{what}: need an origin of 3 values, voxel_size > 0 and min_weight > 0, got {origin}, {voxel_size}, "
+                           f"{min_weight}")
+    mv, mt = int(max_vertices), int(max_triangles)
+    if mv < 0 or mt < 0:
+        raise RuntimeError(f"{what}: the capacities must not be negative, got {max_vertices} and {max_triangles}")
+    b, dev = dims[0], volume.device
+    wbytes = int(N.load().mi_tsdf_surface_workspace_bytes(*dims))
+    if wbytes == 0:
+        raise RuntimeError(f"{what}: unsupported volume {tuple(volume.shape)}: vertex ids need 12 * NZ * NY * NX < 2^31")
+    work = torch.empty((wbytes // 8,), dtype=torch.int64, device=dev)
+    counts = torch.empty((b, 2), dtype=torch.int32, device=dev)
+    vertex = torch.empty((b, mv, 4), dtype=F32, device=dev) if mv else None
+    normal = torch.empty((b, mv, 4), dtype=F32, device=dev) if mv and normals else None
+    tris = torch.empty((b, mt, 3), dtype=torch.int32, device=dev) if mt and triangles else None
+    N.call("mi_tsdf_surface", ptr, *dims, *o, float(voxel_size), float(min_weight), mv, mt if tris is not None else 0,
+           vertex.data_ptr() if vertex is not None else None, normal.data_ptr() if normal is not None else None,
+           tris.data_ptr() if tris is not None else None, counts.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    return vertex, normal, tris, counts
+
+
+def tsdf_surface(volume: torch.Tensor, origin, voxel_size: float, max_vertices: int, max_triangles: int, min_weight: float = 1.0,
+                 normals: bool = True, triangles: bool = True):
+    """`mi_tsdf_surface`: the zero level set of volume (B, NZ, NY, NX, 2) by marching tetrahedra -> (vertex (B, max_vertices, 4)
+    float32 in the world frame, normal likewise or None, triangles (B, max_triangles, 3) int32 or None, counts (B, 2) int32 =
+    the true (vertices, triangles) of every volume, which may exceed the capacities).  Rows past the counts are zeros and
+    (-1, -1, -1).  triangles=False forms no triangle (a point cloud); the counts still hold both totals.  No synchronisation."""
+    vertex, normal, tris, counts = _tsdf_surface_call(volume, origin, voxel_size, min_weight, max_vertices, max_triangles, normals,
+                                                      triangles, "tsdf_surface")
+    b, dev = int(volume.shape[0]), volume.device
+    if vertex is None:                                           # a capacity of 0: empty arrays, nothing to write
+        vertex = torch.empty((b, 0, 4), dtype=F32, device=dev)
+        normal = torch.empty((b, 0, 4), dtype=F32, device=dev) if normals else None
+    if tris is None and triangles:
+        tris = torch.empty((b, 0, 3), dtype=torch.int32, device=dev)
+    return vertex, normal, tris, counts
+
+
+def tsdf_surface_counts(volume: torch.Tensor, min_weight: float = 1.0) -> torch.Tensor:
+    """The sizing pass of `mi_tsdf_surface`: (B, 2) int32 on the device, the (vertices, triangles) a full call would produce.
+    The counts depend on neither the origin nor the voxel size."""
+    return _tsdf_surface_call(volume, (0.0, 0.0, 0.0), 1.0, min_weight, 0, 0, False, False, "tsdf_surface_counts")[3]
+
+
 # ---- K16 frame ingest (sample/visual_odometry.py:65-92 load_image_from_array) ------------------------------------------
 
 INGEST_MAX_DIM = 16384             # include/mi355x_match.h MI_INGEST_MAX_DIM

@@ -1,8 +1,8 @@
 """TsdfVolume -- the fused model of an RGB-D odometry: depth frames integrated into a truncated signed distance volume, the
 volume raycast at a predicted pose into a synthetic surfel map, and that map handed to the point-to-plane ICP of
 DenseRgbdRefiner in place of a single noisy depth frame (frame-to-model tracking).  K19: `mi_tsdf_reset`,
-`mi_tsdf_integrate`, `mi_tsdf_raycast`, `mi_pose_compose`; the algorithm is stated in include/mi355x_match.h.  The reference
-has no counterpart."""
+`mi_tsdf_integrate`, `mi_tsdf_raycast`, `mi_pose_compose`; K20 takes the fused surface out as a triangle mesh or a point cloud:
+`mi_tsdf_surface`.  The algorithms are stated in include/mi355x_match.h.  The reference has no counterpart."""
 import math
 
 import torch
@@ -30,9 +30,15 @@ class TsdfVolume(nn.Module):
                                          pose before the failed step -- where the system was degenerate (an empty volume
                                          returns the prediction)
     forward(depth, R_pred, t_pred)       track, then integrate at the tracked pose where ok; the same outputs
+    extract_surface(max_vertices=None, max_triangles=None, min_weight=1.0)
+                                         -> (vertices, normals, triangles, counts): the fused surface as an indexed triangle
+                                         mesh in the world frame (K20, marching tetrahedra)
+    extract_points(max_points=None, min_weight=1.0)
+                                         -> (points, normals, counts): the mesh's vertices alone, a point cloud
 
     truncation defaults to 4 voxels; max_weight caps the running mean's memory; the raycast samples every step_fraction (at
-    most 1) of the truncation.  Everything runs on the current stream without a synchronisation and is capturable."""
+    most 1) of the truncation.  Everything runs on the current stream without a synchronisation and is capturable, except an
+    extraction without capacities, which reads the counts back once to size its outputs."""
 
     def __init__(self, K: torch.Tensor, dims, voxel_size: float, origin, truncation: float | None = None, max_weight: float = 64.0,
                  step_fraction: float = 0.5, depth_scale: float = 1.0, min_depth: float = 0.1, max_depth: float = 10.0,
@@ -155,6 +161,40 @@ class TsdfVolume(nn.Module):
                                                             self.min_correspondences)
         r, t = ops.pose_compose(r_i, t_i, r_pred, t_pred)
         return r, t, info, rmse, count, ok
+
+    def _capacities(self, max_vertices, max_triangles, min_weight: float, triangles: bool):
+        """the capacities as given, or -- where one is None -- the exact totals from the sizing pass: ONE host round trip.  The
+        sizing pass allocates its own workspace (a byte per voxel), as the extraction after it does again."""
+        # extract_points passes triangles=False and max_triangles=None: no triangle capacity is wanted, so 0 without a sizing pass
+        if max_vertices is not None and (max_triangles is not None or not triangles):
+            return int(max_vertices), int(max_triangles or 0)
+        counts = ops.tsdf_surface_counts(self.volume, min_weight).max(dim=0).values.tolist()      # synchronises
+        return (counts[0] if max_vertices is None else int(max_vertices),
+                counts[1] if max_triangles is None else int(max_triangles))
+
+    @torch.no_grad()
+    def extract_surface(self, max_vertices: int | None = None, max_triangles: int | None = None, min_weight: float = 1.0):
+        """K20, `mi_tsdf_surface`: the fused surface as an indexed triangle mesh -> (vertices (B, MV, 4) float32 (x, y, z, 1) in
+        the world frame, normals (B, MV, 4) (unit, towards free space, 1; zeros where the gradient is not available), triangles
+        (B, MT, 3) int32 vertex ids, counts (B, 2) int32 = the true (vertices, triangles) of every volume).  Volume b's mesh is
+        the first counts[b, 0] vertices and counts[b, 1] triangles; the rows after them are zeros and (-1, -1, -1).  A voxel
+        counts as observed from weight >= min_weight.
+        With both capacities given it runs on the current stream without a synchronisation and is capturable; counts above a
+        capacity mean an incomplete mesh.  With a capacity None it first runs the sizing pass and reads the counts back -- one
+        host synchronisation -- so that the arrays hold exactly the largest volume's mesh."""
+        self._on_gpu(self.volume, "the volume")
+        mv, mt = self._capacities(max_vertices, max_triangles, min_weight, True)
+        return ops.tsdf_surface(self.volume, self.origin, self.voxel_size, mv, mt, min_weight)
+
+    @torch.no_grad()
+    def extract_points(self, max_points: int | None = None, min_weight: float = 1.0):
+        """The vertices of `extract_surface` on their own -> (points (B, MP, 4), normals (B, MP, 4), counts (B, 2)); no triangle
+        is formed.  max_points None: the sizing pass and one host synchronisation, as above.  The cloud of volume b is
+        points[b, :counts[b, 0], :3]: `ops.voxel_downsample_batch` (VoxelDownsampling, K12) takes the list of these slices."""
+        self._on_gpu(self.volume, "the volume")
+        mp, _ = self._capacities(max_points, None, min_weight, False)
+        points, normals, _, counts = ops.tsdf_surface(self.volume, self.origin, self.voxel_size, mp, 0, min_weight, triangles=False)
+        return points, normals, counts
 
     @torch.no_grad()
     def forward(self, depth: torch.Tensor, R_pred: torch.Tensor, t_pred: torch.Tensor):
