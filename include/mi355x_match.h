@@ -988,6 +988,71 @@ MI_API int mi_icp_refine(const float *vertex1, const float *normal1, const float
                          int32_t *count, int32_t *steps, uint8_t *ok, void *workspace, size_t workspace_bytes,
                          mi_stream_t stream);
 
+/* ---- direct RGB-D refinement (K21): a photometric term joined to K18's point-to-plane system --------------------------------
+ * K18 uses depth alone, so a scene of one plane (a wall, a floor, a table top) leaves three directions free and freezes
+ * the pair.  This section adds the intensity residual of direct RGB-D odometry, taken on the gray model frames of
+ * mi_ingest_frames: texture pins what geometry leaves free.  The term is a WEIGHTED OPTION: texture seen past an occlusion
+ * edge biases it, so on a scene that K18 already constrains well the joint result can be further from the truth than
+ * K18's.  Four entries, batched over pairs, under the contract of the K15 / K17 / K18 sections: pure functions of their
+ * arguments, no allocation, no synchronisation, no memset, one stream, no atomics, every sum in a fixed order, capturable
+ * into a hipGraph; outputs and workspace may hold anything on entry and every output element is written; MI_E_* before any
+ * launch.  A pair's result is the same bits alone or inside a batch, and from run to run.  Per-pixel arithmetic is float32
+ * with nothing fused, the joint system, the solve and the pose float64.  K18's entries, kernels and bits are untouched.
+ *
+ * Intensity maps (mi_intensity_maps), per frame: one record of 4 float32 per pixel, (batch, h, w, 4): (I, gx, gy, f) with
+ *   I the gray value as float32, gx = 0.5f * (I(x+1, y) - I(x-1, y)), gy = 0.5f * (I(x, y+1) - I(x, y-1)); valid (f = 1) for an
+ *   interior pixel (1 <= x <= w - 2, 1 <= y <= h - 2) whose five values are finite, else zeros.  Border pixels have none.
+ *
+ * One photometric linearisation at pose (R, t), float32, and source stride s: over the pixels of frame 1 on the stride's
+ *   grid whose VERTEX record and intensity record are valid (no normal is needed), with v1 and I1 of frame 1:
+ *     q, u, v, px, py exactly as in K18;  x0 = floorf(u), y0 = floorf(v), a = u - x0, b = v - y0
+ *   rejected when q_2 <= 0, the footprint (x0 .. x0 + 1, y0 .. y0 + 1) is not inside the frame, one of its four intensity
+ *   records in frame 2 is invalid, frame 2's vertex record at the NEAREST pixel (px, py) is invalid, or |q_2 - v2_2| >
+ *   distance_threshold (the occlusion check).  I2, gx, gy are the bilinear blends of the four records c00 c01 (row y0) and
+ *   c10 c11 (row y0 + 1), each as top = c00 + a * (c01 - c00), bot = c10 + a * (c11 - c10), top + b * (bot - top).
+ *   r = I2 - I1; rejected when |r| > intensity_threshold.  For a survivor
+ *     c = ((fx * gx) / q_2, (fy * gy) / q_2, -((c_0 * q_0 + c_1 * q_1) / q_2))   and   J = [q x c, c]
+ *   (the cross product's components as q_i c_j - q_j c_i).  29 sums in K18's layout: the 21 entries of the upper triangle of
+ *   sum J^T J in row-major order, the 6 of sum J r, sum r^2, the count.  The order of the sums is K18's, word for word: the
+ *   same slabs of 2048 sampled pixels, lanes, wave tree and float64 folding.
+ *
+ * Joint step.  With w = photo_weight (the depth's unit per gray level) as float64 and the geometric sums g of K18's
+ *   linearisation and the photometric sums p at the same pose and stride: s_k = g_k + (w * w) * p_k for the 21 + 6 + 1
+ *   entries of A, b and sum r^2, and the count count_g + count_p.  K18's step is applied to s: the same solve, the same
+ *   rules of degeneracy (the joint count below min_correspondences, a pivot, anything not finite), the same update,
+ *   freezing and schedule.  The final linearisation reports both counts, rmse = sqrt(g_27 / count_g) and rmse_photo =
+ *   sqrt(p_27 / count_p) (0 for a count of 0) and information = the joint A; ok = 1 when no solve failed and count_g +
+ *   count_p is at least min_correspondences.  photo_weight == 0 launches nothing photometric, s = g, count_photo = 0,
+ *   rmse_photo = 0: every other output has mi_icp_refine's bits. */
+
+/* gray (batch, h, w), uint8 (gray_is_u8 = 1) or float32 (0): the two outputs of mi_ingest_frames -> intensity_out
+ * (batch, h, w, 4) float32, 16-byte aligned (MI_E_ALIGN).  Shape limits of mi_surfel_maps.  One launch, one thread per pixel. */
+MI_API int mi_intensity_maps(const void *gray, int gray_is_u8, int batch, int h, int w, float *intensity_out, mi_stream_t stream);
+
+/* bytes of workspace for mi_photo_linearise / mi_rgbd_refine (0 for an unsupported shape): mi_icp_workspace_bytes' content
+ * with a second array of slab records. */
+MI_API size_t mi_rgbd_workspace_bytes(int batch, int h, int w);
+
+/* One photometric linearisation: the vertex and intensity maps of both frames, r (batch, 3, 3) and t (batch, 3) float32 per
+ * pair -> sums (batch, 29) float64 in the order above.  The checks of mi_icp_linearise (no angle), and intensity_threshold
+ * <= 0 or not finite: MI_E_PARAM.  Two launches. */
+MI_API int mi_photo_linearise(const float *vertex1, const float *intensity1, const float *vertex2, const float *intensity2,
+                              const float *r, const float *t, int batch, int h, int w, float fx, float fy, float cx, float cy,
+                              int stride, float distance_threshold, float intensity_threshold, double *sums, void *workspace,
+                              size_t workspace_bytes, mi_stream_t stream);
+
+/* The joint refinement from r0, t0: mi_icp_refine's arguments, the two intensity maps, photo_weight and
+ * intensity_threshold; mi_icp_refine's outputs (count, rmse: the geometric term's) and rmse_photo (batch) float32,
+ * count_photo (batch) int32.  The checks of mi_icp_refine, and photo_weight < 0 or not finite, intensity_threshold <= 0 or
+ * not finite: MI_E_PARAM.  1 + 3 (iterations + 1) launches (2 (iterations + 1) for photo_weight == 0), enqueued back to back. */
+MI_API int mi_rgbd_refine(const float *vertex1, const float *normal1, const float *intensity1, const float *vertex2,
+                          const float *normal2, const float *intensity2, const float *r0, const float *t0, int batch, int h,
+                          int w, float fx, float fy, float cx, float cy, const int32_t *strides, const int32_t *iterations,
+                          int stages, float distance_threshold, float angle_threshold, float photo_weight,
+                          float intensity_threshold, int min_correspondences, float *r, float *t, float *information,
+                          float *rmse, int32_t *count, float *rmse_photo, int32_t *count_photo, int32_t *steps, uint8_t *ok,
+                          void *workspace, size_t workspace_bytes, mi_stream_t stream);
+
 /* ---- TSDF fusion (K19): depth frames -> a fused signed distance volume -> a synthetic surfel map for K18 -----------------------
  * K17 and K18 estimate each pose against ONE noisy depth frame.  This section accumulates depth frames into a truncated
  * signed distance volume and raycasts the volume, at a predicted pose, into a surfel map in exactly mi_surfel_maps' record

@@ -19,15 +19,11 @@
 // Built with -ffp-contract=off; every sum has a fixed order: bitwise reproducible, alone or in a batch.
 #include "common.h"
 #include "icp_math.h"
+#include "icp_shared.h"
 
 #include <math.h>
 
 namespace {
-
-constexpr int ICP_THREADS = 256;
-constexpr int ICP_PER_LANE = 8;
-constexpr int ICP_SLAB = ICP_THREADS * ICP_PER_LANE;       // sampled pixels per workgroup
-constexpr int ICP_REC = 32;                                // doubles per slab record (29 used)
 
 // ---- K18m ------------------------------------------------------------------------------------------------------------------
 template <typename D>
@@ -71,10 +67,6 @@ __global__ __launch_bounds__(64) void icp_init_kernel(const float *__restrict__ 
 }
 
 // ---- K18r ------------------------------------------------------------------------------------------------------------------
-struct IcpCam {
-  float fx, fy, cx, cy;
-};
-
 // The pose comes from r / t (float32, mi_icp_linearise) or, when pose64 is given, from the workspace's float64 pose
 // rounded to float32 (mi_icp_refine).
 __global__ __launch_bounds__(ICP_THREADS) void icp_reduce_kernel(const float4 *__restrict__ vertex1, const float4 *__restrict__ normal1,
@@ -213,25 +205,6 @@ __global__ __launch_bounds__(64) void icp_solve_kernel(const double *__restrict_
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-int icp_shape_status(int batch, int h, int w) {
-  if (batch < 1 || h < 3 || w < 3) return MI_E_SHAPE;
-  if (batch > 65535) return MI_E_PARAM;
-  if ((long long)batch * h * w >= 0x80000000LL) return MI_E_SHAPE;
-  return MI_OK;
-}
-bool icp_stride_ok(int s) { return s == 1 || s == 2 || s == 4 || s == 8; }
-bool icp_positive(float v) { return v > 0.0f && v < INFINITY; }
-int icp_gate_status(float fx, float fy, float cx, float cy, float distance_threshold, float angle_threshold) {
-  if (!icp_positive(fx) || !icp_positive(fy) || !(fabsf(cx) < INFINITY) || !(fabsf(cy) < INFINITY) ||
-      !icp_positive(distance_threshold) || !(angle_threshold > 0.0f) || !(angle_threshold <= 3.14159274f))
-    return MI_E_PARAM;
-  return MI_OK;
-}
-int icp_samples(int h, int w, int s, int *ws) {
-  *ws = (w + s - 1) / s;
-  return ((h + s - 1) / s) * *ws;
-}
-
 struct IcpWork {
   double *pose, *slabs;
   int *state, *steps;
@@ -268,6 +241,22 @@ int icp_linearise_launch(const float4 *v1, const float4 *n1, const float4 *v2, c
 }
 
 }  // namespace
+
+// ---- shared with K21 (photo.hip; declared in icp_shared.h) -------------------------------------------------------------------
+int icp_init_launch(const float *r0, const float *t0, int batch, double *pose, int *state, int *steps, hipStream_t s) {
+  hipLaunchKernelGGL(icp_init_kernel, dim3((unsigned)ceil_div(batch, 64)), dim3(64), 0, s, r0, t0, batch, pose, state, steps);
+  return mi_launch_status();
+}
+
+int icp_reduce_launch(const float4 *v1, const float4 *n1, const float4 *v2, const float4 *n2, const float *r, const float *t,
+                      const double *pose64, const int *state, int batch, int h, int w, int stride, int max_slabs, IcpCam cam,
+                      float thr2, float cos_thr, double *slabs, hipStream_t s) {
+  int ws;
+  const int samples = icp_samples(h, w, stride, &ws), nslabs = ceil_div(samples, ICP_SLAB);
+  hipLaunchKernelGGL(icp_reduce_kernel, dim3((unsigned)nslabs, (unsigned)batch), dim3(ICP_THREADS), 0, s, v1, n1, v2, n2, r, t,
+                     pose64, state, h, w, stride, ws, samples, max_slabs, cam, thr2, cos_thr, slabs);
+  return mi_launch_status();
+}
 
 extern "C" int mi_surfel_maps(const void *depth, int depth_is_u16, int batch, int h, int w, const float *k_inv, float z_scale,
                               float min_depth, float max_depth, float normal_max_jump, float *vertex_out, float *normal_out,

@@ -1396,6 +1396,100 @@ def icp_refine(maps1, maps2, r0: torch.Tensor, t0: torch.Tensor, camera, schedul
     return r, t, info, rmse, count, steps, ok.view(torch.bool)
 
 
+# ---- K21 direct RGB-D refinement (include/mi355x_match.h, "direct RGB-D refinement") -----------------------------------------
+
+def intensity_maps(gray: torch.Tensor):
+    """`mi_intensity_maps`: gray frames (B, H, W), uint8 or float32 (`ingest_frames`' outputs) -> (B, H, W, 4) float32: the
+    gray value, its central differences in x and y and 1 / 0 for valid / invalid (interior pixels with finite values;
+    invalid records are zero).  Current stream, no synchronisation, capturable."""
+    if not gray.is_cuda:
+        raise RuntimeError(f"intensity_maps: gray must live on the GPU (got device {gray.device}); this package has no CPU path")
+    if gray.dtype not in (F32, U8):
+        raise RuntimeError(f"intensity_maps: gray must be float32 or uint8, got {gray.dtype}")
+    if gray.dim() != 3 or gray.shape[1] < 3 or gray.shape[2] < 3 or gray.shape[0] < 1:
+        raise RuntimeError(f"intensity_maps: gray must be (B, H, W) with H, W >= 3, got {tuple(gray.shape)}")
+    g = gray.contiguous()
+    b, h, w = (int(x) for x in g.shape)
+    out = torch.empty((b, h, w, 4), dtype=F32, device=g.device)
+    N.call("mi_intensity_maps", g.data_ptr(), int(g.dtype == U8), b, h, w, out.data_ptr(), N.stream_ptr())
+    return out
+
+
+def _rgbd_inputs(named_maps, r: torch.Tensor, t: torch.Tensor, camera, what: str):
+    first = named_maps[0][1]
+    if not first.is_cuda:
+        raise RuntimeError(f"{what}: the maps must live on the GPU (got device {first.device}); this package has no CPU path")
+    if first.dim() != 4 or first.shape[-1] != 4 or any(x.shape != first.shape or x.dtype != F32 for _, x in named_maps):
+        raise RuntimeError(f"{what}: the maps must be float32 (B, H, W, 4) of one shape, got "
+                           + ", ".join(f"{n} {x.dtype} {tuple(x.shape)}" for n, x in named_maps))
+    b, h, w = int(first.shape[0]), int(first.shape[1]), int(first.shape[2])
+    rr, tt = r.float().contiguous(), t.float().contiguous()
+    if tuple(rr.shape) != (b, 3, 3) or tuple(tt.shape) != (b, 3):
+        raise RuntimeError(f"{what}: the pose must be ({b}, 3, 3) and ({b}, 3), got {tuple(r.shape)} and {tuple(t.shape)}")
+    keep = tuple(x.contiguous() for _, x in named_maps)
+    maps = tuple(N.dev(x, F32, n) for (n, _), x in zip(named_maps, keep))
+    cam = tuple(float(x) for x in camera)
+    if len(cam) != 4:
+        raise RuntimeError(f"{what}: camera must be (fx, fy, cx, cy), got {camera!r}")
+    wbytes = int(N.load().mi_rgbd_workspace_bytes(b, h, w))
+    if wbytes == 0:
+        raise RuntimeError(f"{what}: unsupported request (batch {b}, {h} x {w})")
+    work = torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=first.device)
+    return keep, maps, rr, tt, cam, b, h, w, work, wbytes
+
+
+def photo_linearise(vertex1: torch.Tensor, intensity1: torch.Tensor, vertex2: torch.Tensor, intensity2: torch.Tensor,
+                    r: torch.Tensor, t: torch.Tensor, camera, stride: int = 1, distance_threshold: float = 0.1,
+                    intensity_threshold: float = 30.0):
+    """`mi_photo_linearise`: one photometric linearisation of frame 1's pixels (its `surfel_maps` vertex map and
+    `intensity_maps` map) against frame 2's at the pose r (B, 3, 3), t (B, 3), camera = (fx, fy, cx, cy), over every
+    stride-th source pixel -> sums (B, 29) float64 in `icp_linearise`'s layout.  distance_threshold is the occlusion gate
+    on depth, intensity_threshold the gate on the residual in gray levels."""
+    named = [("vertex1", vertex1), ("intensity1", intensity1), ("vertex2", vertex2), ("intensity2", intensity2)]
+    keep, maps, rr, tt, cam, b, h, w, work, wbytes = _rgbd_inputs(named, r, t, camera, "photo_linearise")
+    sums = torch.empty((b, ICP_SUMS), dtype=torch.float64, device=rr.device)
+    N.call("mi_photo_linearise", *maps, N.dev(rr, F32, "r"), N.dev(tt, F32, "t"), b, h, w, *cam, int(stride),
+           float(distance_threshold), float(intensity_threshold), sums.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    return sums
+
+
+def rgbd_refine(maps1, maps2, r0: torch.Tensor, t0: torch.Tensor, camera, schedule=((4, 4), (2, 4), (1, 6)),
+                distance_threshold: float = 0.1, angle_threshold: float = 0.5235987755982988, photo_weight: float = 0.003,
+                intensity_threshold: float = 30.0, min_correspondences: int = 64):
+    """`mi_rgbd_refine`: `icp_refine` with a photometric term joined to every step.  maps1, maps2 = (vertex, normal,
+    intensity) of `surfel_maps` and `intensity_maps` -> (R (B, 3, 3), t (B, 3), information (B, 6, 6) float32 of the joint
+    system, rmse (B,) float32 and count (B,) int32 of the geometric term, rmse_photo (B,) float32 and count_photo (B,) int32
+    of the photometric term, steps (B,) int32, ok (B,) bool).  photo_weight is the depth's unit per gray level; 0 gives
+    `icp_refine`'s bits."""
+    import ctypes
+    names = ("vertex", "normal", "intensity")
+    if len(maps1) != 3 or len(maps2) != 3:
+        raise RuntimeError("rgbd_refine: maps1 and maps2 must each be (vertex, normal, intensity)")
+    named = [(f"{n}{i}", x) for i, maps in ((1, maps1), (2, maps2)) for n, x in zip(names, maps)]
+    keep, maps, rr, tt, cam, b, h, w, work, wbytes = _rgbd_inputs(named, r0, t0, camera, "rgbd_refine")
+    sched = [(int(s), int(i)) for s, i in schedule]
+    if not 1 <= len(sched) <= ICP_MAX_STAGES:
+        raise RuntimeError(f"rgbd_refine: the schedule needs 1 .. {ICP_MAX_STAGES} stages, got {len(sched)}")
+    strides = (ctypes.c_int32 * len(sched))(*[s for s, _ in sched])
+    iters = (ctypes.c_int32 * len(sched))(*[i for _, i in sched])
+    dev = rr.device
+    r = torch.empty((b, 3, 3), dtype=F32, device=dev)
+    t = torch.empty((b, 3), dtype=F32, device=dev)
+    info = torch.empty((b, 6, 6), dtype=F32, device=dev)
+    rmse = torch.empty((b,), dtype=F32, device=dev)
+    count = torch.empty((b,), dtype=I32, device=dev)
+    rmse_photo = torch.empty((b,), dtype=F32, device=dev)
+    count_photo = torch.empty((b,), dtype=I32, device=dev)
+    steps = torch.empty((b,), dtype=I32, device=dev)
+    ok = torch.empty((b,), dtype=U8, device=dev)
+    N.call("mi_rgbd_refine", *maps, N.dev(rr, F32, "r0"), N.dev(tt, F32, "t0"), b, h, w, *cam,
+           ctypes.cast(strides, ctypes.c_void_p), ctypes.cast(iters, ctypes.c_void_p), len(sched), float(distance_threshold),
+           float(angle_threshold), float(photo_weight), float(intensity_threshold), int(min_correspondences), r.data_ptr(),
+           t.data_ptr(), info.data_ptr(), rmse.data_ptr(), count.data_ptr(), rmse_photo.data_ptr(), count_photo.data_ptr(),
+           steps.data_ptr(), ok.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    return r, t, info, rmse, count, rmse_photo, count_photo, steps, ok.view(torch.bool)
+
+
 # ---- K19 TSDF fusion (include/mi355x_match.h, "TSDF fusion") ------------------------------------------------------------------
 
 def _tsdf_volume(volume: torch.Tensor, what: str):

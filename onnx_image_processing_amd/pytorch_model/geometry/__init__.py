@@ -1,8 +1,9 @@
 from .dense_rgbd import DenseRgbdRefiner
+from .direct_rgbd import DirectRgbdRefiner
 from .essential_matrix_estimator import EssentialMatrixEstimator
 from .relative_pose import RelativePoseEstimator, triangulate_points
 from .rgbd_pose import RgbdPoseEstimator
 from .tsdf_volume import TsdfVolume
 
-__all__ = ["DenseRgbdRefiner", "EssentialMatrixEstimator", "RelativePoseEstimator", "RgbdPoseEstimator", "TsdfVolume",
+__all__ = ["DenseRgbdRefiner", "DirectRgbdRefiner", "EssentialMatrixEstimator", "RelativePoseEstimator", "RgbdPoseEstimator", "TsdfVolume",
            "triangulate_points"]
