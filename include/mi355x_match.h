@@ -1184,6 +1184,62 @@ MI_API int mi_tsdf_surface(const float *volume, int batch, int nz, int ny, int n
                            float *normal_out, int32_t *triangle_out, int32_t *counts_out, void *workspace, size_t workspace_bytes,
                            mi_stream_t stream);
 
+/* ---- TSDF intensity (K22): gray values in the fused model -> direct frame-to-model tracking, gray per mesh vertex -----------------
+ * K19's volume holds (tsdf, weight) alone, so its raycast gives K18 a surfel map and nothing photometric: on a textured wall,
+ * floor or table top model tracking freezes, as K18 does between two frames.  This section keeps a SECOND volume of gray
+ * values beside K19's, fuses it from gray frames in the same pass as the depth, and gathers it at given points: at the
+ * raycast's vertex map it yields a record map in mi_intensity_maps' layout, (I, 0, 0, f).  mi_photo_linearise /
+ * mi_rgbd_refine read only I and f of FRAME 1's intensity record (the gradients are frame 2's, the live frame), so that map
+ * is a legitimate `intensity1` and K21 is unchanged.  At the world vertices of mi_tsdf_surface it yields gray per vertex.
+ * The reference has no counterpart.  Three entries, batched over volumes, under the contract of the K19 section: no
+ * allocation, no synchronisation, no memset, no atomics, one stream, capturable; every output element is written; MI_E_*
+ * before any launch; a volume's result is the same bits alone or inside a batch, and from run to run.  Per-voxel and
+ * per-sample arithmetic is float32 with nothing fused.  K19's entries, kernels and bits are untouched.
+ *
+ * Intensity volume.  (batch, nz, ny, nx) records of two float32 (gray, gweight), 8 bytes, x fastest: K19's layout, alignment
+ *   (16 bytes, MI_E_ALIGN), origin, voxel_size and shape checks.  An empty record is (0, 0).
+ *
+ * Integration, per voxel, for the frames in order (a frame whose `active` byte is 0 is left out): K19's update of (tsdf, weight),
+ *   step for step, with its q, (px, py), d, Z and sdf = Z - q_2.  Where that update HAPPENED (no skip), and sdf <= truncation,
+ *   and g = gray[py][px] (the depth sample's own pixel; uint8 converted to float32) is finite:
+ *     gray <- (gray * gweight + g) / (gweight + 1);   gweight <- fminf(gweight + 1, max_weight)
+ *   So only voxels inside the band |sdf| <= truncation around a seen surface ever hold a gray value.  The written `volume` has
+ *   mi_tsdf_integrate's bits.  One pass over both volumes however many frames; frames given in one call and the same frames
+ *   given one per call give the same bits in both volumes.
+ *
+ * Sampling, per point record (x, y, z, f) with f != 0 and x, y, z finite (any other point is invalid):
+ *   with a pose (world to camera, the point is in the camera's frame): c = (x - t_0, y - t_1, z - t_2),
+ *     X_w,j = (R_0j c_0 + R_1j c_1) + R_2j c_2: the raycast's operations, so for its vertex (xn s*, yn s*, s*) the grid coordinate
+ *     below has the raycast's own bits.  Without a pose the point is X_w.
+ *   g_a = (X_w,a - origin_a) / voxel_size - 0.5f per axis; invalid unless 0 <= g_a <= n_a - 1 on every axis (NaN fails).
+ *   b_a = fminf(floorf(g_a), n_a - 2), a_a = g_a - b_a: the last layer of voxels is reached with a = 1.
+ *   Over the corners m = 0..7 of cell b IN THAT ORDER (corner m is voxel b + (m & 1, (m >> 1) & 1, (m >> 2) & 1)), with
+ *     w_m = (wx * wy) * wz, wx = a_x where m & 1 else 1.0f - a_x, and likewise wy, wz with bits 1 and 2:
+ *     num and den start at 0 and, for every corner with gweight_m > 0, num <- num + w_m * gray_m, den <- den + w_m.
+ *   Valid iff den > 0: I = num / den, the record (I, 0, 0, 1); else zeros.  This is the weight-normalised blend over the OBSERVED
+ *   corners: a vertex at the rim of the observed band still gets the gray of what was seen. */
+
+/* (0, 0) into every record of intensity_volume (batch, nz, ny, nx, 2).  One launch. */
+MI_API int mi_tsdf_gray_reset(float *intensity_volume, int batch, int nz, int ny, int nx, mi_stream_t stream);
+
+/* mi_tsdf_integrate with a gray frame beside every depth frame: gray (batch, frames, h, w), float32 (gray_is_u8 = 0) or uint8
+ * (1), in the depth's camera.  mi_tsdf_integrate's checks; NULL intensity_volume or gray: MI_E_NULL; intensity_volume not
+ * 16-byte aligned: MI_E_ALIGN.  One launch, a wave per x-row; a voxel's intensity record is read and written only if a frame
+ * updates it. */
+MI_API int mi_tsdf_integrate_gray(float *volume, float *intensity_volume, int batch, int nz, int ny, int nx, float origin_x,
+                                  float origin_y, float origin_z, float voxel_size, float truncation, float max_weight,
+                                  const void *depth, int depth_is_u16, const void *gray, int gray_is_u8, int frames, int h, int w,
+                                  float fx, float fy, float cx, float cy, float z_scale, float min_depth, float max_depth,
+                                  const float *r, const float *t, const uint8_t *active, mi_stream_t stream);
+
+/* intensity_volume + points (batch, n, 4) float32 + an optional pose per volume, r (batch, 3, 3) and t (batch, 3), both given
+ * or both NULL (one without the other: MI_E_NULL) -> intensity_out (batch, n, 4) float32.  The volume's checks (no truncation);
+ * n < 1, batch * n >= 2^31: MI_E_SHAPE; intensity_volume, points and intensity_out 16-byte aligned (MI_E_ALIGN).  One launch, one
+ * thread per point. */
+MI_API int mi_tsdf_sample_gray(const float *intensity_volume, int batch, int nz, int ny, int nx, float origin_x, float origin_y,
+                               float origin_z, float voxel_size, const float *points, int n, const float *r, const float *t,
+                               float *intensity_out, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

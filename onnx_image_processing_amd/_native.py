@@ -157,6 +157,12 @@ SIGNATURES = {
     "mi_tsdf_surface_workspace_bytes": [c_int, c_int, c_int, c_int],
     "mi_tsdf_surface": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p,
                         c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    "mi_tsdf_gray_reset": [c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "mi_tsdf_integrate_gray": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float,
+                               c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
+                               c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
+    "mi_tsdf_sample_gray": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_void_p, c_int, c_void_p,
+                            c_void_p, c_void_p, c_void_p],
 }
 
 

@@ -1640,6 +1640,104 @@ def tsdf_surface_counts(volume: torch.Tensor, min_weight: float = 1.0) -> torch.
     return _tsdf_surface_call(volume, (0.0, 0.0, 0.0), 1.0, min_weight, 0, 0, False, False, "tsdf_surface_counts")[3]
 
 
+# ---- K22 TSDF intensity (include/mi355x_match.h, "TSDF intensity") ---------------------------------------------------------------
+
+def _tsdf_intensity(intensity: torch.Tensor, dims, what: str) -> int:
+    if not intensity.is_cuda:
+        raise RuntimeError(f"{what}: the intensity volume must live on the GPU (got device {intensity.device}); this package has "
+                           f"no CPU path")
+    if intensity.dtype != F32 or tuple(intensity.shape) != (*dims, 2):
+        raise RuntimeError(f"{what}: the intensity volume must be float32 {(*dims, 2)}, the volume's shape, got {intensity.dtype} "
+                           f"{tuple(intensity.shape)}")
+    return N.dev(intensity, F32, "intensity volume")
+
+
+def tsdf_gray_reset(intensity: torch.Tensor) -> torch.Tensor:
+    """`mi_tsdf_gray_reset`: (gray, gweight) = (0, 0) into every record of intensity (B, NZ, NY, NX, 2) float32, in place."""
+    ptr, dims = _tsdf_volume(intensity, "tsdf_gray_reset")
+    N.call("mi_tsdf_gray_reset", ptr, *dims, N.stream_ptr())
+    return intensity
+
+
+def tsdf_integrate_gray(volume: torch.Tensor, intensity: torch.Tensor, depth: torch.Tensor, gray: torch.Tensor, r: torch.Tensor,
+                        t: torch.Tensor, camera, origin, voxel_size: float, truncation: float, max_weight: float = 64.0,
+                        z_scale: float = 1.0, min_depth: float = 0.1, max_depth: float = 10.0,
+                        active: torch.Tensor | None = None):
+    """`mi_tsdf_integrate_gray`: `tsdf_integrate` with gray (B, F, H, W), float32 or uint8, beside depth (B, F, H, W): volume gets
+    `tsdf_integrate`'s bits and intensity (B, NZ, NY, NX, 2), records of (gray, gweight), the running mean of the gray value at
+    every voxel inside the truncation band of a seen surface, both in place in one pass -> (volume, intensity)."""
+    ptr, dims = _tsdf_volume(volume, "tsdf_integrate_gray")
+    iptr = _tsdf_intensity(intensity, dims, "tsdf_integrate_gray")
+    if not depth.is_cuda or not gray.is_cuda:
+        dev = depth.device if not depth.is_cuda else gray.device
+        raise RuntimeError(f"tsdf_integrate_gray: depth and gray must live on the GPU (got device {dev}); this package has no CPU "
+                           f"path")
+    if depth.dtype not in (F32, U16):
+        raise RuntimeError(f"tsdf_integrate_gray: depth must be float32 or uint16, got {depth.dtype}")
+    if gray.dtype not in (F32, U8):
+        raise RuntimeError(f"tsdf_integrate_gray: gray must be float32 or uint8, got {gray.dtype}")
+    b = dims[0]
+    if depth.dim() != 4 or depth.shape[0] != b or depth.shape[1] < 1 or depth.shape[2] < 3 or depth.shape[3] < 3:
+        raise RuntimeError(f"tsdf_integrate_gray: depth must be ({b}, F, H, W) with F >= 1 and H, W >= 3, got {tuple(depth.shape)}")
+    if gray.shape != depth.shape:
+        raise RuntimeError(f"tsdf_integrate_gray: gray must have depth's shape {tuple(depth.shape)}, got {tuple(gray.shape)}")
+    d, g = depth.contiguous(), gray.contiguous()
+    f, h, w = (int(x) for x in d.shape[1:])
+    rr, tt = r.float().contiguous(), t.float().contiguous()
+    if tuple(rr.shape) != (b, f, 3, 3) or tuple(tt.shape) != (b, f, 3):
+        raise RuntimeError(f"tsdf_integrate_gray: the poses must be ({b}, {f}, 3, 3) and ({b}, {f}, 3), got {tuple(r.shape)} and "
+                           f"{tuple(t.shape)}")
+    act = None
+    if active is not None:
+        if active.dtype not in (torch.bool, U8) or tuple(active.shape) != (b, f):
+            raise RuntimeError(f"tsdf_integrate_gray: active must be bool or uint8 ({b}, {f}), got {active.dtype} "
+                               f"{tuple(active.shape)}")
+        act = active.contiguous().view(U8)
+    grid = _tsdf_grid(origin, voxel_size, truncation, "tsdf_integrate_gray")
+    fx, fy, cx, cy = (float(x) for x in camera)
+    N.call("mi_tsdf_integrate_gray", ptr, iptr, *dims, *grid, float(max_weight), d.data_ptr(), int(d.dtype == U16), g.data_ptr(),
+           int(g.dtype == U8), f, h, w, fx, fy, cx, cy, float(z_scale), float(min_depth), float(max_depth), N.dev(rr, F32, "r"),
+           N.dev(tt, F32, "t"), N.dev(act, U8, "active") if act is not None else None, N.stream_ptr())
+    return volume, intensity
+
+
+def tsdf_sample_gray(intensity: torch.Tensor, points: torch.Tensor, origin, voxel_size: float, r: torch.Tensor | None = None,
+                     t: torch.Tensor | None = None) -> torch.Tensor:
+    """`mi_tsdf_sample_gray`: the intensity volume (B, NZ, NY, NX, 2) gathered at points (B, ..., 4) float32 records (x, y, z, f)
+    -> records of the same shape in `intensity_maps`' layout, (I, 0, 0, 1) or zeros: the weight-normalised trilinear blend
+    over the observed corners of the point's cell.  With a world-to-camera pose r (B, 3, 3), t (B, 3) the points are in the
+    camera's frame (a raycast's vertex map gives the model's intensity map, `rgbd_refine`'s maps1[2]); without, world points
+    (the vertices of `tsdf_surface`)."""
+    ptr, dims = _tsdf_volume(intensity, "tsdf_sample_gray")
+    b = dims[0]
+    if not points.is_cuda:
+        raise RuntimeError(f"tsdf_sample_gray: the points must live on the GPU (got device {points.device}); this package has no "
+                           f"CPU path")
+    if points.dtype != F32 or points.dim() < 3 or points.shape[0] != b or points.shape[-1] != 4:
+        raise RuntimeError(f"tsdf_sample_gray: the points must be float32 ({b}, N, 4) or ({b}, H, W, 4), got {points.dtype} "
+                           f"{tuple(points.shape)}")
+    if (r is None) != (t is None):
+        raise RuntimeError("tsdf_sample_gray: give both r and t, or neither")
+    o = tuple(float(x) for x in origin)
+    if len(o) != 3 or not voxel_size > 0:
+        raise RuntimeError(f"tsdf_sample_gray: need an origin of 3 values and voxel_size > 0, got {origin}, {voxel_size}")
+    pts = points.contiguous()
+    n = pts.numel() // (4 * b)
+    rp = tp = None
+    if r is not None:
+        rr, tt = r.float().contiguous(), t.float().contiguous()
+        if tuple(rr.shape) != (b, 3, 3) or tuple(tt.shape) != (b, 3):
+            raise RuntimeError(f"tsdf_sample_gray: the pose must be ({b}, 3, 3) and ({b}, 3), got {tuple(r.shape)} and "
+                               f"{tuple(t.shape)}")
+        rp, tp = N.dev(rr, F32, "r"), N.dev(tt, F32, "t")
+    out = torch.empty_like(pts)
+    if n == 0:                                                   # no point (a capacity of 0): nothing to write
+        return out
+    N.call("mi_tsdf_sample_gray", ptr, *dims, *o, float(voxel_size), N.dev(pts, F32, "points"), n, rp, tp, out.data_ptr(),
+           N.stream_ptr())
+    return out
+
+
 # ---- K16 frame ingest (sample/visual_odometry.py:65-92 load_image_from_array) ------------------------------------------
 
 INGEST_MAX_DIM = 16384             # include/mi355x_match.h MI_INGEST_MAX_DIM
