@@ -1240,6 +1240,113 @@ MI_API int mi_tsdf_sample_gray(const float *intensity_volume, int batch, int nz,
                                float origin_z, float voxel_size, const float *points, int n, const float *r, const float *t,
                                float *intensity_out, mi_stream_t stream);
 
+/* ---- absolute pose (K23): 3-D points + the pixels they are seen at -> the camera pose, batched P3P RANSAC ----------------------
+ * K15 estimates a motion from 2-D to 2-D matches (unit translation), K17 from 3-D to 3-D matches (depth in both frames).
+ * This section takes 3-D points on one side and pixels on the other: matches whose depth is missing in the second frame, a
+ * colour frame against the points of a TSDF volume, a new frame against triangulated landmarks.  The host call users would
+ * reach for is cv2.solvePnPRansac.  Four entries, batched over pairs, under the contract of the K15 / K17 sections: pure
+ * functions of their arguments, no allocation, no synchronisation, no memset, one stream, no atomics, every sum in a fixed
+ * order (the same inputs and seed give the same bits), capturable into a hipGraph; outputs and workspace may hold anything
+ * on entry and every output element is written; MI_E_* before any launch.
+ * Row i of pair b is pts3[b][i] <-> pts2[b][i]: pts3 (batch, n, 3) float32 points X in the model frame, pts2 (batch, n, 2)
+ * float32 NORMALISED image points (u, v) = (x, y) as mi_normalise_keypoints writes them; `valid` / `mask` (batch, n) bytes
+ * select rows (non-zero = use; valid may be NULL: every row).  Rows that are not selected are never read for their
+ * coordinates.  The pose is X_c = R X + t, the camera looking along +z.  Thresholds are in normalised units (pixels / mean
+ * focal length), as in K15.  1 <= n <= MI_PNP_MAX_N (a staged row is 20 bytes: 40 KB of rows and 4 KB of indices in LDS;
+ * the second kernel of mi_pnp_ransac adds 4 KB of flags), batch <= 65535 (MI_E_PARAM beyond; < 1: MI_E_SHAPE).
+ *
+ * Divergences from cv2.solvePnPRansac, all deliberate:
+ *   - a fixed number of hypotheses, no adaptive stop from `confidence`; the sampler is K15's stateless counter-based hash,
+ *     not cv::RNG: results do not depend on call history;
+ *   - the best hypothesis is the one of minimum truncated cost sum min(d^2, thr^2) (MSAC), not of maximum inlier count;
+ *   - the minimal solver is stated below (OpenCV's default inside RANSAC is EPnP on 5 points, or P3P/AP3P on request);
+ *   - refinement is refine_rounds rounds of a FIXED number of Gauss-Newton iterations on the inliers (local optimisation),
+ *     where OpenCV runs Levenberg-Marquardt to a tolerance on the final inlier set;
+ *   - no camera matrix and no distortion coefficients: the image points arrive normalised and undistorted.
+ *
+ * Sampling.  K15's draw(seed, b, h, s), unchanged (the counter is still 8 h + s), for the slots s = 0 .. 3, with the same
+ *   without-replacement rule over the ranks of the valid rows: four distinct ranks.  Slots 0 .. 2 are the minimal sample,
+ *   slot 3 picks among its solutions.
+ * Solve (float32; only + - * / and sqrt, every loop of a fixed length; csrc/pnp_math.h).  With X_k, (u_k, v_k), k = 0, 1, 2:
+ *   1. bearings f_k = (u, v, 1) / sqrt((u^2 + v^2) + 1); c12 = f_0 . f_1, c13 = f_0 . f_2, c23 = f_1 . f_2 (each
+ *      (x x' + y y') + z z'); a12 = |X_0 - X_1|^2, a13 = |X_0 - X_2|^2, a23 = |X_1 - X_2|^2.  The depths l_k along the
+ *      bearings satisfy l_i^2 + l_j^2 - 2 c_ij l_i l_j = a_ij, i.e. L^T M_ij L = a_ij for L = (l_1, l_2, l_3).
+ *   2. D1 = a23 M12 - a12 M23 and D2 = a23 M13 - a13 M23 give L^T D1 L = L^T D2 L = 0.  det(D1 + g D2) is a cubic in g:
+ *      c0 = det D1, c3 = det D2, c1 = sum_ij cof(D1)_ij D2_ij, c2 = sum_ij cof(D2)_ij D1_ij; divided by c3 it is
+ *      g^3 + b g^2 + c g + d.
+ *   3. One real root g by 24 Newton steps g <- g - p(g) / p'(g) (a step with p'(g) = 0 is skipped) from a start beyond the
+ *      outer stationary point: with v = sqrt(b^2 - 3 c) real, t1 = (-b - v) / 3; if p(t1) > 0 the start is
+ *      t1 - sqrt(-p(t1) / (3 t1 + b)), else with t2 = (-b + v) / 3 it is t2 + sqrt(-p(t2) / (3 t2 + b)); without stationary
+ *      points the start is the inflection -b / 3.  From there Newton's iteration is monotone.
+ *   4. D0 = D1 + g D2 is singular.  Its eigen-decomposition by K17's cyclic Jacobi (6 sweeps, pairs (0,1) (0,2) (1,2)); the
+ *      eigenvalue of smallest magnitude (the first among equals) is dropped, the other two, sigma_p > 0 > sigma_q with unit
+ *      eigenvectors e_p, e_q (no solution when their product is not negative), factor the form:
+ *      L^T D0 L = (n+ . L)(n- . L) with n+- = sqrt(sigma_p) e_p +- sqrt(-sigma_q) e_q.
+ *   5. Candidate c = 0 .. 3: the plane n = n+ for c < 2 and n- for c >= 2 gives l_1 = w0 l_2 + w1 l_3 with w0 = -n_1 / n_0,
+ *      w1 = -n_2 / n_0; substituted into a13 L^T M12 L - a12 L^T M13 L = 0 and divided by l_2^2 this is qa tau^2 + qb tau
+ *      + qc = 0 for tau = l_3 / l_2, with
+ *          qa = ((a13 - a12) w1^2 + 2 a12 c13 w1) - a12
+ *          qb = (2 a12 c13 w0 - 2 a13 c12 w1) - 2 w0 w1 (a12 - a13)
+ *          qc = ((a13 - a12) w0^2 - 2 a13 c12 w0) + a13;
+ *      no candidate when qb^2 - 4 qa qc < 0; q = -(qb + sign(qb) sqrt(qb^2 - 4 qa qc)) / 2 (sign(0) = +1); tau = q / qa for
+ *      even c and qc / q for odd c; no candidate unless tau > 0.  l_2 = sqrt(a23 / (tau (tau - 2 c23) + 1)), l_3 = tau l_2,
+ *      l_1 = w0 l_2 + w1 l_3; no candidate unless all three are positive and finite.
+ *   6. Polish: 2 Gauss-Newton steps L <- L - J^-1 r on the three equations of step 1 (J^-1 by the adjugate; a step with
+ *      det J = 0 is skipped); afterwards the depths must again be positive and finite.
+ *   7. (R, t) of the candidate: K17's minimal solve (Horn, "metric RGB-D pose": Solve) with a_k = X_k, b_k = l_k f_k,
+ *      including its degeneracy test of both triangles and its finiteness test.
+ *   8. The candidate with the smallest d^2 (Score, below) on the slot-3 row wins; the first candidate that exists is taken
+ *      whatever its d^2, a later one replaces it only with a strictly smaller d^2.
+ * Refusals.  Fewer than 4 valid rows; the three model points, or the three bearings, degenerate under K17's test
+ *   (|e1 x e2|^2 <= 1e-6 |e1|^2 |e2|^2); no candidate; a non-finite result or cost: cost = +inf, count = 0, zeros in rt_h.
+ * Score.  For every valid row (x, y, z) = (R X) + t, each component ((R_j0 X_0 + R_j1 X_1) + R_j2 X_2) + t_j;
+ *   d^2 = (x / z - u)^2 + (y / z - v)^2; a row with z <= 0 or a non-finite d^2 has d^2 = +inf (beyond any threshold).
+ *   inlier: d^2 <= thr^2; count = number of inliers, cost = sum over the valid rows in index order of min(d^2, thr^2), float32.
+ * Refit.  Gauss-Newton on the reprojection error under K18's left perturbation (omega, tau): R <- Exp(omega) R,
+ *   t <- Exp(omega) t + tau.  A row with z > 0 gives, with xn = x / z, yn = y / z, iz = 1 / z (float32),
+ *       J_u = [-(xn yn), 1 + xn^2, -yn, iz, 0, -(xn iz)]   r_u = xn - u
+ *       J_v = [-(1 + yn^2), xn yn, xn, 0, iz, -(yn iz)]    r_v = yn - v
+ *   and rows with z <= 0 are skipped.  The 29 sums have K18's layout (21 of A = J^T J's upper triangle, 6 of b = J^T r, r^2,
+ *   and the number of ROWS used), each row adding its u line, then its v line; lanes stride over the rows and
+ *   wave_sum_dpp folds the 64 partial sums.  K18's solve of A x = -b (float64 LDL^T, pivot ratio 1e-6) and pose update
+ *   (float64 pose, rounded to float32 for the next linearisation).  3 iterations, then one more linearisation at the
+ *   result, whose A is `info`.  Any of these 4 systems unusable -- fewer than 4 rows, a pivot ratio at or below 1e-6, a
+ *   non-finite value -- stops the refit: ok = 0, (r, t) = (r0, t0), info = 0. */
+#define MI_PNP_MAX_N 2048
+
+/* H = num_hypotheses hypotheses per pair, generated and scored: rt_h (batch, H, 12) = R row-major, then t; cost (batch, H)
+ * float32, count (batch, H) int32.  H < 1: MI_E_SHAPE; H > MI_POSE_MAX_HYPOTHESES, threshold <= 0 or not finite:
+ * MI_E_PARAM.  One launch: ceil(H / 64) x batch waves, a lane per hypothesis. */
+MI_API int mi_pnp_hypotheses(const float *pts3, const float *pts2, const uint8_t *valid, int batch, int n, int num_hypotheses,
+                             float threshold, uint32_t seed, float *rt_h, float *cost, int32_t *count, mi_stream_t stream);
+
+/* The refit of the section above over the rows with mask != 0 (mask is required) from the pose r0 (batch, 3, 3), t0
+ * (batch, 3): r (batch, 3, 3), t (batch, 3), info (batch, 6, 6) float32 (the full symmetric A in (omega, tau) order),
+ * ok (batch) bytes.  One wave per pair. */
+MI_API int mi_pnp_refit(const float *pts3, const float *pts2, const uint8_t *mask, const float *r0, const float *t0, int batch,
+                        int n, float *r, float *t, float *info, uint8_t *ok, mi_stream_t stream);
+
+/* The whole estimator, K17's point for point: mi_pnp_hypotheses into the workspace, then per pair the hypothesis of minimum
+ * cost (the lowest h among equals; h = 0 when every cost is +inf) and refine_rounds rounds r = 0 .. R-1 of local
+ * optimisation: take the inliers of the best pose so far at k_r * threshold, k_r = 1 + (R - 1 - r) / 2, refit from that
+ * pose as mi_pnp_refit, score at `threshold`; the refit replaces the best pose only when its cost is strictly lower.  Inside
+ * this step a cost is held as (number of valid rows beyond the threshold, float32 sum of the inliers' d^2, summed
+ * lanes-strided) and compared as k thr^2 + s in float64, the hypothesis' own cost re-formed that way first (K17 says why).
+ * A round whose refit is not ok changes nothing.
+ * r (batch, 3, 3), t (batch, 3); inlier (batch, n) bytes: d^2 <= threshold^2 under (r, t), 0 for rows that are not valid;
+ * best_h (batch) the selected hypothesis; count (batch) = number of inlier bytes set; rmse (batch) float32 = sqrt of the
+ * mean d^2 over the inliers (normalised units); info (batch, 6, 6) float32 = A of the Refit linearisation at (r, t) over
+ * the inliers; ok (batch) bytes = 1 when a usable hypothesis exists and count >= 4.  Where ok = 0: r = identity, t = 0, no
+ * inliers, count = 0, rmse = 0, info = 0.  With refine_rounds = 0 and ok = 1, r / t / count are exactly rt_h[best_h] /
+ * count[best_h] of mi_pnp_hypotheses.
+ * 0 <= refine_rounds <= MI_POSE_MAX_REFINE_ROUNDS (MI_E_PARAM).  workspace: mi_pnp_ransac_workspace_bytes(batch, n, H) bytes
+ * (0 for an unsupported request), 16-byte aligned (MI_E_ALIGN), any content; shorter: MI_E_CAPACITY.  Two launches. */
+MI_API size_t mi_pnp_ransac_workspace_bytes(int batch, int n, int num_hypotheses);
+MI_API int mi_pnp_ransac(const float *pts3, const float *pts2, const uint8_t *valid, int batch, int n, int num_hypotheses,
+                         float threshold, int refine_rounds, uint32_t seed, float *r, float *t, uint8_t *inlier,
+                         int32_t *best_h, int32_t *count, float *rmse, float *info, uint8_t *ok, void *workspace,
+                         size_t workspace_bytes, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1301,6 +1301,86 @@ def rigid_ransac(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | N
     return r, t, inlier.view(torch.bool), best_h, count, rmse, ok.view(torch.bool)
 
 
+# ---- K23 absolute pose (include/mi355x_match.h, "absolute pose") ------------------------------------------------------------
+
+PNP_MAX_N = 2048                           # MI_PNP_MAX_N
+
+
+def _model_matches(pts3: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, what: str):
+    """(B, N, 3) model points, (B, N, 2) normalised (x, y) image points and an optional (B, N) mask, as the C ABI reads them."""
+    q3, q2 = pts3.float().contiguous(), pts2.float().contiguous()
+    if q3.dim() != 3 or q3.shape[-1] != 3 or q2.dim() != 3 or q2.shape[-1] != 2 or q3.shape[:2] != q2.shape[:2]:
+        raise RuntimeError(f"{what}: points must be (B, N, 3) and (B, N, 2), got {tuple(pts3.shape)} and {tuple(pts2.shape)}")
+    b, n = int(q3.shape[0]), int(q3.shape[1])
+    if not 1 <= n <= PNP_MAX_N:
+        raise RuntimeError(f"{what}: N = {n} rows, supported: 1 .. {PNP_MAX_N}")
+    v = _validity_bytes(valid)
+    if v is not None and tuple(v.shape) != (b, n):
+        raise RuntimeError(f"{what}: the mask must be ({b}, {n}), got {tuple(v.shape)}")
+    N.dev(q3, F32, "pts3"), N.dev(q2, F32, "pts2")
+    return q3, q2, v, b, n
+
+
+def pnp_hypotheses(pts3: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, num_hypotheses: int, threshold: float,
+                   seed: int = 0):
+    """`mi_pnp_hypotheses`: H P3P poses per pair from the counter-based sampler (three rows solve, a fourth picks the
+    candidate), each scored on every valid row by its reprojection distance in normalised units -> (rt_h (B, H, 12): R
+    row-major then t, MSAC cost (B, H) float32, inlier count (B, H) int32)."""
+    q3, q2, v, b, n = _model_matches(pts3, pts2, valid, "pnp_hypotheses")
+    h = int(num_hypotheses)
+    rt_h = torch.empty((b, h, 12), dtype=F32, device=q3.device)
+    cost = torch.empty((b, h), dtype=F32, device=q3.device)
+    count = torch.empty((b, h), dtype=I32, device=q3.device)
+    N.call("mi_pnp_hypotheses", q3.data_ptr(), q2.data_ptr(), N.dev(v, U8, "valid") if v is not None else None, b, n, h,
+           float(threshold), int(seed) & 0xFFFFFFFF, rt_h.data_ptr(), cost.data_ptr(), count.data_ptr(), N.stream_ptr())
+    return rt_h, cost, count
+
+
+def pnp_refit(pts3: torch.Tensor, pts2: torch.Tensor, mask: torch.Tensor, r0: torch.Tensor, t0: torch.Tensor):
+    """`mi_pnp_refit`: a fixed number of reprojection Gauss-Newton iterations over the masked rows from the pose r0 (B, 3, 3),
+    t0 (B, 3) -> (R (B, 3, 3), t (B, 3), info (B, 6, 6) = J^T J at the result in (omega, tau) order, ok (B,) bool); where ok
+    is False the pose is (r0, t0) and info zero."""
+    q3, q2, v, b, n = _model_matches(pts3, pts2, mask, "pnp_refit")
+    if v is None:
+        raise RuntimeError("pnp_refit needs a mask")
+    ra, ta = r0.float().contiguous(), t0.float().contiguous()
+    if tuple(ra.shape) != (b, 3, 3) or tuple(ta.shape) != (b, 3):
+        raise RuntimeError(f"pnp_refit: the starting pose must be ({b}, 3, 3) and ({b}, 3), got {tuple(r0.shape)} and {tuple(t0.shape)}")
+    r = torch.empty((b, 3, 3), dtype=F32, device=q3.device)
+    t = torch.empty((b, 3), dtype=F32, device=q3.device)
+    info = torch.empty((b, 6, 6), dtype=F32, device=q3.device)
+    ok = torch.empty((b,), dtype=U8, device=q3.device)
+    N.call("mi_pnp_refit", q3.data_ptr(), q2.data_ptr(), N.dev(v, U8, "mask"), N.dev(ra, F32, "r0"), N.dev(ta, F32, "t0"), b, n,
+           r.data_ptr(), t.data_ptr(), info.data_ptr(), ok.data_ptr(), N.stream_ptr())
+    return r, t, info, ok.view(torch.bool)
+
+
+def pnp_ransac(pts3: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, num_hypotheses: int, threshold: float,
+               refine_rounds: int = 3, seed: int = 0):
+    """`mi_pnp_ransac`: hypotheses, MSAC selection and refine_rounds rounds of refit-and-rescore in two launches ->
+    (R (B, 3, 3), t (B, 3), inlier (B, N) bool, best_h (B,) int32, count (B,) int32, rmse (B,) float32 in normalised units,
+    info (B, 6, 6) float32, ok (B,) bool)."""
+    q3, q2, v, b, n = _model_matches(pts3, pts2, valid, "pnp_ransac")
+    h = int(num_hypotheses)
+    wbytes = int(N.load().mi_pnp_ransac_workspace_bytes(b, n, h))
+    if wbytes == 0:
+        raise RuntimeError(f"pnp_ransac: unsupported request (batch {b}, N {n}, {h} hypotheses)")
+    work = torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=q3.device)
+    r = torch.empty((b, 3, 3), dtype=F32, device=q3.device)
+    t = torch.empty((b, 3), dtype=F32, device=q3.device)
+    inlier = torch.empty((b, n), dtype=U8, device=q3.device)
+    best_h = torch.empty((b,), dtype=I32, device=q3.device)
+    count = torch.empty((b,), dtype=I32, device=q3.device)
+    rmse = torch.empty((b,), dtype=F32, device=q3.device)
+    info = torch.empty((b, 6, 6), dtype=F32, device=q3.device)
+    ok = torch.empty((b,), dtype=U8, device=q3.device)
+    N.call("mi_pnp_ransac", q3.data_ptr(), q2.data_ptr(), N.dev(v, U8, "valid") if v is not None else None, b, n, h,
+           float(threshold), int(refine_rounds), int(seed) & 0xFFFFFFFF, r.data_ptr(), t.data_ptr(), inlier.data_ptr(),
+           best_h.data_ptr(), count.data_ptr(), rmse.data_ptr(), info.data_ptr(), ok.data_ptr(), work.data_ptr(), wbytes,
+           N.stream_ptr())
+    return r, t, inlier.view(torch.bool), best_h, count, rmse, info, ok.view(torch.bool)
+
+
 # ---- K18 dense RGB-D refinement (include/mi355x_match.h, "dense RGB-D refinement") ------------------------------------------
 
 ICP_MAX_STAGES = 4                         # MI_ICP_MAX_STAGES

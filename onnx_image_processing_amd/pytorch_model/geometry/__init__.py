@@ -1,3 +1,4 @@
+from .absolute_pose import AbsolutePoseEstimator
 from .dense_rgbd import DenseRgbdRefiner
 from .direct_rgbd import DirectRgbdRefiner
 from .direct_tsdf_volume import DirectTsdfVolume
@@ -6,5 +7,5 @@ from .relative_pose import RelativePoseEstimator, triangulate_points
 from .rgbd_pose import RgbdPoseEstimator
 from .tsdf_volume import TsdfVolume
 
-__all__ = ["DenseRgbdRefiner", "DirectRgbdRefiner", "DirectTsdfVolume", "EssentialMatrixEstimator", "RelativePoseEstimator", "RgbdPoseEstimator",
+__all__ = ["AbsolutePoseEstimator", "DenseRgbdRefiner", "DirectRgbdRefiner", "DirectTsdfVolume", "EssentialMatrixEstimator", "RelativePoseEstimator", "RgbdPoseEstimator",
            "TsdfVolume", "triangulate_points"]
