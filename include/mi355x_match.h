@@ -357,7 +357,13 @@ MI_API int mi_match_filter_masks(const float *p, int batch, int n, int m, int ha
  * valid (batch,max_matches) u8, match_ij (batch,max_matches,2) i32 (may be NULL).
  * n <= 4096.  Ties: first index (argmax), then (score desc, row asc) for the top-max_matches.
  * m <= 1024: one pass over p (row and column winners together; col_best, 8-byte aligned, is cleared by the call and
- * filled by 64-bit atomic maxima -- exact, so the order of arrival cannot be seen); larger m: a row and a column pass. */
+ * filled by 64-bit atomic maxima -- exact, so the order of arrival cannot be seen); larger m: a row and a column pass.
+ * Precondition: every entry of the core p[:, :n, :m] is finite and >= +0.0 (a probability; -0.0 is not).  The winners
+ * are maxima of keys built from the entries' raw bits, which order non-negative floats only.  Outside the
+ * precondition the two paths differ and neither is the reference: in the one-pass path (m <= 1024) a NaN entry never
+ * wins a row or a column (a row of nothing but NaN has no match) and a negative entry loses to every other; the row
+ * and column passes (m > 1024) compare raw bits throughout, so there a NaN or a negative entry beats every
+ * probability. */
 MI_API int mi_mnn_extract(const float *p, int batch, int n, int m, const float *kpts1, const float *kpts2,
                    int max_matches, float threshold, uint64_t *row_best, uint64_t *col_best,
                    float *mk1, float *mk2, float *scores, uint8_t *valid, int32_t *match_ij,
