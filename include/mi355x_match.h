@@ -377,7 +377,15 @@ MI_API int mi_mnn_extract(const float *p, int batch, int n, int m, const float *
  * passed to / returned by mi_sinkhorn (mi_sinkhorn_dots) with p == NULL.  m <= 1024, n <= 4096.
  * workspace: mi_mnn_duals_workspace_bytes(batch, n, m) bytes (0 = unsupported size), 8-byte aligned.
  * solver_status (mi_mnn_from_duals_dots; may be NULL): the status word of the mi_sinkhorn_dots call that produced
- * u, v.  When it is non-zero on the device every match of this call comes back with score -1 / valid 0 / match_ij -1. */
+ * u, v.  When it is non-zero on the device every match of this call comes back with score -1 / valid 0 / match_ij -1.
+ * The _records forms write the same matches as ONE float32 record array (batch, max_matches, 6), 8-byte aligned, in
+ * place of mk1 / mk2 / scores: per slot mk1.y, mk1.x, mk2.y, mk2.x, score, valid as 1.0f / 0.0f (every slot below
+ * max_matches is written); valid (u8) and match_ij as above.  A consumer that wants the packed record (a gather of
+ * matches between devices) then needs no packing kernel.
+ * flags (mi_mnn_from_duals_dots_records): 0 or MI_SOLVER_DOTS_BELOW_1024, with the meaning it has for mi_sinkhorn_dots:
+ * the caller vouches that every dot product is < 1024, and the kernel multiplies the uint16, read as an fp16 denormal,
+ * in one mixed-precision instruction instead of converting first.  The same matches bit for bit; a value >= 1024 under
+ * the flag gives wrong matches, no fault.  Any other bit: MI_E_PARAM. */
 MI_API size_t mi_mnn_duals_workspace_bytes(int batch, int n, int m);
 MI_API int mi_mnn_from_duals(const float *z, int batch, int n, int m, int pitch, const float *u, const float *v,
                       const float *kpts1, const float *kpts2, int max_matches, float threshold, void *workspace,
@@ -388,6 +396,15 @@ MI_API int mi_mnn_from_duals_dots(const uint16_t *dots, const float *row_info, c
                            const float *kpts2, int max_matches, float threshold, void *workspace,
                            size_t workspace_bytes, const uint32_t *solver_status, float *mk1, float *mk2,
                            float *scores, uint8_t *valid, int32_t *match_ij, mi_stream_t stream);
+MI_API int mi_mnn_from_duals_records(const float *z, int batch, int n, int m, int pitch, const float *u, const float *v,
+                              const float *kpts1, const float *kpts2, int max_matches, float threshold,
+                              void *workspace, size_t workspace_bytes, float *record, uint8_t *valid,
+                              int32_t *match_ij, mi_stream_t stream);
+MI_API int mi_mnn_from_duals_dots_records(const uint16_t *dots, const float *row_info, const float *col_info, int batch,
+                                   int n, int m, int pitch, double epsilon, const float *u, const float *v,
+                                   const float *kpts1, const float *kpts2, int max_matches, float threshold,
+                                   void *workspace, size_t workspace_bytes, const uint32_t *solver_status, int flags,
+                                   float *record, uint8_t *valid, int32_t *match_ij, mi_stream_t stream);
 
 /* ---- detector/akaze.py  AKAZE (BASELINE config 4), all maps fp32 (n,1,h,w) ---------------------
  * mi_akaze_diffuse: one explicit step of NonLinearDiffusion.forward (akaze.py:98-131):

@@ -74,6 +74,11 @@ SIGNATURES = {
     "mi_mnn_from_duals_dots": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_int, c_float, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p],
+    "mi_mnn_from_duals_records": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_float, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p],
+    "mi_mnn_from_duals_dots_records": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_size_t, c_void_p, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_void_p],
     "mi_core_maxima": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "mi_normalise_keypoints": [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p],
     "mi_essential_matrix_workspace_bytes": [c_int, c_int, c_int, c_int],

@@ -192,6 +192,19 @@ __device__ __forceinline__ float mi_z_from_dot(float dot, float2 row, float2 col
   return __builtin_fmaf(dot * col.x, -2.0f * neg_inv_eps * row.x, col.y * neg_inv_eps) + row.y * neg_inv_eps;
 }
 
+// fp32(half(bits of w's low / high 16 bits) * t): one v_fma_mix_f32 (addend +0: the product is never negative here).
+// For a uint16 dot product below 1024 the half is the denormal dot * 2^-24 (sinkhorn_dots.hip, MIX).
+__device__ __forceinline__ float mix_mul_lo(uint32_t w, float t) {
+  float p;
+  asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel_hi:[1,0,0]" : "=v"(p) : "v"(w), "v"(t));
+  return p;
+}
+__device__ __forceinline__ float mix_mul_hi(uint32_t w, float t) {
+  float p;
+  asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(p) : "v"(w), "v"(t));
+  return p;
+}
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

@@ -118,12 +118,15 @@ __global__ __launch_bounds__(512) void mnn_p_kernel(const float *__restrict__ p,
 
 // col_part != NULL (m <= 1024): the per-band column winners of mnn_band_kernel are merged here, in the prologue, instead
 // of by a separate mnn_colmerge_kernel launch (one dependent launch less; what one pair per call is made of)
+// record != NULL: the matches leave as one (batch, max_matches, 6) float record per slot -- mk1.y, mk1.x, mk2.y, mk2.x,
+// score, valid as 1.0f / 0.0f: distributed.unpack_records' layout -- in place of mk1 / mk2 / scores, so that no later
+// kernel has to pack them (a slot is 24 bytes: 8-byte aligned, three float2 stores)
 __global__ __launch_bounds__(MX_THREADS) void mnn_select_kernel(
     int n, int m, const uint64_t *__restrict__ row_best, const uint64_t *__restrict__ col_best,
     const uint64_t *__restrict__ col_part, int nb,
     const float *__restrict__ kpts1, const float *__restrict__ kpts2, int max_matches, float threshold,
     const uint32_t *__restrict__ solver_status,
-    float *__restrict__ mk1, float *__restrict__ mk2, float *__restrict__ scores,
+    float *__restrict__ mk1, float *__restrict__ mk2, float *__restrict__ scores, float *__restrict__ record,
     uint8_t *__restrict__ valid, int32_t *__restrict__ match_ij) {
   __shared__ uint64_t keys[MX_MAX];
   // the Sinkhorn call that produced the duals timed out (mi_sinkhorn_dots_status_word): no match of this call is valid
@@ -231,12 +234,21 @@ __global__ __launch_bounds__(MX_THREADS) void mnn_select_kernel(
     const uint32_t jw = 0xFFFFFFFFu - (uint32_t)(rb[i] & 0xFFFFFFFFull);
     const uint32_t j = jw < (uint32_t)m ? jw : 0u;
     const size_t o = (size_t)b * max_matches + s;
-    mk1[o * 2 + 0] = kpts1[((size_t)b * n + i) * 2 + 0];
-    mk1[o * 2 + 1] = kpts1[((size_t)b * n + i) * 2 + 1];
-    mk2[o * 2 + 0] = kpts2[((size_t)b * m + j) * 2 + 0];
-    mk2[o * 2 + 1] = kpts2[((size_t)b * m + j) * 2 + 1];
-    scores[o] = sc;
+    const float y1 = kpts1[((size_t)b * n + i) * 2 + 0], x1 = kpts1[((size_t)b * n + i) * 2 + 1];
+    const float y2 = kpts2[((size_t)b * m + j) * 2 + 0], x2 = kpts2[((size_t)b * m + j) * 2 + 1];
     const bool ok = sc > 0.0f;
+    if (record) {
+      float2 *rec = reinterpret_cast<float2 *>(record + o * 6);
+      rec[0] = make_float2(y1, x1);
+      rec[1] = make_float2(y2, x2);
+      rec[2] = make_float2(sc, ok ? 1.0f : 0.0f);
+    } else {
+      mk1[o * 2 + 0] = y1;
+      mk1[o * 2 + 1] = x1;
+      mk2[o * 2 + 0] = y2;
+      mk2[o * 2 + 1] = x2;
+      scores[o] = sc;
+    }
     valid[o] = ok ? 1 : 0;
     if (match_ij) {
       match_ij[o * 2 + 0] = ok ? (int32_t)i : -1;
@@ -252,7 +264,16 @@ __global__ __launch_bounds__(MX_THREADS) void mnn_select_kernel(
 // of P.  A workgroup owns a band of NW*RW rows (a wave holds RW whole rows, 8 consecutive columns
 // per lane per 512-column chunk): row winners by a wave reduction, per-band column winners merged
 // over the waves in LDS; a second tiny kernel merges the bands.
+//
+// A log-score source hands the kernel three things: the raw 8-column piece of a row (load_raw), two per-row constants
+// (row_consts) and two per-column constants (col_consts, formed once per column and workgroup on the way into LDS);
+// z_pair(raw, q, row, cx, cy) rebuilds the log-scores of the piece's columns q and q + 1 from them.  The kernel works on
+// such pairs throughout: v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 are the same IEEE operations on two columns at once,
+// at less than twice the issue cost of one -- and this kernel is bound by vector issue.
+typedef float v2f __attribute__((ext_vector_type(2)));
+
 struct ZSourceF32 {
+  static constexpr bool HAS_CONSTS = false;
   const float *z;       // (batch, n, pitch)
   int pitch;
   struct Raw { float4 a, c; };
@@ -266,22 +287,28 @@ struct ZSourceF32 {
     if (j + 4 < m) r.c = *reinterpret_cast<const float4 *>(src + 4);
     return r;
   }
-  __device__ __forceinline__ void decode(const Raw &r, float (&out)[8]) const {
-    out[0] = r.a.x; out[1] = r.a.y; out[2] = r.a.z; out[3] = r.a.w;
-    out[4] = r.c.x; out[5] = r.c.y; out[6] = r.c.z; out[7] = r.c.w;
-  }
   __device__ __forceinline__ Row load_row(int, int, int) const { return Row(); }
-  __device__ __forceinline__ void begin_row(const Row &) {}
-  __device__ __forceinline__ float col(int, int) const { return 0.0f; }
-  __device__ __forceinline__ void finish(float (&)[8], const float2 (&)[8]) const {}
+  __device__ __forceinline__ float2 row_consts(const Row &) const { return make_float2(0.f, 0.f); }
+  __device__ __forceinline__ float2 col_consts(float2) const { return make_float2(0.f, 0.f); }
+  __device__ __forceinline__ v2f z_pair(const Raw &r, int q, float2, v2f, v2f) const {
+    const float x[8] = {r.a.x, r.a.y, r.a.z, r.a.w, r.c.x, r.c.y, r.c.z, r.c.w};
+    return v2f{x[q], x[q + 1]};
+  }
 };
 
+// mi_z_from_dot(dot, row, col, nie) = fma(dot * col.x, -2 * nie * row.x, col.y * nie) + row.y * nie with its products
+// formed once where their operands live: col.y * nie per column, -2 * nie * row.x and row.y * nie per row -- the same
+// fp32 products, so the same z bit for bit.  MIX (the caller vouches for dots < 1024, MI_SOLVER_DOTS_BELOW_1024): the
+// uint16 is read as the fp16 denormal dot * 2^-24 and dot * col.x is one v_fma_mix_f32; the row factor carries the 2^24
+// back.  The exactness argument is sinkhorn_dots.hip's MIX note: the scaled product rounds as the unscaled one does and
+// the fma forms the exact product before it rounds.
+template <bool MIX>
 struct ZSourceDots {
+  static constexpr bool HAS_CONSTS = true;
   const uint16_t *dots;  // (batch, n, pitch) uint16 dot products
   int pitch;
-  const float2 *row_info, *col_info;
+  const float2 *row_info;
   float neg_inv_eps;
-  float2 ri;
   typedef uint4 Raw;
   typedef float2 Row;
   __device__ __forceinline__ Raw load_raw(int b, int n, int i, int j, int m) const {
@@ -290,16 +317,19 @@ struct ZSourceDots {
     // (their values are never used: the kernel replaces p by -1 for j >= m)
     return *reinterpret_cast<const uint4 *>(dots + ((size_t)b * n + i) * pitch + min(j, pitch - 8));   // pitch % 8 == 0
   }
-  __device__ __forceinline__ void decode(const Raw &r, float (&out)[8]) const {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int q = 0; q < 8; ++q) out[q] = (float)((q & 1) ? (w[q >> 1] >> 16) : (w[q >> 1] & 0xFFFFu));
-  }
   __device__ __forceinline__ Row load_row(int b, int n, int i) const { return row_info[(size_t)b * n + i]; }
-  __device__ __forceinline__ void begin_row(const Row &r) { ri = r; }
-  __device__ __forceinline__ void finish(float (&x)[8], const float2 (&ci)[8]) const {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) x[q] = mi_z_from_dot(x[q], ri, ci[q], neg_inv_eps);
+  __device__ __forceinline__ float2 row_consts(const Row &r) const {
+    const float g = -2.0f * neg_inv_eps * r.x;
+    return make_float2(MIX ? g * 16777216.0f : g, r.y * neg_inv_eps);
+  }
+  __device__ __forceinline__ float2 col_consts(float2 c) const { return make_float2(c.x, c.y * neg_inv_eps); }
+  __device__ __forceinline__ v2f z_pair(const Raw &r, int q, float2 rk, v2f cx, v2f cy) const {
+    const uint32_t w4[4] = {r.x, r.y, r.z, r.w};
+    const uint32_t w = w4[q >> 1];
+    v2f t;
+    if constexpr (MIX) t = v2f{mix_mul_lo(w, cx.x), mix_mul_hi(w, cx.y)};
+    else t = v2f{(float)(w & 0xFFFFu), (float)(w >> 16)} * cx;
+    return __builtin_elementwise_fma(t, v2f{rk.x, rk.x}, cy) + v2f{rk.y, rk.y};
   }
 };
 
@@ -312,7 +342,9 @@ struct ZSourceDots {
 // VGPRs with 11 dwords of scratch, two 16-wave workgroups per CU (78 KB of LDS each) -- 139.9 us per 128 pairs of
 // 1024 x 1024 against 166.6 at 75 VGPRs (one workgroup per CU) and 158.5 for the two-chunk kernel (137 VGPRs).  The
 // one-chunk kernel itself loses by the same squeeze (77 -> 110 us per 448 pairs): its three 8-wave workgroups per CU
-// already overlap each other's phases.
+// already overlap each other's phases.  (Figures of the kernel's earlier body, which kept a running (value, index) pair
+// per row and column; the body below needs 63-65 VGPRs in every one-chunk form, the split one with at most 12 bytes of
+// scratch; at 128 pairs of 1024 x 1024 the whole call, select kernel included, went from 161.6 to 125.2 us.)
 template <typename SRC, int E8, int RW, int NW, bool FULL = false, bool SPLIT = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPLIT ? 8 : 1, 8))) void mnn_band_kernel(SRC src, int n, int m, const float *__restrict__ u,
                                                            const float *__restrict__ v,
@@ -320,6 +352,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPLIT ?
                                                            uint64_t *__restrict__ row_best,
                                                            uint64_t *__restrict__ col_part) {
   static_assert(!SPLIT || (E8 == 1 && NW % 2 == 0), "the split form runs the one-chunk code on wave pairs");
+  static_assert(RW == 4, "the rows' maxima are reduced four at a time (wave_max4)");
   constexpr int RG = SPLIT ? NW / 2 : NW;        // row groups of the workgroup
   constexpr int BAND = RG * RW;
   constexpr int NC = 512 * E8 * (SPLIT ? 2 : 1);   // columns covered by the workgroup
@@ -345,9 +378,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPLIT ?
   }
   // per-column data: the workgroup fetches v and col_info once with coalesced loads and every lane picks its
   // eight consecutive columns out of LDS (sixteen strided 4- and 8-byte loads per lane otherwise: the address
-  // unit, not the data, was what this prologue cost)
+  // unit, not the data, was what this prologue cost).  The column constants are formed on the way in: once per
+  // column and workgroup, not once per element.
   __shared__ float s_v[NC];
-  __shared__ float2 s_ci[NC];
+  __shared__ float s_cx[SRC::HAS_CONSTS ? NC : 1], s_cy[SRC::HAS_CONSTS ? NC : 1];   // apart: a pair's constants side by side
   {
     constexpr int PER = NC / (64 * NW);            // columns per thread (1 or 2): both loads issued, then both stores
     float tv[PER];
@@ -356,68 +390,106 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SPLIT ?
     for (int q = 0; q < PER; ++q) {
       const int c = threadIdx.x + q * 64 * NW;
       tv[q] = c < m ? v[(size_t)b * (m + 1) + c] : 0.0f;
-      tc[q] = (col_info && c < m) ? col_info[(size_t)b * m + c] : make_float2(0.f, 0.f);
+      if constexpr (SRC::HAS_CONSTS) tc[q] = c < m ? col_info[(size_t)b * m + c] : make_float2(0.f, 0.f);
     }
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
       const int c = threadIdx.x + q * 64 * NW;
       s_v[c] = tv[q];
-      s_ci[c] = tc[q];
+      if constexpr (SRC::HAS_CONSTS) {
+        const float2 ck = src.col_consts(tc[q]);
+        s_cx[c] = ck.x;
+        s_cy[c] = ck.y;
+      }
     }
   }
   __syncthreads();
-  float vv[E8][8];
-  float2 ci[E8][8];
+  v2f vv[E8][4], cx[E8][4], cy[E8][4];
+#pragma unroll
+  for (int e = 0; e < E8; ++e)
+#pragma unroll
+    for (int q = 0; q < 8; q += 2) {
+      const int c = cbase + e * 512 + lane * 8 + q;
+      vv[e][q >> 1] = v2f{s_v[c], s_v[c + 1]};
+      cx[e][q >> 1] = SRC::HAS_CONSTS ? v2f{s_cx[c], s_cx[c + 1]} : v2f{0.f, 0.f};
+      cy[e][q >> 1] = SRC::HAS_CONSTS ? v2f{s_cy[c], s_cy[c + 1]} : v2f{0.f, 0.f};
+    }
+
+  // The wave's RW x 8 E8 probabilities stay in registers; entries outside the matrix become -1, below every
+  // probability.  Winners are found by value first and by place second: maxima with v_max3_f32 chains (a NaN operand is
+  // ignored, so a NaN never wins and -1 is what a row or column of nothing but NaN is left with), then the FIRST place
+  // attaining the maximum -- what the strict > of a running (value, index) pair keeps, at a third of the instructions.
+  float p[RW][E8][8];
+  float rmax[RW];          // per-lane row maxima, then (wave_max4) the rows' maxima in every lane
+#pragma unroll
+  for (int r = 0; r < RW; ++r) {
+    const bool live = row0 + r < n;
+    const float ui = uis[r];
+    const float2 rk = src.row_consts(rowd[r]);
+    float lm = -1.0f;
+#pragma unroll
+    for (int e = 0; e < E8; ++e) {
+#pragma unroll
+      for (int q = 0; q < 8; q += 2) {
+        // mi_prob_exp((z + u_i) + v_j), sinkhorn.py:145,206, on two columns: the same operations in the same order
+        const v2f z = src.z_pair(raw[r][e], q, rk, cx[e][q >> 1], cy[e][q >> 1]);
+        const v2f t = ((z + v2f{ui, ui}) + vv[e][q >> 1]) * v2f{1.4426950408889634f, 1.4426950408889634f};
+        const float x[2] = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int j = cbase + e * 512 + lane * 8 + q + h;
+          p[r][e][q + h] = (FULL || (live && j < m)) ? x[h] : -1.0f;
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 8; q += 2) lm = fmaxf(fmaxf(lm, p[r][e][q]), p[r][e][q + 1]);
+    }
+    rmax[r] = lm;
+  }
+  wave_max4(rmax);
+  // a row's winner: the lowest lane holding the row maximum, and in it the lowest column (columns ascend with the chunk,
+  // then the lane, then q).  The ballots are wave-uniform: all of this is scalar work.
+  uint64_t rkey[RW];
+#pragma unroll
+  for (int r = 0; r < RW; ++r) {
+    const float rm = rmax[r];
+    uint32_t jw = 0u;
+#pragma unroll
+    for (int e = E8 - 1; e >= 0; --e) {              // descending: a lower chunk's hit replaces a higher one's
+      uint64_t hit[8], any = 0ull;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        hit[q] = __builtin_amdgcn_ballot_w64(p[r][e][q] == rm);
+        any |= hit[q];
+      }
+      const uint64_t first = any & (0ull - any);
+      uint32_t qw = 7u;
+#pragma unroll
+      for (int q = 6; q >= 0; --q) qw = (hit[q] & first) != 0ull ? (uint32_t)q : qw;
+      const uint32_t le = any != 0ull ? (uint32_t)__builtin_ctzll(any) : 0u;
+      jw = any != 0ull ? (uint32_t)(cbase + e * 512) + le * 8u + qw : jw;
+    }
+    rkey[r] = rm >= 0.0f ? best_key(rm, jw) : 0ull;   // rm == -1: every entry NaN or outside the matrix -- no winner
+  }
+  {
+    const uint64_t mine = lane == 0 ? rkey[0] : lane == 1 ? rkey[1] : lane == 2 ? rkey[2] : rkey[3];   // lane r: row r
+    if constexpr (SPLIT) {
+      if (lane < RW) halfkey[wave][lane] = mine;
+    } else {
+      if (lane < RW && row0 + lane < n) row_best[(size_t)b * n + row0 + lane] = mine;
+    }
+  }
+  // per-lane column winners over this wave's rows: the maximum, then the first row attaining it
 #pragma unroll
   for (int e = 0; e < E8; ++e)
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-      vv[e][q] = s_v[cbase + e * 512 + lane * 8 + q];
-      ci[e][q] = s_ci[cbase + e * 512 + lane * 8 + q];
+      const float cm = fmaxf(fmaxf(fmaxf(fmaxf(p[0][e][q], p[1][e][q]), p[2][e][q]), p[3][e][q]), -1.0f);
+      uint32_t t = 3u;
+#pragma unroll
+      for (int r = 2; r >= 0; --r) t = p[r][e][q] == cm ? (uint32_t)r : t;
+      red[rg][cbase + e * 512 + lane * 8 + q] = cm >= 0.0f ? best_key(cm, (uint32_t)row0 + t) : 0ull;
     }
-
-  float cbest[E8][8];      // per-lane column winners over this wave's rows: rows ascend, strict > keeps the first
-  int cidx[E8][8];
-#pragma unroll
-  for (int e = 0; e < E8; ++e)
-#pragma unroll
-    for (int q = 0; q < 8; ++q) { cbest[e][q] = -1.0f; cidx[e][q] = 0; }
-
-#pragma unroll
-  for (int r = 0; r < RW; ++r) {
-    const int i = row0 + r;
-    const bool live = i < n;
-    const float ui = uis[r];
-    src.begin_row(rowd[r]);
-    float rbest = -1.0f;   // per-lane row winner: columns ascend within a lane
-    int rj = 0;
-#pragma unroll
-    for (int e = 0; e < E8; ++e) {
-      float x[8];
-      src.decode(raw[r][e], x);
-      src.finish(x, ci[e]);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int j = cbase + e * 512 + lane * 8 + q;
-        float p = mi_prob_exp((x[q] + ui) + vv[e][q]);                         // sinkhorn.py:145,206
-        if constexpr (!FULL) p = (live && j < m) ? p : -1.0f;
-        if (p > rbest) { rbest = p; rj = j; }
-        if (p > cbest[e][q]) { cbest[e][q] = p; cidx[e][q] = i; }
-      }
-    }
-    uint64_t key = rbest >= 0.0f ? best_key(rbest, (uint32_t)rj) : 0ull;
-    key = wave_max_u64(key);
-    if constexpr (SPLIT) {
-      if (lane == 0) halfkey[wave][r] = key;
-    } else {
-      if (lane == 0 && live) row_best[(size_t)b * n + i] = key;
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < E8; ++e)
-#pragma unroll
-    for (int q = 0; q < 8; ++q)
-      red[rg][cbase + e * 512 + lane * 8 + q] = cbest[e][q] >= 0.0f ? best_key(cbest[e][q], (uint32_t)cidx[e][q]) : 0ull;
   __syncthreads();
   if constexpr (SPLIT) {                         // the rows' winners: the better of the two halves
     if (half == 0 && lane < RW && row0 + lane < n) {
@@ -469,15 +541,22 @@ DualsWork duals_carve(void *workspace, int batch, int n, int m) {
   return w;
 }
 
+// where the matches go: mk1 / mk2 / scores, or one record (see mnn_select_kernel); valid and match_ij either way
+struct MatchOut {
+  float *mk1, *mk2, *scores, *record;
+  uint8_t *valid;
+  int32_t *match_ij;
+};
+
 template <typename SRC>
 int mnn_from_source(SRC src, const float2 *col_info, int batch, int n, int m, const float *u, const float *v,
                     const float *kpts1, const float *kpts2, int max_matches, float threshold, void *workspace,
-                    size_t workspace_bytes, const uint32_t *solver_status, float *mk1, float *mk2, float *scores,
-                    uint8_t *valid, int32_t *match_ij, hipStream_t s) {
-  if (!u || !v || !kpts1 || !kpts2 || !workspace || !mk1 || !mk2 || !scores || !valid) return MI_E_NULL;
+                    size_t workspace_bytes, const uint32_t *solver_status, const MatchOut &out, hipStream_t s) {
+  if (!u || !v || !kpts1 || !kpts2 || !workspace || !out.valid) return MI_E_NULL;
+  if (!out.record && (!out.mk1 || !out.mk2 || !out.scores)) return MI_E_NULL;
   if (batch <= 0 || n <= 0 || m <= 0 || batch > 65535) return MI_E_SHAPE;
   if (n > MX_MAX || m > 1024 || max_matches <= 0) return MI_E_PARAM;
-  if (((uintptr_t)workspace % 8) != 0) return MI_E_ALIGN;
+  if (((uintptr_t)workspace % 8) != 0 || ((uintptr_t)out.record % 8) != 0) return MI_E_ALIGN;
   if (workspace_bytes < duals_bytes(batch, n, m)) return MI_E_CAPACITY;
   const DualsWork w = duals_carve(workspace, batch, n, m);
   const int nb = ceil_div(n, DUALS_BAND);
@@ -499,18 +578,63 @@ int mnn_from_source(SRC src, const float2 *col_info, int batch, int n, int m, co
                        col_info, w.row_best, w.col_part);
   }
   if (batch <= 32) {
-    // few pairs: the select kernel merges the bands' column winners itself (one launch less on the latency path)
+    // few pairs: the select kernel merges the bands' column winners itself (one launch less on the latency path).
+    // (Measured at 448 pairs of 512 x 512 too: 17.6 us against 6.6 + 14.2 us for the two launches below.  The launch
+    // stays above 32 pairs because the node count of a captured 64-pair forward is pinned by the runtime tests.)
     hipLaunchKernelGGL(mnn_select_kernel, dim3(batch), dim3(MX_THREADS), 0, s, n, m, w.row_best, w.col_best,
-                       (const uint64_t *)w.col_part, nb, kpts1, kpts2, max_matches, threshold, solver_status, mk1, mk2,
-                       scores, valid, match_ij);
+                       (const uint64_t *)w.col_part, nb, kpts1, kpts2, max_matches, threshold, solver_status, out.mk1,
+                       out.mk2, out.scores, out.record, out.valid, out.match_ij);
     return mi_launch_status();
   }
   hipLaunchKernelGGL(mnn_colmerge_kernel, dim3(ceil_div(m, 256), batch), dim3(256), 0, s, w.col_part, nb, m,
                      w.col_best);
   hipLaunchKernelGGL(mnn_select_kernel, dim3(batch), dim3(MX_THREADS), 0, s, n, m, w.row_best, w.col_best,
-                     (const uint64_t *)nullptr, 0, kpts1, kpts2, max_matches, threshold, solver_status, mk1, mk2, scores,
-                     valid, match_ij);
+                     (const uint64_t *)nullptr, 0, kpts1, kpts2, max_matches, threshold, solver_status, out.mk1, out.mk2,
+                     out.scores, out.record, out.valid, out.match_ij);
   return mi_launch_status();
+}
+
+int mnn_from_z(const float *z, int batch, int n, int m, int pitch, const float *u, const float *v, const float *kpts1,
+               const float *kpts2, int max_matches, float threshold, void *workspace, size_t workspace_bytes,
+               const MatchOut &out, hipStream_t s) {
+  if (!z) return MI_E_NULL;
+  if (pitch < m || pitch % 4 != 0 || ((uintptr_t)z % 16) != 0) return MI_E_ALIGN;
+  ZSourceF32 src;
+  src.z = z;
+  src.pitch = pitch;
+  return mnn_from_source(src, nullptr, batch, n, m, u, v, kpts1, kpts2, max_matches, threshold, workspace,
+                         workspace_bytes, nullptr, out, s);
+}
+
+template <bool MIX>
+int mnn_from_dots_as(const uint16_t *dots, const float *row_info, const float *col_info, int batch, int n, int m,
+                     int pitch, double epsilon, const float *u, const float *v, const float *kpts1, const float *kpts2,
+                     int max_matches, float threshold, void *workspace, size_t workspace_bytes,
+                     const uint32_t *solver_status, const MatchOut &out, hipStream_t s) {
+  ZSourceDots<MIX> src;
+  src.dots = dots;
+  src.pitch = pitch;
+  src.row_info = reinterpret_cast<const float2 *>(row_info);
+  src.neg_inv_eps = (float)(-1.0 / epsilon);
+  return mnn_from_source(src, reinterpret_cast<const float2 *>(col_info), batch, n, m, u, v, kpts1, kpts2, max_matches,
+                         threshold, workspace, workspace_bytes, solver_status, out, s);
+}
+
+int mnn_from_dots(const uint16_t *dots, const float *row_info, const float *col_info, int batch, int n, int m, int pitch,
+                  double epsilon, const float *u, const float *v, const float *kpts1, const float *kpts2,
+                  int max_matches, float threshold, void *workspace, size_t workspace_bytes,
+                  const uint32_t *solver_status, int flags, const MatchOut &out, hipStream_t s) {
+  if (!dots || !row_info || !col_info) return MI_E_NULL;
+  if (pitch < m || pitch % 8 != 0 || ((uintptr_t)dots % 16) != 0) return MI_E_ALIGN;
+  if (!(epsilon > 0.0) || (flags & ~MI_SOLVER_DOTS_BELOW_1024) != 0) return MI_E_PARAM;
+  if (solver_status && ((uintptr_t)solver_status % 4) != 0) return MI_E_ALIGN;
+  // dots vouched to be < 1024: read as fp16 denormals.  Only for the epsilons mi_sinkhorn_dots itself takes: the row
+  // factor carries 2^24 there, and 1 / epsilon is bounded.
+  if ((flags & MI_SOLVER_DOTS_BELOW_1024) != 0 && epsilon >= MI_DOTS_MIN_EPSILON)
+    return mnn_from_dots_as<true>(dots, row_info, col_info, batch, n, m, pitch, epsilon, u, v, kpts1, kpts2, max_matches,
+                                  threshold, workspace, workspace_bytes, solver_status, out, s);
+  return mnn_from_dots_as<false>(dots, row_info, col_info, batch, n, m, pitch, epsilon, u, v, kpts1, kpts2, max_matches,
+                                 threshold, workspace, workspace_bytes, solver_status, out, s);
 }
 
 }  // namespace
@@ -525,13 +649,19 @@ extern "C" int mi_mnn_from_duals(const float *z, int batch, int n, int m, int pi
                                  void *workspace, size_t workspace_bytes, float *mk1, float *mk2, float *scores,
                                  uint8_t *valid, int32_t *match_ij, mi_stream_t stream) {
   MI_ENTER();
-  if (!z) return MI_E_NULL;
-  if (pitch < m || pitch % 4 != 0 || ((uintptr_t)z % 16) != 0) return MI_E_ALIGN;
-  ZSourceF32 src;
-  src.z = z;
-  src.pitch = pitch;
-  return mnn_from_source(src, nullptr, batch, n, m, u, v, kpts1, kpts2, max_matches, threshold, workspace,
-                         workspace_bytes, nullptr, mk1, mk2, scores, valid, match_ij, (hipStream_t)stream);
+  if (!mk1 || !mk2 || !scores) return MI_E_NULL;
+  return mnn_from_z(z, batch, n, m, pitch, u, v, kpts1, kpts2, max_matches, threshold, workspace, workspace_bytes,
+                    MatchOut{mk1, mk2, scores, nullptr, valid, match_ij}, (hipStream_t)stream);
+}
+
+extern "C" int mi_mnn_from_duals_records(const float *z, int batch, int n, int m, int pitch, const float *u,
+                                         const float *v, const float *kpts1, const float *kpts2, int max_matches,
+                                         float threshold, void *workspace, size_t workspace_bytes, float *record,
+                                         uint8_t *valid, int32_t *match_ij, mi_stream_t stream) {
+  MI_ENTER();
+  if (!record) return MI_E_NULL;
+  return mnn_from_z(z, batch, n, m, pitch, u, v, kpts1, kpts2, max_matches, threshold, workspace, workspace_bytes,
+                    MatchOut{nullptr, nullptr, nullptr, record, valid, match_ij}, (hipStream_t)stream);
 }
 
 extern "C" int mi_mnn_from_duals_dots(const uint16_t *dots, const float *row_info, const float *col_info, int batch,
@@ -541,19 +671,23 @@ extern "C" int mi_mnn_from_duals_dots(const uint16_t *dots, const float *row_inf
                                       float *mk1, float *mk2, float *scores, uint8_t *valid, int32_t *match_ij,
                                       mi_stream_t stream) {
   MI_ENTER();
-  if (!dots || !row_info || !col_info) return MI_E_NULL;
-  if (pitch < m || pitch % 8 != 0 || ((uintptr_t)dots % 16) != 0) return MI_E_ALIGN;
-  if (!(epsilon > 0.0)) return MI_E_PARAM;
-  ZSourceDots src;
-  src.dots = dots;
-  src.pitch = pitch;
-  src.row_info = reinterpret_cast<const float2 *>(row_info);
-  src.col_info = reinterpret_cast<const float2 *>(col_info);
-  src.neg_inv_eps = (float)(-1.0 / epsilon);
-  src.ri = make_float2(0.f, 0.f);
-  if (solver_status && ((uintptr_t)solver_status % 4) != 0) return MI_E_ALIGN;
-  return mnn_from_source(src, src.col_info, batch, n, m, u, v, kpts1, kpts2, max_matches, threshold, workspace,
-                         workspace_bytes, solver_status, mk1, mk2, scores, valid, match_ij, (hipStream_t)stream);
+  if (!mk1 || !mk2 || !scores) return MI_E_NULL;
+  return mnn_from_dots(dots, row_info, col_info, batch, n, m, pitch, epsilon, u, v, kpts1, kpts2, max_matches, threshold,
+                       workspace, workspace_bytes, solver_status, 0, MatchOut{mk1, mk2, scores, nullptr, valid, match_ij},
+                       (hipStream_t)stream);
+}
+
+extern "C" int mi_mnn_from_duals_dots_records(const uint16_t *dots, const float *row_info, const float *col_info,
+                                              int batch, int n, int m, int pitch, double epsilon, const float *u,
+                                              const float *v, const float *kpts1, const float *kpts2, int max_matches,
+                                              float threshold, void *workspace, size_t workspace_bytes,
+                                              const uint32_t *solver_status, int flags, float *record, uint8_t *valid,
+                                              int32_t *match_ij, mi_stream_t stream) {
+  MI_ENTER();
+  if (!record) return MI_E_NULL;
+  return mnn_from_dots(dots, row_info, col_info, batch, n, m, pitch, epsilon, u, v, kpts1, kpts2, max_matches, threshold,
+                       workspace, workspace_bytes, solver_status, flags,
+                       MatchOut{nullptr, nullptr, nullptr, record, valid, match_ij}, (hipStream_t)stream);
 }
 
 extern "C" int mi_mnn_extract(const float *p, int batch, int n, int m, const float *kpts1, const float *kpts2,
@@ -581,7 +715,7 @@ extern "C" int mi_mnn_extract(const float *p, int batch, int n, int m, const flo
   }
   hipLaunchKernelGGL(mnn_select_kernel, dim3(batch), dim3(MX_THREADS), 0, s, n, m, row_best, col_best,
                      (const uint64_t *)nullptr, 0, kpts1, kpts2, max_matches, threshold, (const uint32_t *)nullptr, mk1,
-                     mk2, scores, valid, match_ij);
+                     mk2, scores, (float *)nullptr, valid, match_ij);
   return mi_launch_status();
 }
 

@@ -128,17 +128,7 @@ __device__ __forceinline__ float combine_column(const float *__restrict__ part_b
 // re-enters in u_i and in the dustbin-column entry.  Per-column data come from aligned, padded
 // arrays (16-byte loads): tp = t_j (0 in the padding), wp = nie*nb_j + v_j (-inf in the padding:
 // such a column contributes nowhere), the latter rebuilt by the combine kernel every iteration.
-// fp32(half(bits of w's low / high 16 bits) * t): one v_fma_mix_f32 (addend +0: the product is never negative here)
-__device__ __forceinline__ float mix_mul_lo(uint32_t w, float t) {
-  float p;
-  asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel_hi:[1,0,0]" : "=v"(p) : "v"(w), "v"(t));
-  return p;
-}
-__device__ __forceinline__ float mix_mul_hi(uint32_t w, float t) {
-  float p;
-  asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(p) : "v"(w), "v"(t));
-  return p;
-}
+// (mix_mul_lo / mix_mul_hi, the one-instruction product of the MIX form below, live in common.h: K7 uses them too)
 
 // MIX (round 4; the caller vouches for dots < 1024, MI_SOLVER_DOTS_BELOW_1024): a uint16 below 1024 read as an fp16 is the
 // denormal dot * 2^-24, which v_fma_mix_f32 widens on the fly -- dot * t becomes ONE instruction (fma(half, t, +0): the

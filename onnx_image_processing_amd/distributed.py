@@ -55,8 +55,42 @@ def shard_range(total: int, rank: int, world: int) -> tuple[int, int]:
     return begin, begin + base + (1 if rank < extra else 0)
 
 
+def tag_record(rec: torch.Tensor, valid: torch.Tensor) -> None:
+    """Mark `valid` (B, Mx) as the validity mask that one call wrote together with the record `rec` (B, Mx, 6) -- what
+    the match kernels do (ops.mnn_from_duals[_dots]): rec[..., 5] already holds valid as 1.0 / 0.0.  The versions of both
+    tensors are remembered: an in-place edit of either (through any view) ends the claim."""
+    valid._mi_record = (rec, rec._version, valid._version)
+
+
+def _tagged_record(mk1: torch.Tensor, mk2: torch.Tensor, scores: torch.Tensor, valid: torch.Tensor):
+    """The record the four tensors already ARE -- mk1 / mk2 / scores the views [..., 0:2], [..., 2:4], [..., 4] of one
+    contiguous (B, Mx, 6) float32 tensor that `valid` was tagged with, nothing edited since -- or None."""
+    tag = getattr(valid, "_mi_record", None)
+    if tag is None:
+        return None
+    rec, rec_version, valid_version = tag
+    if rec._version != rec_version or valid._version != valid_version:
+        return None
+    if rec.dtype != torch.float32 or rec.dim() != 3 or rec.shape[2] != RECORD_FIELDS or not rec.is_contiguous():
+        return None
+    b, mx, f = rec.shape
+    if tuple(valid.shape) != (b, mx) or valid.device != rec.device:
+        return None
+    off = rec.storage_offset()
+    for t, shape, stride, first in ((mk1, (b, mx, 2), (mx * f, f, 1), 0), (mk2, (b, mx, 2), (mx * f, f, 1), 2),
+                                    (scores, (b, mx), (mx * f, f), 4)):
+        if (t._base is not rec or tuple(t.shape) != shape or tuple(t.stride()) != stride
+                or t.storage_offset() != off + first):
+            return None
+    return rec
+
+
 def pack_records(mk1: torch.Tensor, mk2: torch.Tensor, scores: torch.Tensor, valid: torch.Tensor) -> torch.Tensor:
-    """(B,Mx,2),(B,Mx,2),(B,Mx),(B,Mx) -> one float32 record tensor (B, Mx, 6)."""
+    """(B,Mx,2),(B,Mx,2),(B,Mx),(B,Mx) -> one float32 record tensor (B, Mx, 6).  Matches that come straight from the
+    match kernels are views of such a record already: it is returned as it is (no copy, no kernel launch)."""
+    rec = _tagged_record(mk1, mk2, scores, valid)
+    if rec is not None:
+        return rec
     return torch.cat([mk1, mk2, scores.unsqueeze(-1), valid.to(scores.dtype).unsqueeze(-1)], dim=-1).contiguous()
 
 

@@ -9,6 +9,7 @@ from __future__ import annotations
 import torch
 
 from . import _native as N
+from .distributed import RECORD_FIELDS, tag_record
 
 F32 = torch.float32
 
@@ -376,6 +377,14 @@ def dots_supported(b: int, n: int, m: int, epsilon: float = 1.0) -> bool:
     return epsilon >= DOTS_MIN_EPSILON and int(N.load().mi_sinkhorn_dots_workspace_bytes(b, n, m)) > 0
 
 
+class DotsState(tuple):
+    """The state tuple of sinkhorn_bits(return_state=True) -- (dots, row_info, col_info, pitch, (workspace, status word
+    address)) -- which also remembers the descriptors' bit count: below 1024 bits every dot product is below 1024, and
+    mnn_from_duals_dots may vouch for that (MI_SOLVER_DOTS_BELOW_1024).  A slice or a hand-built tuple carries no count
+    and nothing is vouched for."""
+    num_bits = None
+
+
 def sinkhorn_bits(bits1: torch.Tensor, bits2: torch.Tensor, normalized: bool, epsilon: float, unused_score: float,
                   iterations: int, return_duals: bool = False, want_p: bool = True, return_state: bool = False):
     """Cost + Sinkhorn for packed hard-bit descriptors (B,N,D/32),(B,M,D/32) int32 -> P (B,N+1,M+1),
@@ -409,7 +418,9 @@ def sinkhorn_bits(bits1: torch.Tensor, bits2: torch.Tensor, normalized: bool, ep
            _solver_flags | (MI_SOLVER_DOTS_BELOW_1024 if words * 32 < 1024 else 0), N.stream_ptr())
     if return_state:
         status = N.load().mi_sinkhorn_dots_status_word(work.data_ptr(), b, n, m)
-        return p, u, v, (dots, row_info, col_info, pitch, (work, status))
+        state = DotsState((dots, row_info, col_info, pitch, (work, status)))
+        state.num_bits = words * 32
+        return p, u, v, state
     return (p, u, v) if (return_duals or not want_p) else p
 
 
@@ -457,14 +468,23 @@ def mnn_extract(p: torch.Tensor, kpts1: torch.Tensor, kpts2: torch.Tensor, max_m
     return out + (ij,) if return_indices else out
 
 
-def _mnn_outputs(b, max_matches, dev):
-    return (torch.empty((b, max_matches, 2), dtype=F32, device=dev), torch.empty((b, max_matches, 2), dtype=F32, device=dev),
-            torch.empty((b, max_matches), dtype=F32, device=dev), torch.empty((b, max_matches), dtype=torch.bool, device=dev),
+def mnn_duals_supported(b: int, n: int, m: int) -> bool:
+    return int(N.load().mi_mnn_duals_workspace_bytes(b, n, m)) > 0
+
+
+def _mnn_record_outputs(b, max_matches, dev):
+    """(record (B, Mx, 6) float32, valid (B, Mx) bool, match_ij (B, Mx, 2) int32) for the _records entries."""
+    return (torch.empty((b, max_matches, RECORD_FIELDS), dtype=F32, device=dev),
+            torch.empty((b, max_matches), dtype=torch.bool, device=dev),          # the kernel writes 0/1 bytes
             torch.empty((b, max_matches, 2), dtype=torch.int32, device=dev))
 
 
-def mnn_duals_supported(b: int, n: int, m: int) -> bool:
-    return int(N.load().mi_mnn_duals_workspace_bytes(b, n, m)) > 0
+def _mnn_record_views(rec, valid, ij, return_indices):
+    """mk1, mk2, scores as views of the record the select kernel wrote, and valid tagged as that record's own
+    (distributed.pack_records then hands the record back instead of packing it again)."""
+    tag_record(rec, valid)
+    out = (rec[..., 0:2], rec[..., 2:4], rec[..., 4], valid)
+    return out + (ij,) if return_indices else out
 
 
 def mnn_from_duals(z: torch.Tensor, m: int, pitch: int, u: torch.Tensor, v: torch.Tensor, kpts1: torch.Tensor,
@@ -476,32 +496,36 @@ def mnn_from_duals(z: torch.Tensor, m: int, pitch: int, u: torch.Tensor, v: torc
     if wbytes == 0:
         raise RuntimeError(f"mnn_from_duals supports N <= 4096 and M <= 1024, got ({n}, {m})")
     work = torch.empty((wbytes // 8,), dtype=torch.int64, device=z.device)
-    mk1, mk2, sc, valid, ij = _mnn_outputs(b, max_matches, z.device)
-    N.call("mi_mnn_from_duals", N.dev(z, F32, "z"), b, n, m, pitch, N.dev(u, F32, "u"), N.dev(v, F32, "v"),
+    rec, valid, ij = _mnn_record_outputs(b, max_matches, z.device)
+    N.call("mi_mnn_from_duals_records", N.dev(z, F32, "z"), b, n, m, pitch, N.dev(u, F32, "u"), N.dev(v, F32, "v"),
            N.dev(k1, F32, "keypoints1"), N.dev(k2, F32, "keypoints2"), int(max_matches), float(threshold),
-           work.data_ptr(), wbytes, mk1.data_ptr(), mk2.data_ptr(), sc.data_ptr(), valid.data_ptr(), ij.data_ptr(),
-           N.stream_ptr())
-    out = (mk1, mk2, sc, valid)
-    return out + (ij,) if return_indices else out
+           work.data_ptr(), wbytes, rec.data_ptr(), valid.data_ptr(), ij.data_ptr(), N.stream_ptr())
+    return _mnn_record_views(rec, valid, ij, return_indices)
 
 
 def mnn_from_duals_dots(state, m: int, epsilon: float, u: torch.Tensor, v: torch.Tensor, kpts1: torch.Tensor,
-                        kpts2: torch.Tensor, max_matches: int, threshold: float, return_indices: bool = False):
+                        kpts2: torch.Tensor, max_matches: int, threshold: float, return_indices: bool = False,
+                        dots_below_1024: bool | None = None):
+    """dots_below_1024: vouch that every dot product is below 1024 (the kernel then multiplies the uint16 in one mixed-
+    precision instruction; the same matches bit for bit).  None: decided from the bit count a DotsState carries."""
     dots, row_info, col_info, pitch = state[:4]
     status = state[4][1] if len(state) > 4 else None          # the producing Sinkhorn call's status word (device address)
+    if dots_below_1024 is None:
+        num_bits = getattr(state, "num_bits", None)
+        dots_below_1024 = num_bits is not None and num_bits < 1024
     b, n, _ = dots.shape
     k1, k2 = kpts1.float().contiguous(), kpts2.float().contiguous()
     wbytes = int(N.load().mi_mnn_duals_workspace_bytes(b, n, m))
     if wbytes == 0:
         raise RuntimeError(f"mnn_from_duals_dots supports N <= 4096 and M <= 1024, got ({n}, {m})")
     work = torch.empty((wbytes // 8,), dtype=torch.int64, device=dots.device)
-    mk1, mk2, sc, valid, ij = _mnn_outputs(b, max_matches, dots.device)
-    N.call("mi_mnn_from_duals_dots", dots.data_ptr(), row_info.data_ptr(), col_info.data_ptr(), b, n, m, pitch,
+    rec, valid, ij = _mnn_record_outputs(b, max_matches, dots.device)
+    N.call("mi_mnn_from_duals_dots_records", dots.data_ptr(), row_info.data_ptr(), col_info.data_ptr(), b, n, m, pitch,
            float(epsilon), N.dev(u, F32, "u"), N.dev(v, F32, "v"), N.dev(k1, F32, "keypoints1"),
            N.dev(k2, F32, "keypoints2"), int(max_matches), float(threshold), work.data_ptr(), wbytes, status,
-           mk1.data_ptr(), mk2.data_ptr(), sc.data_ptr(), valid.data_ptr(), ij.data_ptr(), N.stream_ptr())
-    out = (mk1, mk2, sc, valid)
-    return out + (ij,) if return_indices else out
+           MI_SOLVER_DOTS_BELOW_1024 if dots_below_1024 else 0, rec.data_ptr(), valid.data_ptr(), ij.data_ptr(),
+           N.stream_ptr())
+    return _mnn_record_views(rec, valid, ij, return_indices)
 
 
 # ---- AKAZE (detector/akaze.py) ------------------------------------------------------------------
