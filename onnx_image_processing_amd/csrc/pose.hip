@@ -2,18 +2,17 @@
 // Replaces the host step of reference pytorch_model/vo/pose_estimation.py:53-162 (cv2.findEssentialMat(RANSAC),
 // cv2.recoverPose, cv2.triangulatePoints), one pair at a time there, batched over pairs here.
 //
-// K15a  po_hyp_kernel      grid (ceil(H / 64), pairs), ONE WAVE per workgroup, lane = hypothesis.  The wave compacts the
-//       pair's valid correspondences into LDS once (float4 per correspondence, ballot prefix: index order kept).  Each
-//       lane draws its 8-sample (counter-based hash, header), builds the 8x9 epipolar system on Hartley-normalised points
-//       in LDS -- element (r, c) of lane l at word (r * 9 + c) * 64 + l, so every access of the wave is one bank row,
+// The RANSAC skeleton -- staging, the hypothesis kernel, the first minimum, the mask write-back, the host checks -- is
+// ransac_wave.h's; PoModel below is what K15 supplies to it.
+// K15a  rw_hyp_kernel<PoModel>.  Each lane builds the 8x9 epipolar system of its sample on Hartley-normalised
+//       points in LDS -- element (r, c) of lane l at word (r * 9 + c) * 64 + l, so every access of the wave is one bank row,
 //       conflict-free, and the elimination indexes rows and columns at run time without scratch -- and reduces it by
 //       Gauss-Jordan with complete pivoting (the column permutation is nine nibbles of one 64-bit register).  Null vector,
-//       denormalisation, manifold projection (essential_math.h), then the lane scores its E on every staged
-//       correspondence: LDS broadcast reads, E in registers, a serial sum in index order -- no cross-lane reduction.
-// K15b  po_ransac_kernel   one wave per pair: first minimum of the costs (lanes stride over h, then a (cost, h) butterfly),
-//       then refine_rounds x {inliers of the best E at k_r * threshold -> normal equations (45 sums per lane, lanes stride
-//       over the correspondences, wave_sum_dpp) -> minimum eigenvector by shifted inverse iteration on a Cholesky factor,
-//       every lane redundantly -> denormalise, project -> rescore}; inlier bytes of the best E at `threshold`.
+//       denormalisation, manifold projection (essential_math.h).
+// K15b  po_ransac_kernel   one wave per pair: the best hypothesis, then refine_rounds x {inliers of the best E at k_r *
+//       threshold -> normal equations (45 sums per lane, lanes stride over the correspondences, wave_sum_dpp) -> minimum
+//       eigenvector by shifted inverse iteration on a Cholesky factor, every lane redundantly -> denormalise, project ->
+//       rescore: the float32 truncated sum over all rows, compared in float32}; inlier bytes of the best E at `threshold`.
 // K15c  po_refit_kernel    the refit alone on a caller's mask.
 // K15d  po_pose_kernel     one wave per pair: t from the largest cross product of E's columns, the two rotations
 //       cof(E) -+ [t]x E, four candidates, per-correspondence depths from the two-view linear equations, ballot counts.
@@ -21,43 +20,17 @@
 // fp32 throughout; built with -ffp-contract=off; no atomics; every reduction has a fixed order: bitwise reproducible.
 #include "common.h"
 #include "essential_math.h"
-#include "pose_sampler.h"      // po_mix, po_draw, po_sample_ranks (header: "Sampling")
+#include "ransac_wave.h"       // the skeleton; pose_sampler.h: po_mix, po_draw, po_sample_ranks (header: "Sampling")
 
 #include <math.h>
 
 namespace {
 
 constexpr int PO_MAXN = MI_POSE_MAX_N;
-constexpr int PO_MAXH = MI_POSE_MAX_HYPOTHESES;
-constexpr int PO_MAXR = MI_POSE_MAX_REFINE_ROUNDS;
 constexpr float PO_RANK_TOL = 1e-5f;      // a pivot at or below this fraction of the first pivot: rank-deficient sample
 constexpr int PO_SQUARINGS = 14;          // manifold projection: B^(2^14) in place of 16384 power-iteration steps
 constexpr int PO_INVERSE_ITERS = 6;       // refit: inverse-iteration steps
 constexpr int PO_JACOBI_SWEEPS = 6;       // triangulate: one-sided Jacobi sweeps over the 6 column pairs
-
-// ---- staging: the pair's selected correspondences, compacted in index order (one wave) ---------------------------------------
-struct PoStage {
-  float4 p[PO_MAXN];              // x1, y1, x2, y2
-  unsigned short idx[PO_MAXN];    // the correspondence's index in the caller's arrays
-};
-__device__ __forceinline__ int po_stage(PoStage &S, const float *__restrict__ p1, const float *__restrict__ p2,
-                                        const uint8_t *__restrict__ sel, int n) {
-  const int lane = threadIdx.x & 63;
-  int base = 0;
-  for (int i0 = 0; i0 < n; i0 += 64) {
-    const int i = i0 + lane;
-    const bool v = i < n && (sel ? sel[i] != 0 : true);
-    const unsigned long long mk = __ballot(v);
-    if (v) {
-      const int slot = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-      S.p[slot] = make_float4(p1[2 * i], p1[2 * i + 1], p2[2 * i], p2[2 * i + 1]);
-      S.idx[slot] = (unsigned short)i;
-    }
-    base += (int)__popcll(mk);
-  }
-  __syncthreads();
-  return base;
-}
 
 // squared Sampson distance of one correspondence (header: "Scoring"); +inf where the gradient vanishes
 __host__ __device__ __forceinline__ float po_sampson(const float *e, float4 q) {
@@ -219,52 +192,24 @@ __host__ __device__ inline bool po_solve_minimal(const float4 *q, float *A, floa
   return ok;
 }
 
-// ---- K15a ------------------------------------------------------------------------------------------------------------------
-struct PoHypShared {
-  PoStage st;
-  float a[81 * 64];               // rows 0..7 of the system, row 8: the null vector
+// ---- K15's model (ransac_wave.h) ----------------------------------------------------------------------------------------------
+struct PoModel {
+  using Row = float4;                         // x1, y1, x2, y2
+  static constexpr int MAX_N = PO_MAXN, SAMPLE = 8, MIN_ROWS = 8, FLOATS = 9, STRIDE1 = 2, STRIDE2 = 2;
+  struct HypScratch {
+    float a[81 * 64];                         // rows 0..7 of the system, row 8: the null vector
+  };
+  static __device__ __forceinline__ Row load(const float *__restrict__ p1, const float *__restrict__ p2, int i) {
+    return make_float4(p1[2 * i], p1[2 * i + 1], p2[2 * i], p2[2 * i + 1]);
+  }
+  static __device__ __forceinline__ float *lane_scratch(HypScratch &x) { return x.a + threadIdx.x; }
+  static constexpr auto solve_minimal = po_solve_minimal;      // called as it stands: a wrapper changes K15a's code
+  static __host__ __device__ __forceinline__ float dist2(const float *e, Row q) { return po_sampson(e, q); }
 };
-
-__global__ __launch_bounds__(64) void po_hyp_kernel(const float *__restrict__ pts1, const float *__restrict__ pts2,
-                                                    const uint8_t *__restrict__ valid, int n, int num_hyp, float thr2,
-                                                    uint32_t seed, float *__restrict__ e_h, float *__restrict__ cost_out,
-                                                    int *__restrict__ count_out) {
-  __shared__ PoHypShared S;
-  const int lane = threadIdx.x, b = blockIdx.y, h = blockIdx.x * 64 + lane;
-  const int nv = po_stage(S.st, pts1 + (size_t)b * n * 2, pts2 + (size_t)b * n * 2, valid ? valid + (size_t)b * n : nullptr, n);
-  if (h >= num_hyp) return;                   // no barrier below
-  float e[9];
-  bool ok = nv >= 8;
-  if (ok) {
-    // 8 distinct ranks among the nv valid correspondences
-    int pick[8];
-    po_sample_ranks<8>(seed, (uint32_t)b, (uint32_t)h, nv, pick);
-    float4 q[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) q[s] = S.st.p[pick[s]];
-    ok = po_solve_minimal(q, S.a + lane, e);
-  }
-  float cost = INFINITY;
-  int count = 0;
-  if (ok) {
-    cost = 0.0f;
-    for (int i = 0; i < nv; ++i) {
-      const float d2 = po_sampson(e, S.st.p[i]);                  // the same address in every lane: a broadcast
-      count += d2 <= thr2 ? 1 : 0;
-      cost += fminf(d2, thr2);
-    }
-    if (!(cost < INFINITY)) { ok = false; cost = INFINITY; count = 0; }
-  }
-  const size_t o = (size_t)b * num_hyp + h;
-#pragma unroll
-  for (int c = 0; c < 9; ++c) e_h[o * 9 + c] = ok ? e[c] : 0.0f;
-  cost_out[o] = cost;
-  count_out[o] = count;
-}
+using PoStage = RwStage<PoModel>;
+using PoPairShared = RwPairShared<PoModel>;
 
 // ---- wave-wide pieces of K15b / K15c ----------------------------------------------------------------------------------------
-__device__ __forceinline__ int wave_count(bool p) { return (int)__popcll(__ballot(p)); }
-
 // MSAC cost and inlier count of E over the staged correspondences, lanes striding, fixed reduction order
 __device__ __forceinline__ void po_score_wave(const float *e, const PoStage &S, int nv, float thr2, float &cost, int &count) {
   const int lane = threadIdx.x & 63;
@@ -392,22 +337,6 @@ __device__ bool po_refit_wave(const PoStage &S, int nv, const uint8_t *sel, floa
   return po_finish_e(v, h1, h2, e_out);
 }
 
-// flags by staged rank -> bytes by the caller's index, every one of the n bytes written (one wave)
-__device__ __forceinline__ void po_write_mask(const PoStage &S, int nv, const uint8_t *flag, uint8_t *by_index, int n,
-                                              uint8_t *__restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  for (int i = lane; i < n; i += 64) by_index[i] = 0;
-  __syncthreads();
-  for (int i = lane; i < nv; i += 64) by_index[S.idx[i]] = flag[i];
-  __syncthreads();
-  for (int i = lane; i < n; i += 64) out[i] = by_index[i];
-}
-
-struct PoPairShared {
-  PoStage st;
-  uint8_t sel[PO_MAXN], by_index[PO_MAXN];
-};
-
 // ---- K15b ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void po_ransac_kernel(const float *__restrict__ pts1, const float *__restrict__ pts2,
                                                        const uint8_t *__restrict__ valid, int n, int num_hyp, float thr,
@@ -417,35 +346,18 @@ __global__ __launch_bounds__(64) void po_ransac_kernel(const float *__restrict__
                                                        int *__restrict__ count_out) {
   __shared__ PoPairShared S;
   const int lane = threadIdx.x, b = blockIdx.x;
-  const int nv = po_stage(S.st, pts1 + (size_t)b * n * 2, pts2 + (size_t)b * n * 2, valid ? valid + (size_t)b * n : nullptr, n);
-  // the first minimum of the costs
-  float best = INFINITY;
-  int bh = 0x7fffffff;
-  for (int h = lane; h < num_hyp; h += 64) {
-    const float c = cost_h[(size_t)b * num_hyp + h];
-    if (c < best || (c == best && h < bh)) { best = c; bh = h; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float oc = __shfl_xor(best, o, 64);
-    const int oh = __shfl_xor(bh, o, 64);
-    if (oc < best || (oc == best && oh < bh)) { best = oc; bh = oh; }
-  }
-  if (bh >= num_hyp) { bh = 0; best = INFINITY; }                    // NaN costs only (mi_essential_hypotheses writes none)
+  const int nv = rw_stage(S.st, pts1 + (size_t)b * n * 2, pts2 + (size_t)b * n * 2, valid ? valid + (size_t)b * n : nullptr, n);
   float e[9];
-#pragma unroll
-  for (int c = 0; c < 9; ++c) e[c] = e_h[((size_t)b * num_hyp + bh) * 9 + c];
+  int bh;
+  const bool usable = rw_best_hypothesis<PoModel>(e_h, cost_h, b, num_hyp, e, bh);
   const float thr2 = thr * thr;
-  const bool usable = best < INFINITY;                                // wave-uniform
   if (usable && rounds > 0) {
     float cur;
     int cnt;
     po_score_wave(e, S.st, nv, thr2, cur, cnt);                       // the hypothesis' cost in THIS kernel's summation order
     for (int r = 0; r < rounds; ++r) {
       const float kr = 1.0f + 0.5f * (float)(rounds - 1 - r);
-      const float t2 = (kr * thr) * (kr * thr);
-      for (int i = lane; i < nv; i += 64) S.sel[i] = po_sampson(e, S.st.p[i]) <= t2 ? 1 : 0;
-      __syncthreads();
+      rw_flag_inliers(S, nv, e, (kr * thr) * (kr * thr), true);
       float e2[9], c2;
       int k2;
       const bool ok = po_refit_wave(S.st, nv, S.sel, e2);
@@ -459,11 +371,10 @@ __global__ __launch_bounds__(64) void po_ransac_kernel(const float *__restrict__
       }
     }
   }
-  for (int i = lane; i < nv; i += 64) S.sel[i] = (usable && po_sampson(e, S.st.p[i]) <= thr2) ? 1 : 0;
-  __syncthreads();
+  rw_flag_inliers(S, nv, e, thr2, usable);
   int cnt = 0;
   for (int i0 = 0; i0 < nv; i0 += 64) cnt += wave_count(i0 + lane < nv && S.sel[i0 + lane] != 0);
-  po_write_mask(S.st, nv, S.sel, S.by_index, n, inlier + (size_t)b * n);
+  rw_write_mask(S, nv, n, inlier + (size_t)b * n);
   if (lane == 0) {
 #pragma unroll
     for (int c = 0; c < 9; ++c) e_out[(size_t)b * 9 + c] = e[c];
@@ -478,7 +389,7 @@ __global__ __launch_bounds__(64) void po_refit_kernel(const float *__restrict__ 
                                                       uint8_t *__restrict__ ok_out) {
   __shared__ PoStage S;
   const int b = blockIdx.x;
-  const int nv = po_stage(S, pts1 + (size_t)b * n * 2, pts2 + (size_t)b * n * 2, mask + (size_t)b * n, n);
+  const int nv = rw_stage(S, pts1 + (size_t)b * n * 2, pts2 + (size_t)b * n * 2, mask + (size_t)b * n, n);
   float e[9];
   const bool ok = po_refit_wave(S, nv, nullptr, e);
   if (threadIdx.x == 0) {
@@ -561,7 +472,7 @@ __global__ __launch_bounds__(64) void po_pose_kernel(const float *__restrict__ e
                                                      uint8_t *__restrict__ ok_out) {
   __shared__ PoPairShared S;
   const int lane = threadIdx.x, b = blockIdx.x;
-  const int nv = po_stage(S.st, pts1 + (size_t)b * n * 2, pts2 + (size_t)b * n * 2, mask ? mask + (size_t)b * n : nullptr, n);
+  const int nv = rw_stage(S.st, pts1 + (size_t)b * n * 2, pts2 + (size_t)b * n * 2, mask ? mask + (size_t)b * n : nullptr, n);
   float t[3], rot[2][3][3];
   const bool usable = po_decompose(e_in + (size_t)b * 9, t, rot);   // wave-uniform
   // candidates 0: (Ra, +t)  1: (Rb, +t)  2: (Ra, -t)  3: (Rb, -t); most points in front of both cameras, the first on ties
@@ -583,7 +494,7 @@ __global__ __launch_bounds__(64) void po_pose_kernel(const float *__restrict__ e
     for (int c = 0; c < 3; ++c) rk[r][c] = (best_k & 1) ? rot[1][r][c] : rot[0][r][c];
   for (int i = lane; i < nv; i += 64) S.sel[i] = (usable && po_in_front(rk, tk, S.st.p[i], dist)) ? 1 : 0;
   __syncthreads();
-  po_write_mask(S.st, nv, S.sel, S.by_index, n, pose_mask + (size_t)b * n);
+  rw_write_mask(S, nv, n, pose_mask + (size_t)b * n);
   if (lane == 0) {
     const bool ok = best_cnt >= 5;
     for (int r = 0; r < 3; ++r) {
@@ -682,28 +593,7 @@ __global__ __launch_bounds__(256) void po_triangulate_kernel(const float *__rest
   finite[gid] = ok ? 1 : 0;
 }
 
-int po_shape_status(int batch, int n) {
-  if (batch < 1 || n < 1) return MI_E_SHAPE;
-  if (n > PO_MAXN || batch > 65535) return MI_E_PARAM;
-  return MI_OK;
-}
-
-struct PoWork {
-  float *e_h, *cost;
-  int *count;
-  size_t total;
-};
-PoWork po_carve(void *ws, int batch, int num_hyp) {
-  char *base = static_cast<char *>(ws);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char *q = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
-  PoWork w;
-  w.e_h = reinterpret_cast<float *>(take((size_t)batch * num_hyp * 9 * sizeof(float)));
-  w.cost = reinterpret_cast<float *>(take((size_t)batch * num_hyp * sizeof(float)));
-  w.count = reinterpret_cast<int *>(take((size_t)batch * num_hyp * sizeof(int)));
-  w.total = off;
-  return w;
-}
+int po_shape_status(int batch, int n) { return rw_shape_status(batch, n, PO_MAXN); }
 
 }  // namespace
 
@@ -712,12 +602,9 @@ extern "C" int mi_essential_hypotheses(const float *pts1, const float *pts2, con
                                        int32_t *count, mi_stream_t stream) {
   MI_ENTER();
   if (!pts1 || !pts2 || !e_h || !cost || !count) return MI_E_NULL;
-  if (const int s = po_shape_status(batch, n)) return s;
-  if (num_hypotheses < 1) return MI_E_SHAPE;
-  if (num_hypotheses > PO_MAXH || !(threshold > 0.0f) || !(threshold < INFINITY)) return MI_E_PARAM;
-  hipLaunchKernelGGL(po_hyp_kernel, dim3((unsigned)ceil_div(num_hypotheses, 64), (unsigned)batch), dim3(64), 0,
-                     (hipStream_t)stream, pts1, pts2, valid, n, num_hypotheses, threshold * threshold, seed, e_h, cost, count);
-  return mi_launch_status();
+  if (const int s = rw_hyp_params(batch, n, PO_MAXN, num_hypotheses, threshold)) return s;
+  return rw_launch_hyp<PoModel>(pts1, pts2, valid, batch, n, num_hypotheses, threshold, seed, e_h, cost, count,
+                                (hipStream_t)stream);
 }
 
 extern "C" int mi_essential_refit(const float *pts1, const float *pts2, const uint8_t *mask, int batch, int n, float *e,
@@ -730,8 +617,7 @@ extern "C" int mi_essential_refit(const float *pts1, const float *pts2, const ui
 }
 
 extern "C" size_t mi_essential_ransac_workspace_bytes(int batch, int n, int num_hypotheses) {
-  if (po_shape_status(batch, n) != MI_OK || num_hypotheses < 1 || num_hypotheses > PO_MAXH) return 0;
-  return po_carve(nullptr, batch, num_hypotheses).total;
+  return rw_workspace_bytes(batch, n, PO_MAXN, num_hypotheses, 9);
 }
 
 extern "C" int mi_essential_ransac(const float *pts1, const float *pts2, const uint8_t *valid, int batch, int n,
@@ -740,19 +626,15 @@ extern "C" int mi_essential_ransac(const float *pts1, const float *pts2, const u
                                    size_t workspace_bytes, mi_stream_t stream) {
   MI_ENTER();
   if (!pts1 || !pts2 || !e || !inlier || !best_h || !count || !workspace) return MI_E_NULL;
-  if (const int s = po_shape_status(batch, n)) return s;
-  if (num_hypotheses < 1) return MI_E_SHAPE;
-  if (num_hypotheses > PO_MAXH || !(threshold > 0.0f) || !(threshold < INFINITY)) return MI_E_PARAM;
-  if (refine_rounds < 0 || refine_rounds > PO_MAXR) return MI_E_PARAM;
-  if (((uintptr_t)workspace % 16) != 0) return MI_E_ALIGN;
-  if (workspace_bytes < mi_essential_ransac_workspace_bytes(batch, n, num_hypotheses)) return MI_E_CAPACITY;
-  const PoWork w = po_carve(workspace, batch, num_hypotheses);
+  if (const int s = rw_ransac_params(batch, n, PO_MAXN, num_hypotheses, threshold, refine_rounds, 9, workspace, workspace_bytes))
+    return s;
+  const RwWork w = rw_carve(workspace, batch, num_hypotheses, 9);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(po_hyp_kernel, dim3((unsigned)ceil_div(num_hypotheses, 64), (unsigned)batch), dim3(64), 0, s, pts1, pts2,
-                     valid, n, num_hypotheses, threshold * threshold, seed, w.e_h, w.cost, w.count);
-  MI_CHECK_LAUNCH();
+  if (const int st = rw_launch_hyp<PoModel>(pts1, pts2, valid, batch, n, num_hypotheses, threshold, seed, w.model_h,
+                                            w.cost, w.count, s))
+    return st;
   hipLaunchKernelGGL(po_ransac_kernel, dim3((unsigned)batch), dim3(64), 0, s, pts1, pts2, valid, n, num_hypotheses, threshold,
-                     refine_rounds, w.e_h, w.cost, e, inlier, best_h, count);
+                     refine_rounds, w.model_h, w.cost, e, inlier, best_h, count);
   return mi_launch_status();
 }
 

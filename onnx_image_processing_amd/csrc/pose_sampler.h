@@ -1,5 +1,6 @@
-// The counter-based sampler of the RANSAC kernels (include/mi355x_match.h, "Sampling"), shared by K15 (pose.hip: 8 ranks
-// per hypothesis) and K17 (rigid.hip: 3 ranks).  Integer arithmetic only, callable on the host as well.
+// The counter-based sampler of the RANSAC kernels (include/mi355x_match.h, "Sampling"), called by ransac_wave.h's
+// hypothesis kernel for K15 (pose.hip: 8 ranks per hypothesis), K17 (rigid.hip: 3 ranks) and K23 (pnp.hip: 4 ranks, three
+// rows to solve and one to pick the candidate).  Integer arithmetic only, callable on the host as well.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1125,33 +1125,55 @@ POSE_MAX_N = 2048                          # MI_POSE_MAX_N
 POSE_MAX_REFINE_ROUNDS = 8                 # MI_POSE_MAX_REFINE_ROUNDS
 
 
-def _correspondences(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, what: str):
-    """(B, N, 2) normalised (x, y) points of both views and an optional (B, N) mask, as the C ABI reads them."""
-    q1, q2 = pts1.float().contiguous(), pts2.float().contiguous()
-    if q1.dim() != 3 or q1.shape[-1] != 2 or q1.shape != q2.shape:
-        raise RuntimeError(f"{what}: points must both be (B, N, 2), got {tuple(pts1.shape)} and {tuple(pts2.shape)}")
-    b, n = int(q1.shape[0]), int(q1.shape[1])
-    if not 1 <= n <= POSE_MAX_N:
-        raise RuntimeError(f"{what}: N = {n} correspondences, supported: 1 .. {POSE_MAX_N}")
+def _row_pairs(a: torch.Tensor, b: torch.Tensor, valid: torch.Tensor | None, what: str, widths: tuple, limit: int, names: tuple,
+               rows: str = "rows"):
+    """The two (B, N, widths[i]) float32 arrays of a RANSAC solver and an optional (B, N) mask, as the C ABI reads them."""
+    qa, qb = a.float().contiguous(), b.float().contiguous()
+    if qa.dim() != 3 or qb.dim() != 3 or (qa.shape[-1], qb.shape[-1]) != widths or qa.shape[:2] != qb.shape[:2]:
+        must = f"both be (B, N, {widths[0]})" if widths[0] == widths[1] else f"be (B, N, {widths[0]}) and (B, N, {widths[1]})"
+        raise RuntimeError(f"{what}: points must {must}, got {tuple(a.shape)} and {tuple(b.shape)}")
+    bsz, n = int(qa.shape[0]), int(qa.shape[1])
+    if not 1 <= n <= limit:
+        raise RuntimeError(f"{what}: N = {n} {rows}, supported: 1 .. {limit}")
     v = _validity_bytes(valid)
-    if v is not None and tuple(v.shape) != (b, n):
-        raise RuntimeError(f"{what}: the mask must be ({b}, {n}), got {tuple(v.shape)}")
-    N.dev(q1, F32, "pts1"), N.dev(q2, F32, "pts2")
-    return q1, q2, v, b, n
+    if v is not None and tuple(v.shape) != (bsz, n):
+        raise RuntimeError(f"{what}: the mask must be ({bsz}, {n}), got {tuple(v.shape)}")
+    N.dev(qa, F32, names[0]), N.dev(qb, F32, names[1])
+    return qa, qb, v, bsz, n
+
+
+def _correspondences(pts1, pts2, valid, what: str):
+    """(B, N, 2) normalised (x, y) points of both views"""
+    return _row_pairs(pts1, pts2, valid, what, (2, 2), POSE_MAX_N, ("pts1", "pts2"), "correspondences")
+
+
+def _hypotheses(entry: str, qa: torch.Tensor, qb: torch.Tensor, v, b: int, n: int, num_hypotheses: int, threshold: float,
+                seed: int, floats: tuple):
+    """`mi_*_hypotheses` share one signature: -> (models (B, H, *floats), MSAC cost (B, H) float32, count (B, H) int32)"""
+    h = int(num_hypotheses)
+    m_h = torch.empty((b, h, *floats), dtype=F32, device=qa.device)
+    cost = torch.empty((b, h), dtype=F32, device=qa.device)
+    count = torch.empty((b, h), dtype=I32, device=qa.device)
+    N.call(entry, qa.data_ptr(), qb.data_ptr(), N.dev(v, U8, "valid") if v is not None else None, b, n, h, float(threshold),
+           int(seed) & 0xFFFFFFFF, m_h.data_ptr(), cost.data_ptr(), count.data_ptr(), N.stream_ptr())
+    return m_h, cost, count
+
+
+def _ransac_workspace(entry: str, what: str, b: int, n: int, num_hypotheses: int, device):
+    """(H, the workspace `mi_*_ransac` wants as an int64 tensor, its size in bytes)"""
+    h = int(num_hypotheses)
+    wbytes = int(getattr(N.load(), entry)(b, n, h))
+    if wbytes == 0:
+        raise RuntimeError(f"{what}: unsupported request (batch {b}, N {n}, {h} hypotheses)")
+    return h, torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=device), wbytes
 
 
 def essential_hypotheses(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, num_hypotheses: int,
                          threshold: float, seed: int = 0):
     """`mi_essential_hypotheses`: H 8-point hypotheses per pair from the counter-based sampler, each scored on every valid
     correspondence -> (E_h (B, H, 3, 3), MSAC cost (B, H) float32, inlier count (B, H) int32)."""
-    q1, q2, v, b, n = _correspondences(pts1, pts2, valid, "essential_hypotheses")
-    h = int(num_hypotheses)
-    e_h = torch.empty((b, h, 3, 3), dtype=F32, device=q1.device)
-    cost = torch.empty((b, h), dtype=F32, device=q1.device)
-    count = torch.empty((b, h), dtype=I32, device=q1.device)
-    N.call("mi_essential_hypotheses", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "valid") if v is not None else None, b, n, h,
-           float(threshold), int(seed) & 0xFFFFFFFF, e_h.data_ptr(), cost.data_ptr(), count.data_ptr(), N.stream_ptr())
-    return e_h, cost, count
+    return _hypotheses("mi_essential_hypotheses", *_correspondences(pts1, pts2, valid, "essential_hypotheses"), num_hypotheses,
+                       threshold, seed, (3, 3))
 
 
 def essential_refit(pts1: torch.Tensor, pts2: torch.Tensor, mask: torch.Tensor):
@@ -1171,11 +1193,7 @@ def essential_ransac(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor
     """`mi_essential_ransac`: hypotheses, MSAC selection and refine_rounds rounds of refit-and-rescore in two launches ->
     (E (B, 3, 3), inlier (B, N) bool, best_h (B,) int32, count (B,) int32)."""
     q1, q2, v, b, n = _correspondences(pts1, pts2, valid, "essential_ransac")
-    h = int(num_hypotheses)
-    wbytes = int(N.load().mi_essential_ransac_workspace_bytes(b, n, h))
-    if wbytes == 0:
-        raise RuntimeError(f"essential_ransac: unsupported request (batch {b}, N {n}, {h} hypotheses)")
-    work = torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=q1.device)
+    h, work, wbytes = _ransac_workspace("mi_essential_ransac_workspace_bytes", "essential_ransac", b, n, num_hypotheses, q1.device)
     e = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
     inlier = torch.empty((b, n), dtype=U8, device=q1.device)
     best_h = torch.empty((b,), dtype=I32, device=q1.device)
@@ -1260,33 +1278,17 @@ def lift_keypoints(keypoints: torch.Tensor, depth: torch.Tensor, k_inv: torch.Te
     return pts, ok.view(torch.bool)
 
 
-def _point_pairs(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, what: str):
-    """(B, N, 3) points of both frames and an optional (B, N) mask, as the C ABI reads them."""
-    q1, q2 = pts1.float().contiguous(), pts2.float().contiguous()
-    if q1.dim() != 3 or q1.shape[-1] != 3 or q1.shape != q2.shape:
-        raise RuntimeError(f"{what}: points must both be (B, N, 3), got {tuple(pts1.shape)} and {tuple(pts2.shape)}")
-    b, n = int(q1.shape[0]), int(q1.shape[1])
-    if not 1 <= n <= RIGID_MAX_N:
-        raise RuntimeError(f"{what}: N = {n} rows, supported: 1 .. {RIGID_MAX_N}")
-    v = _validity_bytes(valid)
-    if v is not None and tuple(v.shape) != (b, n):
-        raise RuntimeError(f"{what}: the mask must be ({b}, {n}), got {tuple(v.shape)}")
-    N.dev(q1, F32, "pts1"), N.dev(q2, F32, "pts2")
-    return q1, q2, v, b, n
+def _point_pairs(pts1, pts2, valid, what: str):
+    """(B, N, 3) points of both frames"""
+    return _row_pairs(pts1, pts2, valid, what, (3, 3), RIGID_MAX_N, ("pts1", "pts2"))
 
 
 def rigid_hypotheses(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, num_hypotheses: int,
                      threshold: float, seed: int = 0):
     """`mi_rigid_hypotheses`: H 3-point rigid motions per pair from the counter-based sampler, each scored on every valid
     row -> (rt_h (B, H, 12): R row-major then t, MSAC cost (B, H) float32, inlier count (B, H) int32)."""
-    q1, q2, v, b, n = _point_pairs(pts1, pts2, valid, "rigid_hypotheses")
-    h = int(num_hypotheses)
-    rt_h = torch.empty((b, h, 12), dtype=F32, device=q1.device)
-    cost = torch.empty((b, h), dtype=F32, device=q1.device)
-    count = torch.empty((b, h), dtype=I32, device=q1.device)
-    N.call("mi_rigid_hypotheses", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "valid") if v is not None else None, b, n, h,
-           float(threshold), int(seed) & 0xFFFFFFFF, rt_h.data_ptr(), cost.data_ptr(), count.data_ptr(), N.stream_ptr())
-    return rt_h, cost, count
+    return _hypotheses("mi_rigid_hypotheses", *_point_pairs(pts1, pts2, valid, "rigid_hypotheses"), num_hypotheses, threshold, seed,
+                       (12,))
 
 
 def rigid_refit(pts1: torch.Tensor, pts2: torch.Tensor, mask: torch.Tensor):
@@ -1307,11 +1309,7 @@ def rigid_ransac(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | N
     """`mi_rigid_ransac`: hypotheses, MSAC selection and refine_rounds rounds of refit-and-rescore in two launches ->
     (R (B, 3, 3), t (B, 3), inlier (B, N) bool, best_h (B,) int32, count (B,) int32, rmse (B,) float32, ok (B,) bool)."""
     q1, q2, v, b, n = _point_pairs(pts1, pts2, valid, "rigid_ransac")
-    h = int(num_hypotheses)
-    wbytes = int(N.load().mi_rigid_ransac_workspace_bytes(b, n, h))
-    if wbytes == 0:
-        raise RuntimeError(f"rigid_ransac: unsupported request (batch {b}, N {n}, {h} hypotheses)")
-    work = torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=q1.device)
+    h, work, wbytes = _ransac_workspace("mi_rigid_ransac_workspace_bytes", "rigid_ransac", b, n, num_hypotheses, q1.device)
     r = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
     t = torch.empty((b, 3), dtype=F32, device=q1.device)
     inlier = torch.empty((b, n), dtype=U8, device=q1.device)
@@ -1330,19 +1328,9 @@ def rigid_ransac(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | N
 PNP_MAX_N = 2048                           # MI_PNP_MAX_N
 
 
-def _model_matches(pts3: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, what: str):
-    """(B, N, 3) model points, (B, N, 2) normalised (x, y) image points and an optional (B, N) mask, as the C ABI reads them."""
-    q3, q2 = pts3.float().contiguous(), pts2.float().contiguous()
-    if q3.dim() != 3 or q3.shape[-1] != 3 or q2.dim() != 3 or q2.shape[-1] != 2 or q3.shape[:2] != q2.shape[:2]:
-        raise RuntimeError(f"{what}: points must be (B, N, 3) and (B, N, 2), got {tuple(pts3.shape)} and {tuple(pts2.shape)}")
-    b, n = int(q3.shape[0]), int(q3.shape[1])
-    if not 1 <= n <= PNP_MAX_N:
-        raise RuntimeError(f"{what}: N = {n} rows, supported: 1 .. {PNP_MAX_N}")
-    v = _validity_bytes(valid)
-    if v is not None and tuple(v.shape) != (b, n):
-        raise RuntimeError(f"{what}: the mask must be ({b}, {n}), got {tuple(v.shape)}")
-    N.dev(q3, F32, "pts3"), N.dev(q2, F32, "pts2")
-    return q3, q2, v, b, n
+def _model_matches(pts3, pts2, valid, what: str):
+    """(B, N, 3) model points and (B, N, 2) normalised (x, y) image points"""
+    return _row_pairs(pts3, pts2, valid, what, (3, 2), PNP_MAX_N, ("pts3", "pts2"))
 
 
 def pnp_hypotheses(pts3: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, num_hypotheses: int, threshold: float,
@@ -1350,14 +1338,8 @@ def pnp_hypotheses(pts3: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor |
     """`mi_pnp_hypotheses`: H P3P poses per pair from the counter-based sampler (three rows solve, a fourth picks the
     candidate), each scored on every valid row by its reprojection distance in normalised units -> (rt_h (B, H, 12): R
     row-major then t, MSAC cost (B, H) float32, inlier count (B, H) int32)."""
-    q3, q2, v, b, n = _model_matches(pts3, pts2, valid, "pnp_hypotheses")
-    h = int(num_hypotheses)
-    rt_h = torch.empty((b, h, 12), dtype=F32, device=q3.device)
-    cost = torch.empty((b, h), dtype=F32, device=q3.device)
-    count = torch.empty((b, h), dtype=I32, device=q3.device)
-    N.call("mi_pnp_hypotheses", q3.data_ptr(), q2.data_ptr(), N.dev(v, U8, "valid") if v is not None else None, b, n, h,
-           float(threshold), int(seed) & 0xFFFFFFFF, rt_h.data_ptr(), cost.data_ptr(), count.data_ptr(), N.stream_ptr())
-    return rt_h, cost, count
+    return _hypotheses("mi_pnp_hypotheses", *_model_matches(pts3, pts2, valid, "pnp_hypotheses"), num_hypotheses, threshold, seed,
+                       (12,))
 
 
 def pnp_refit(pts3: torch.Tensor, pts2: torch.Tensor, mask: torch.Tensor, r0: torch.Tensor, t0: torch.Tensor):
@@ -1385,11 +1367,7 @@ def pnp_ransac(pts3: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | Non
     (R (B, 3, 3), t (B, 3), inlier (B, N) bool, best_h (B,) int32, count (B,) int32, rmse (B,) float32 in normalised units,
     info (B, 6, 6) float32, ok (B,) bool)."""
     q3, q2, v, b, n = _model_matches(pts3, pts2, valid, "pnp_ransac")
-    h = int(num_hypotheses)
-    wbytes = int(N.load().mi_pnp_ransac_workspace_bytes(b, n, h))
-    if wbytes == 0:
-        raise RuntimeError(f"pnp_ransac: unsupported request (batch {b}, N {n}, {h} hypotheses)")
-    work = torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=q3.device)
+    h, work, wbytes = _ransac_workspace("mi_pnp_ransac_workspace_bytes", "pnp_ransac", b, n, num_hypotheses, q3.device)
     r = torch.empty((b, 3, 3), dtype=F32, device=q3.device)
     t = torch.empty((b, 3), dtype=F32, device=q3.device)
     inlier = torch.empty((b, n), dtype=U8, device=q3.device)
