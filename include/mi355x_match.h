@@ -89,7 +89,8 @@ enum {
                                  kernel of the batched form then reads a uint16 as the fp16 denormal dot * 2^-24 and
                                  multiplies in one mixed-precision instruction instead of converting first; the same
                                  duals bit for bit.  A value >= 1024 under this flag reads as some other fp16: wrong
-                                 duals, no fault. */
+                                 duals, no fault.  The row padding (columns m..pitch) may hold anything, as without the
+                                 flag. */
 };
 /* stream schedules of mi_sinkhorn_dots for >= 64 pairs (see the conventions above) */
 enum {

@@ -194,14 +194,20 @@ __device__ __forceinline__ float mi_z_from_dot(float dot, float2 row, float2 col
 
 // fp32(half(bits of w's low / high 16 bits) * t): one v_fma_mix_f32 (addend +0: the product is never negative here).
 // For a uint16 dot product below 1024 the half is the denormal dot * 2^-24 (sinkhorn_dots.hip, MIX).
+// clamp: the output modifier, free in the instruction.  A product of the contract lies in [0, 1023 * 2^-24 * t] with t a
+// column scale <= 1, far inside the clamp's [0, 1], so every such result is the same bits as without it; what changes is
+// the row PADDING (columns m..pitch of the dots, which no contract fills): a uint16 there that reads as an fp16 infinity
+// or NaN (>= 0x7C00) times the padding's t = 0 was NaN, went through fma(NaN, g, -inf) and v_exp_f32 into the row sum
+// and left every dual of the pair NaN; the clamp returns 0 for NaN (the kernels run with DX10_CLAMP set, the code
+// object's default), the padding's exponent is -inf again and its term 0, as on the converting path.
 __device__ __forceinline__ float mix_mul_lo(uint32_t w, float t) {
   float p;
-  asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel_hi:[1,0,0]" : "=v"(p) : "v"(w), "v"(t));
+  asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel_hi:[1,0,0] clamp" : "=v"(p) : "v"(w), "v"(t));
   return p;
 }
 __device__ __forceinline__ float mix_mul_hi(uint32_t w, float t) {
   float p;
-  asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(p) : "v"(w), "v"(t));
+  asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0] clamp" : "=v"(p) : "v"(w), "v"(t));
   return p;
 }
 

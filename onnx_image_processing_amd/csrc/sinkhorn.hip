@@ -844,10 +844,18 @@ size_t partials_bytes(int batch, int n, int m, int band) {
 
 }  // namespace
 
+// Columns of the padded copy of v: 256 * E4 of the launch_fused<E4, ..> instance that mi_sinkhorn takes (E4 = 1, 2 or 4: there
+// is no three-chunk instance, 512 < m <= 768 runs E4 = 4).  Sized by ceil(m / 256) the copy was 256 floats per pair short
+// for those m, and the lean probability form's column kernel wrote its -inf padding past the end of the workspace.
+static int fused_columns(int m) {
+  const int e4 = ceil_div(m, 256);
+  return 256 * (e4 <= 2 ? e4 : 4);
+}
+
 extern "C" size_t mi_sinkhorn_workspace_bytes(int batch, int n, int m) {
   const int band = fused_rows_per_band(m);
   if (batch <= 0 || n <= 0 || m <= 0 || band == 0) return 0;
-  return partials_bytes(batch, n, m, band) + (size_t)batch * (size_t)(256 * ceil_div(m, 256) + 4) * sizeof(float);
+  return partials_bytes(batch, n, m, band) + (size_t)batch * (size_t)(fused_columns(m) + 4) * sizeof(float);
 }
 
 extern "C" int mi_sinkhorn(const float *z, int batch, int n, int m, int pitch, float dustbin_logscore,
