@@ -1371,6 +1371,123 @@ MI_API int mi_pnp_ransac(const float *pts3, const float *pts2, const uint8_t *va
                          int32_t *best_h, int32_t *count, float *rmse, float *info, uint8_t *ok, void *workspace,
                          size_t workspace_bytes, mi_stream_t stream);
 
+/* ---- planar two-view pose (K24): 2-D to 2-D matches on a plane or under a pure rotation -> homography, pose, model choice ------
+ * K15 solves for E linearly from 8 correspondences.  That system is degenerate when the matched points lie on a plane and
+ * when the camera only rotates; with pixel noise its rank test still passes and K15 returns a confident, wrong pose.  In
+ * both cases the two views are related by a homography x2 ~ H x1, H = R + T N^T for the plane N . X1 = 1 (T in units of the
+ * plane's distance to camera 1; T = 0 for a pure rotation).  The host calls users would reach for are cv2.findHomography
+ * (RANSAC) and cv2.decomposeHomographyMat; the choice between the two models is ORB-SLAM's initialiser's.  Six entries,
+ * batched over pairs, under the contract of the K15 section: pure functions of their arguments, no allocation, no
+ * synchronisation, no memset, one stream, no atomics, every sum in a fixed order (the same inputs and seed give the same
+ * bits), capturable into a hipGraph; outputs and workspace may hold anything on entry and every output element is written;
+ * MI_E_* before any launch.  Points, `valid` / `mask`, n and batch are K15's: (batch, n, 2) float32 NORMALISED (x, y),
+ * 1 <= n <= MI_POSE_MAX_N, batch <= 65535 (MI_E_PARAM beyond; < 1: MI_E_SHAPE); thresholds are in normalised units.
+ *
+ * Divergences from OpenCV, all deliberate: K15's (a fixed number of hypotheses, MSAC, the counter-based sampler, refit
+ * rounds in place of Levenberg-Marquardt), and: the error is the SYMMETRIC transfer error (findHomography scores the
+ * forward error alone); the decomposition is Ma, Soatto, Kosecka and Sastry's ("An Invitation to 3-D Vision", 5.3.3), not
+ * Malis and Vargas'; its four candidates are returned sorted by a depth test instead of unsorted.
+ *
+ * Model.  18 floats: H row-major, then G = adj(H) (G H = det(H) I), negated when det H < 0: a positive multiple of H^-1.
+ *   Both are scaled to unit Frobenius norm, H first, G computed from the scaled H.  Only H is written out.
+ * Sampling.  K15's draw(seed, b, h, s), unchanged (the counter is still 8 h + s), for the slots s = 0 .. 3: four distinct
+ *   ranks, K23's.
+ * Solve.  tri(a, b, c) = (b_x - a_x)(c_y - a_y) - (b_y - a_y)(c_x - a_x).
+ *   1. Refusal: a triple (a, b, c) of points is COLLINEAR under K17's rule, with e1 = b - a, e2 = c - a, when
+ *      (e1 x e2)^2 <= 1e-6 |e1|^2 |e2|^2.  The sample is refused when any of the triples (0,1,2) (0,1,3) (0,2,3) (1,2,3) is
+ *      collinear in either image.
+ *   2. Per image Hartley's rule over the four points: centroid c = (((p0 + p1) + p2) + p3) / 4, scale s = sqrt(2) /
+ *      sqrt(sum |p - c|^2 / 4) (refused when the sum is 0), p^ = (p - c) s, i.e. T = [s 0 -s c_x; 0 s -s c_y; 0 0 1].
+ *   3. Per image the projective basis of the normalised points: [p0 p1 p2] l = p3 by cofactors, l0 = tri(p3, p1, p2),
+ *      l1 = tri(p0, p3, p2), l2 = tri(p0, p1, p3) (the common denominator tri(p0, p1, p2) scales the result and is left
+ *      out); B = [l0 p0, l1 p1, l2 p2] with columns l_k (x_k, y_k, 1).
+ *   4. H^ = B2 adj(B1), row i of adj(B1) being (column i+1) x (column i+2) of B1, indices mod 3; H = T2^-1 H^ T1.
+ *   5. Sign and completion: H is negated when (H X1)_2 < 0 at sample point 0, X1 = (x1, y1, 1); scaled; G as above.
+ *      Refused when det H = 0, when anything is not finite, or when (H X1)_2 > 0 fails at any of the four sample points
+ *      (the sample straddles the line H sends to infinity).
+ * Score.  For every valid row, with (hx, hy, hw) = H X1 and (gx, gy, gw) = G X2, each component (M_j0 x + M_j1 y) + M_j2:
+ *   d^2 = (((x2 - hx / hw)^2 + (y2 - hy / hw)^2) + (x1 - gx / gw)^2) + (y1 - gy / gw)^2, the symmetric transfer error;
+ *   d^2 = +inf when hw <= 0 or gw <= 0.  inlier: d^2 <= thr^2; count = number of inliers, cost = sum over the valid rows in
+ *   index order of min(d^2, thr^2), float32.
+ * Degenerate: fewer than 4 valid rows or a refused sample give cost = +inf, count = 0 and a zero matrix. */
+
+/* H = num_hypotheses hypotheses per pair, generated and scored: h_h (batch, H, 3, 3), cost (batch, H) float32, count
+ * (batch, H) int32.  H < 1: MI_E_SHAPE; H > MI_POSE_MAX_HYPOTHESES, threshold <= 0 or not finite: MI_E_PARAM.  One launch:
+ * ceil(H / 64) x batch waves, a lane per hypothesis, the sample solved in registers. */
+MI_API int mi_homography_hypotheses(const float *pts1, const float *pts2, const uint8_t *valid, int batch, int n,
+                                    int num_hypotheses, float threshold, uint32_t seed, float *h_h, float *cost,
+                                    int32_t *count, mi_stream_t stream);
+
+/* h (batch, 3, 3) from the rows with mask != 0 (mask is required): Hartley's rule over those rows (centroids from
+ * lanes-strided sums, / m for m rows; scale sqrt(2) / sqrt(sum |p - c|^2 / m)); per row, with u = (x1, y1, 1) of the
+ * normalised points, the two DLT lines [u, 0, -x2 u] and [0, u, -y2 u]; the 9x9 normal equations M = A^T A, which consist
+ * of the blocks S0 = sum u u^T (twice on the diagonal), -Sx = -sum x2 u u^T, -Sy = -sum y2 u u^T and Sr = sum (x2^2 + y2^2)
+ * u u^T and are formed from those 24 sums; the eigenvector of M's smallest eigenvalue by K15's inverse iteration
+ * (mi_essential_refit: 6 steps on the Cholesky factor of M + 2e-6 trace(M) I from the all-ones vector; one code) = H^
+ * row-major; H = T2^-1 H^ T1; negated when (H X1)_2 < 0 at the centroid of the first image's rows; completed as in Solve 5.
+ * ok (batch) bytes: 0 and a zero h for fewer than 4 rows, a point set without spread, det H = 0 or a non-finite result,
+ * else 1.  One wave per pair. */
+MI_API int mi_homography_refit(const float *pts1, const float *pts2, const uint8_t *mask, int batch, int n, float *h,
+                               uint8_t *ok, mi_stream_t stream);
+
+/* The whole estimator, K17's point for point: mi_homography_hypotheses into the workspace, then per pair the hypothesis of
+ * minimum cost (the lowest h among equals; h = 0 when every cost is +inf) and refine_rounds rounds r = 0 .. R-1 of local
+ * optimisation: take the inliers of the best model so far at k_r * threshold, k_r = 1 + (R - 1 - r) / 2, refit as
+ * mi_homography_refit, score at `threshold`; the refit replaces the best model only when its cost is strictly lower, costs
+ * held as (rows beyond the threshold, float32 sum of the inliers' d^2, summed lanes-strided) and compared as k thr^2 + s in
+ * float64, the hypothesis' own cost re-formed that way first (K17 says why).  A round whose refit is not ok changes nothing.
+ * h (batch, 3, 3); inlier (batch, n) bytes: d^2 <= threshold^2 under the model, 0 for rows that are not valid; best_h
+ * (batch) the selected hypothesis; count (batch) = number of inlier bytes set; cost (batch) float32 = the final model's MSAC
+ * cost over the valid rows, k thr^2 + s of the paragraph above rounded to float32.  A pair without a usable hypothesis
+ * gives a zero h, no inliers, count 0 and cost = +inf.  With refine_rounds = 0, h / count / inlier are exactly those of
+ * hypothesis best_h of mi_homography_hypotheses.
+ * 0 <= refine_rounds <= MI_POSE_MAX_REFINE_ROUNDS (MI_E_PARAM).  workspace: mi_homography_ransac_workspace_bytes(batch, n,
+ * H) bytes (0 for an unsupported request), 16-byte aligned (MI_E_ALIGN), any content; shorter: MI_E_CAPACITY.  Two launches. */
+MI_API size_t mi_homography_ransac_workspace_bytes(int batch, int n, int num_hypotheses);
+MI_API int mi_homography_ransac(const float *pts1, const float *pts2, const uint8_t *valid, int batch, int n,
+                                int num_hypotheses, float threshold, int refine_rounds, uint32_t seed, float *h,
+                                uint8_t *inlier, int32_t *best_h, int32_t *count, float *cost, void *workspace,
+                                size_t workspace_bytes, mi_stream_t stream);
+
+/* cv2.decomposeHomographyMat for normalised points, with the candidates tested and sorted: from h (batch, 3, 3; any scale
+ * and sign) and the rows with mask != 0 (NULL: every row), four candidates per pair: r (batch, 4, 3, 3), t (batch, 4, 3),
+ * normal (batch, 4, 3), count (batch, 4) int32, with x2 ~ (r + t normal^T) x1.  t is T in units of the plane's distance to
+ * camera 1 (NOT of unit length); normal is of unit length and points from camera 1 towards the plane.
+ *   1. H is scaled to unit Frobenius norm and negated when X2^T H X1 > 0 holds on fewer than half of the masked rows.
+ *   2. The eigen-decomposition of H^T H by K17's cyclic Jacobi (6 sweeps, pairs (0,1) (0,2) (1,2)); eigenvalues sorted
+ *      w1 >= w2 >= w3 (the lower index first among equals) with unit eigenvectors v1, v2, v3, each negated when its
+ *      component of largest magnitude (the first among equals) is negative.  H is divided by sqrt(w2), the w by w2.
+ *   3. u+- = (sqrt(1 - w3) v1 +- sqrt(w1 - 1) v3) / sqrt(w1 - w3) (a negative radicand counts as 0); N = v2 x u;
+ *      U = [v2, u, N], W = [H v2, H u, H v2 x H u] (columns); R = W U^T followed by one step R (3 I - R^T R) / 2 towards
+ *      the nearest rotation, as in mi_recover_pose; T = (H - R) N.  Candidates: 0 (R+, T+, N+), 1 (R-, T-, N-),
+ *      2 (R+, -T+, -N+), 3 (R-, -T-, -N-).
+ *   4. A masked row PASSES under a candidate when N . X1 > 0 and ((R X1)_2 / (N . X1)) + T_2 > 0: its depths in the two
+ *      cameras, in units of the plane's distance, are positive.
+ *   5. The candidates are written sorted by passing count, descending; equal counts by the larger trace of R, then by
+ *      candidate index.  count holds the passing counts; pose_mask (batch, n) the rows that pass under slot 0.  Two
+ *      candidates generally pass every row of a plane in front of both cameras; which of them is the scene's cannot be
+ *      told from one pair.
+ *   6. rotation_only (batch) bytes: 1 when w1 - w3 <= 5.9e-6 (HG_ROTATION_TOL, csrc/homography_math.h, where its
+ *      measurement is written down).  Slot 0 is then (H (H^T H)^(-1/2) through the eigen-decomposition, followed by the
+ *      step of 3; t = 0; normal = 0) with every masked row passing, and slots 1 .. 3 are copies of it.
+ *   7. ok (batch) bytes: 0 when slot 0 passes fewer than 4 rows or h is zero or not finite; then every r is the identity
+ *      and t, normal, count, pose_mask and rotation_only are zero.
+ * One wave per pair. */
+MI_API int mi_homography_pose(const float *h, const float *pts1, const float *pts2, const uint8_t *mask, int batch, int n,
+                              float *r, float *t, float *normal, int32_t *count, uint8_t *pose_mask, uint8_t *rotation_only,
+                              uint8_t *ok, mi_stream_t stream);
+
+/* The choice between K15's essential matrix e and the homography h (both (batch, 3, 3), any scale) of each pair:
+ * score_M = sum over the valid rows of max(0, 1 - d^2_M / thr_M^2), float32, lanes striding over the rows (lane l sums rows
+ * l, l + 64, .. in order; wave_sum_dpp folds the 64 partial sums), with d^2_E K15's Sampson distance under e and d^2_H the
+ * transfer error of the section above under (h, G = adj(h) sign-matched and scaled to unit Frobenius norm; h is taken as
+ * it comes).  A row with d^2 = +inf adds 0; a zero or singular model scores 0.  score_e, score_h (batch) float32; choice
+ * (batch) bytes: 1 (homography) when score_h > cut * (score_e + score_h), else 0 (also when both scores are 0).
+ * ORB-SLAM's published cut is 0.45.  thr_e, thr_h <= 0 or not finite, cut outside [0, 1]: MI_E_PARAM.  One wave per pair. */
+MI_API int mi_two_view_select(const float *e, const float *h, const float *pts1, const float *pts2, const uint8_t *valid,
+                              int batch, int n, float thr_e, float thr_h, float cut, float *score_e, float *score_h,
+                              uint8_t *choice, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

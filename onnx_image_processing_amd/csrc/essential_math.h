@@ -66,4 +66,67 @@ __host__ __device__ __forceinline__ void em_manifold_from_vectors(const float (*
     for (int c = 0; c < 3; ++c) out[r][c] = (um[r][0] * s_avg) * vm[c][0] + (um[r][1] * s_avg) * vm[c][1];
 }
 
+// squared Sampson distance of one correspondence (header: "Scoring"); +inf where the gradient vanishes.  K15 (pose.hip)
+// scores with it, and K24's model selection (homography.hip) scores E with the same bits.
+__host__ __device__ __forceinline__ float po_sampson(const float *e, float4 q) {
+  const float ex0 = (e[0] * q.x + e[1] * q.y) + e[2], ex1 = (e[3] * q.x + e[4] * q.y) + e[5], ex2 = (e[6] * q.x + e[7] * q.y) + e[8];
+  const float et0 = (e[0] * q.z + e[3] * q.w) + e[6], et1 = (e[1] * q.z + e[4] * q.w) + e[7];
+  const float r = (q.z * ex0 + q.w * ex1) + ex2;
+  const float den = ((ex0 * ex0 + ex1 * ex1) + et0 * et0) + et1 * et1;
+  return den > 0.0f ? (r * r) / den : INFINITY;
+}
+
+// The unit eigenvector v of the smallest eigenvalue of the symmetric positive semi-definite 9x9 matrix mm (the normal
+// equations of K15's and K24's linear refits) by shifted inverse iteration: the Cholesky factor of M + mu I,
+// mu = 2e-6 trace(M) (above the rounding of M's entries, so the factor exists; far below the second smallest eigenvalue
+// of a well-posed set), then EM_INVERSE_ITERS steps from the all-ones vector, each scaled to unit length.
+constexpr int EM_INVERSE_ITERS = 6;
+__host__ __device__ __forceinline__ void em_min_eigenvector9(const float (*mm)[9], float *v) {
+  float tr = 0.0f;
+#pragma unroll
+  for (int r = 0; r < 9; ++r) tr += mm[r][r];
+  const float mu = 2e-6f * tr;
+  float l[9][9];
+#pragma unroll
+  for (int j = 0; j < 9; ++j) {
+    float d = mm[j][j] + mu;
+#pragma unroll
+    for (int k = 0; k < j; ++k) d -= l[j][k] * l[j][k];
+    d = sqrtf(fmaxf(d, 1e-30f));
+    l[j][j] = d;
+#pragma unroll
+    for (int i = j + 1; i < 9; ++i) {
+      float t = mm[i][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) t -= l[i][k] * l[j][k];
+      l[i][j] = t / d;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 9; ++c) v[c] = 1.0f / 3.0f;
+  for (int it = 0; it < EM_INVERSE_ITERS; ++it) {
+    float y[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {                                     // L y = v
+      float t = v[i];
+#pragma unroll
+      for (int k = 0; k < i; ++k) t -= l[i][k] * y[k];
+      y[i] = t / l[i][i];
+    }
+#pragma unroll
+    for (int i = 8; i >= 0; --i) {                                    // L^T x = y
+      float t = y[i];
+#pragma unroll
+      for (int k = i + 1; k < 9; ++k) t -= l[k][i] * v[k];
+      v[i] = t / l[i][i];
+    }
+    float nn = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) nn += v[c] * v[c];
+    nn = sqrtf(nn);
+#pragma unroll
+    for (int c = 0; c < 9; ++c) v[c] = v[c] / nn;
+  }
+}
+
 }  // namespace

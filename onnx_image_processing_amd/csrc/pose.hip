@@ -29,17 +29,9 @@ namespace {
 constexpr int PO_MAXN = MI_POSE_MAX_N;
 constexpr float PO_RANK_TOL = 1e-5f;      // a pivot at or below this fraction of the first pivot: rank-deficient sample
 constexpr int PO_SQUARINGS = 14;          // manifold projection: B^(2^14) in place of 16384 power-iteration steps
-constexpr int PO_INVERSE_ITERS = 6;       // refit: inverse-iteration steps
 constexpr int PO_JACOBI_SWEEPS = 6;       // triangulate: one-sided Jacobi sweeps over the 6 column pairs
 
-// squared Sampson distance of one correspondence (header: "Scoring"); +inf where the gradient vanishes
-__host__ __device__ __forceinline__ float po_sampson(const float *e, float4 q) {
-  const float ex0 = (e[0] * q.x + e[1] * q.y) + e[2], ex1 = (e[3] * q.x + e[4] * q.y) + e[5], ex2 = (e[6] * q.x + e[7] * q.y) + e[8];
-  const float et0 = (e[0] * q.z + e[3] * q.w) + e[6], et1 = (e[1] * q.z + e[4] * q.w) + e[7];
-  const float r = (q.z * ex0 + q.w * ex1) + ex2;
-  const float den = ((ex0 * ex0 + ex1 * ex1) + et0 * et0) + et1 * et1;
-  return den > 0.0f ? (r * r) / den : INFINITY;
-}
+// po_sampson, the squared Sampson distance of one correspondence (header: "Scoring"), is essential_math.h's
 
 // Hartley parameters -> E = T2^T E_hat T1, then the projection onto singular values (s, s, 0).  v: the null vector
 // (row-major E_hat), h1 / h2: (cx, cy, s) of image 1 / 2.  Returns false when the result is not finite.
@@ -286,54 +278,9 @@ __device__ bool po_refit_wave(const PoStage &S, int nv, const uint8_t *sel, floa
         mm[c][r] = t;
       }
   }
-  // shifted inverse iteration: Cholesky factor of M + mu I, mu = 2e-6 trace(M) (above the rounding of M's entries, so the
-  // factor exists; far below the second smallest eigenvalue of a well-posed set), from the all-ones vector
-  float tr = 0.0f;
-#pragma unroll
-  for (int r = 0; r < 9; ++r) tr += mm[r][r];
-  const float mu = 2e-6f * tr;
-  float l[9][9];
-#pragma unroll
-  for (int j = 0; j < 9; ++j) {
-    float d = mm[j][j] + mu;
-#pragma unroll
-    for (int k = 0; k < j; ++k) d -= l[j][k] * l[j][k];
-    d = sqrtf(fmaxf(d, 1e-30f));
-    l[j][j] = d;
-#pragma unroll
-    for (int i = j + 1; i < 9; ++i) {
-      float t = mm[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) t -= l[i][k] * l[j][k];
-      l[i][j] = t / d;
-    }
-  }
+  // the eigenvector of M's smallest eigenvalue: shifted inverse iteration (essential_math.h, shared with K24's refit)
   float v[9];
-#pragma unroll
-  for (int c = 0; c < 9; ++c) v[c] = 1.0f / 3.0f;
-  for (int it = 0; it < PO_INVERSE_ITERS; ++it) {
-    float y[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {                                     // L y = v
-      float t = v[i];
-#pragma unroll
-      for (int k = 0; k < i; ++k) t -= l[i][k] * y[k];
-      y[i] = t / l[i][i];
-    }
-#pragma unroll
-    for (int i = 8; i >= 0; --i) {                                    // L^T x = y
-      float t = y[i];
-#pragma unroll
-      for (int k = i + 1; k < 9; ++k) t -= l[k][i] * v[k];
-      v[i] = t / l[i][i];
-    }
-    float nn = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 9; ++c) nn += v[c] * v[c];
-    nn = sqrtf(nn);
-#pragma unroll
-    for (int c = 0; c < 9; ++c) v[c] = v[c] / nn;
-  }
+  em_min_eigenvector9(mm, v);
   return po_finish_e(v, h1, h2, e_out);
 }
 

@@ -1,11 +1,13 @@
-// The skeleton of the batched RANSAC solvers (include/mi355x_match.h, "relative pose": the contract the three share), once:
-// K15 (pose.hip), K17 (rigid.hip) and K23 (pnp.hip) supply a model type and their own refit.
+// The skeleton of the batched RANSAC solvers (include/mi355x_match.h, "relative pose": the contract the four share), once:
+// K15 (pose.hip), K17 (rigid.hip), K23 (pnp.hip) and K24 (homography.hip) supply a model type and their own refit.
 //
 // A model M names
 //   Row                      one staged row, and  load(p1, p2, i): row i of the caller's two arrays
 //   STRIDE1, STRIDE2         floats per row of the caller's first / second array
 //   MAX_N, SAMPLE, MIN_ROWS  the stage's capacity, the sample size, the fewest rows a pair can be solved from
-//   FLOATS                   floats per model (9: E; 12: R row-major then t)
+//   FLOATS                   floats per model (9: E; 12: R row-major then t; 18: H then its adjugate G)
+//   STORED, restore(m)       optional: only the first STORED floats of a model go to memory, and restore(m) completes a
+//                            model read back from them (K24: G from H); without them all FLOATS are stored
 //   HypScratch               LDS the minimal solve needs beside the stage (an empty struct: no bytes), and
 //                            lane_scratch(x): the lane's part of it, handed on to
 //   solve_minimal(q, lane's scratch, m), dist2(m, row)
@@ -58,6 +60,12 @@ __device__ __forceinline__ int rw_stage(RwStage<M> &S, const float *__restrict__
   return base;
 }
 
+// floats of a model that go to memory: M::STORED where a model names it, else all M::FLOATS
+template <class M, class = void>
+struct RwStored { static constexpr int value = M::FLOATS; };
+template <class M>
+struct RwStored<M, std::void_t<decltype(M::STORED)>> { static constexpr int value = M::STORED; };
+
 // ---- the hypothesis kernel (K15a, K17a, K23a: rw_hyp_kernel<PoModel>, <RgModel>, <PnpModel>) ------------------------------------
 template <class M>
 struct RwHypShared : RwStage<M>, M::HypScratch {};
@@ -97,7 +105,7 @@ __global__ __launch_bounds__(64) void rw_hyp_kernel(const float *__restrict__ pt
   }
   const size_t o = (size_t)b * num_hyp + h;
 #pragma unroll
-  for (int c = 0; c < M::FLOATS; ++c) m_h[o * M::FLOATS + c] = ok ? m[c] : 0.0f;
+  for (int c = 0; c < RwStored<M>::value; ++c) m_h[o * RwStored<M>::value + c] = ok ? m[c] : 0.0f;
   cost_out[o] = cost;
   count_out[o] = count;
 }
@@ -121,7 +129,8 @@ __device__ __forceinline__ bool rw_best_hypothesis(const float *__restrict__ m_h
   }
   if (bh >= num_hyp) { bh = 0; best = INFINITY; }                    // NaN costs only (the hypothesis kernel writes none)
 #pragma unroll
-  for (int c = 0; c < M::FLOATS; ++c) m[c] = m_h[((size_t)b * num_hyp + bh) * M::FLOATS + c];
+  for (int c = 0; c < RwStored<M>::value; ++c) m[c] = m_h[((size_t)b * num_hyp + bh) * RwStored<M>::value + c];
+  if constexpr (RwStored<M>::value != M::FLOATS) M::restore(m);
   bh_out = bh;
   return best < INFINITY;                                             // wave-uniform
 }

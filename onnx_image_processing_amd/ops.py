@@ -1383,6 +1383,86 @@ def pnp_ransac(pts3: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | Non
     return r, t, inlier.view(torch.bool), best_h, count, rmse, info, ok.view(torch.bool)
 
 
+# ---- K24 planar two-view pose (include/mi355x_match.h, "planar two-view pose") ----------------------------------------------
+
+
+def homography_hypotheses(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, num_hypotheses: int,
+                          threshold: float, seed: int = 0):
+    """`mi_homography_hypotheses`: H 4-point homographies per pair from the counter-based sampler, each scored on every valid
+    correspondence by its symmetric transfer error -> (H_h (B, H, 3, 3), MSAC cost (B, H) float32, inlier count (B, H) int32)."""
+    return _hypotheses("mi_homography_hypotheses", *_correspondences(pts1, pts2, valid, "homography_hypotheses"), num_hypotheses,
+                       threshold, seed, (3, 3))
+
+
+def homography_refit(pts1: torch.Tensor, pts2: torch.Tensor, mask: torch.Tensor):
+    """`mi_homography_refit`: the normalised DLT homography over the masked correspondences -> (H (B, 3, 3), ok (B,) bool)."""
+    q1, q2, v, b, n = _correspondences(pts1, pts2, mask, "homography_refit")
+    if v is None:
+        raise RuntimeError("homography_refit needs a mask")
+    h = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
+    ok = torch.empty((b,), dtype=U8, device=q1.device)
+    N.call("mi_homography_refit", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "mask"), b, n, h.data_ptr(), ok.data_ptr(),
+           N.stream_ptr())
+    return h, ok.view(torch.bool)
+
+
+def homography_ransac(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, num_hypotheses: int,
+                      threshold: float, refine_rounds: int = 3, seed: int = 0):
+    """`mi_homography_ransac`: hypotheses, MSAC selection and refine_rounds rounds of refit-and-rescore in two launches ->
+    (H (B, 3, 3), inlier (B, N) bool, best_h (B,) int32, count (B,) int32, MSAC cost (B,) float32)."""
+    q1, q2, v, b, n = _correspondences(pts1, pts2, valid, "homography_ransac")
+    h, work, wbytes = _ransac_workspace("mi_homography_ransac_workspace_bytes", "homography_ransac", b, n, num_hypotheses,
+                                        q1.device)
+    hm = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
+    inlier = torch.empty((b, n), dtype=U8, device=q1.device)
+    best_h = torch.empty((b,), dtype=I32, device=q1.device)
+    count = torch.empty((b,), dtype=I32, device=q1.device)
+    cost = torch.empty((b,), dtype=F32, device=q1.device)
+    N.call("mi_homography_ransac", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "valid") if v is not None else None, b, n, h,
+           float(threshold), int(refine_rounds), int(seed) & 0xFFFFFFFF, hm.data_ptr(), inlier.data_ptr(), best_h.data_ptr(),
+           count.data_ptr(), cost.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    return hm, inlier.view(torch.bool), best_h, count, cost
+
+
+def homography_pose(h: torch.Tensor, pts1: torch.Tensor, pts2: torch.Tensor, mask: torch.Tensor | None):
+    """`mi_homography_pose`: the four (R, t, normal) candidates of each homography, sorted by the number of masked rows in
+    front of both cameras -> (R (B, 4, 3, 3), t (B, 4, 3) in units of the plane's distance, normal (B, 4, 3), count (B, 4)
+    int32, pose_mask (B, N) bool: the rows passing under slot 0, rotation_only (B,) bool, ok (B,) bool)."""
+    q1, q2, v, b, n = _correspondences(pts1, pts2, mask, "homography_pose")
+    hh = h.float().contiguous()
+    if tuple(hh.shape) != (b, 3, 3):
+        raise RuntimeError(f"homography_pose: H must be ({b}, 3, 3), got {tuple(h.shape)}")
+    r = torch.empty((b, 4, 3, 3), dtype=F32, device=q1.device)
+    t = torch.empty((b, 4, 3), dtype=F32, device=q1.device)
+    normal = torch.empty((b, 4, 3), dtype=F32, device=q1.device)
+    count = torch.empty((b, 4), dtype=I32, device=q1.device)
+    pose_mask = torch.empty((b, n), dtype=U8, device=q1.device)
+    rot = torch.empty((b,), dtype=U8, device=q1.device)
+    ok = torch.empty((b,), dtype=U8, device=q1.device)
+    N.call("mi_homography_pose", N.dev(hh, F32, "H"), q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "mask") if v is not None else None,
+           b, n, r.data_ptr(), t.data_ptr(), normal.data_ptr(), count.data_ptr(), pose_mask.data_ptr(), rot.data_ptr(),
+           ok.data_ptr(), N.stream_ptr())
+    return r, t, normal, count, pose_mask.view(torch.bool), rot.view(torch.bool), ok.view(torch.bool)
+
+
+def two_view_select(e: torch.Tensor, h: torch.Tensor, pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None,
+                    threshold_e: float, threshold_h: float, cut: float = 0.45):
+    """`mi_two_view_select`: the truncated-residual scores of an essential matrix and a homography on the valid
+    correspondences and the choice between them -> (score_e (B,) float32, score_h (B,) float32, choice (B,) bool: True for
+    the homography, score_h > cut * (score_e + score_h))."""
+    q1, q2, v, b, n = _correspondences(pts1, pts2, valid, "two_view_select")
+    ee, hh = e.float().contiguous(), h.float().contiguous()
+    if tuple(ee.shape) != (b, 3, 3) or tuple(hh.shape) != (b, 3, 3):
+        raise RuntimeError(f"two_view_select: E and H must be ({b}, 3, 3), got {tuple(e.shape)} and {tuple(h.shape)}")
+    se = torch.empty((b,), dtype=F32, device=q1.device)
+    sh = torch.empty((b,), dtype=F32, device=q1.device)
+    choice = torch.empty((b,), dtype=U8, device=q1.device)
+    N.call("mi_two_view_select", N.dev(ee, F32, "E"), N.dev(hh, F32, "H"), q1.data_ptr(), q2.data_ptr(),
+           N.dev(v, U8, "valid") if v is not None else None, b, n, float(threshold_e), float(threshold_h), float(cut),
+           se.data_ptr(), sh.data_ptr(), choice.data_ptr(), N.stream_ptr())
+    return se, sh, choice.view(torch.bool)
+
+
 # ---- K18 dense RGB-D refinement (include/mi355x_match.h, "dense RGB-D refinement") ------------------------------------------
 
 ICP_MAX_STAGES = 4                         # MI_ICP_MAX_STAGES

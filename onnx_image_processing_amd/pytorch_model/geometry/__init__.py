@@ -3,9 +3,10 @@ from .dense_rgbd import DenseRgbdRefiner
 from .direct_rgbd import DirectRgbdRefiner
 from .direct_tsdf_volume import DirectTsdfVolume
 from .essential_matrix_estimator import EssentialMatrixEstimator
+from .planar_pose import HomographyEstimator, PlanarPoseEstimator, TwoViewPoseEstimator
 from .relative_pose import RelativePoseEstimator, triangulate_points
 from .rgbd_pose import RgbdPoseEstimator
 from .tsdf_volume import TsdfVolume
 
-__all__ = ["AbsolutePoseEstimator", "DenseRgbdRefiner", "DirectRgbdRefiner", "DirectTsdfVolume", "EssentialMatrixEstimator", "RelativePoseEstimator", "RgbdPoseEstimator",
-           "TsdfVolume", "triangulate_points"]
+__all__ = ["AbsolutePoseEstimator", "DenseRgbdRefiner", "DirectRgbdRefiner", "DirectTsdfVolume", "EssentialMatrixEstimator", "HomographyEstimator",
+           "PlanarPoseEstimator", "RelativePoseEstimator", "RgbdPoseEstimator", "TsdfVolume", "TwoViewPoseEstimator", "triangulate_points"]

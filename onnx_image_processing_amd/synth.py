@@ -233,6 +233,50 @@ def synth_two_view(seed: int, n: int, outlier_fraction: float, noise_px: float, 
     return (px1[:, ::-1].astype(np.float32), px2[:, ::-1].astype(np.float32), R, t, inlier)
 
 
+def synth_planar_two_view(seed: int, n: int, outlier_fraction: float, noise_px: float, baseline: float = 0.4, f: float = 500.0):
+    """synth_two_view's scene with every point on ONE PLANE, for the homography kernels: (keypoints1, keypoints2, R, t,
+    normal, distance, inlier).  The same hashed draws as synth_two_view (x and y of the points, the rotation, the
+    translation's direction, the noise, the outliers); the depth of a point is not drawn but follows from the plane
+    normal . X = distance through (0, 0, 5), whose unit normal is (0, 0, 1) tilted by a hashed angle of up to 20 degrees
+    about a hashed axis in the image plane.  t (3,) float64 is the whole translation, `baseline` times the unit direction
+    (synth_two_view returns the direction alone): x2 ~ (R + t normal^T / distance) x1 for the planted inliers.
+    baseline = 0 gives the rotation-only scene (t = 0)."""
+    idx = np.arange(n, dtype=np.uint64)
+
+    def uni(salt, count=n):
+        i = np.arange(count, dtype=np.uint64)
+        return ((_hash3(seed, i, np.uint64(salt) + 0 * i, 21) >> np.uint64(11)).astype(np.float64) + 0.5) / float(1 << 53)
+
+    def normal_draw(salt, count=n):
+        return np.sqrt(-2.0 * np.log(uni(salt, count))) * np.cos(2.0 * np.pi * uni(salt + 1, count))
+
+    tilt, phi = np.deg2rad(20.0) * uni(19, 1)[0], 2.0 * np.pi * uni(20, 1)[0]
+    nrm = np.array([np.sin(tilt) * np.cos(phi), np.sin(tilt) * np.sin(phi), np.cos(tilt)])
+    dist = 5.0 * nrm[2]
+    x, y = -2.0 + 4.0 * uni(0), -1.5 + 3.0 * uni(1)
+    pts = np.stack([x, y, (dist - nrm[0] * x - nrm[1] * y) / nrm[2]], axis=1)
+    w = 0.08 * normal_draw(3, 3)
+    th = float(np.linalg.norm(w))
+    k = w / th if th > 0 else np.array([0.0, 0.0, 1.0])
+    kx = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    R = np.eye(3) + np.sin(th) * kx + (1.0 - np.cos(th)) * (kx @ kx)
+    d = normal_draw(5, 3)
+    t = float(baseline) * d / np.linalg.norm(d)
+    K = two_view_camera(f)
+    x2 = pts @ R.T + t
+    px1 = (pts / pts[:, 2:]) @ K.T
+    px2 = (x2 / x2[:, 2:]) @ K.T
+    px1 = px1[:, :2] + noise_px * np.stack([normal_draw(7), normal_draw(9)], axis=1)
+    px2 = px2[:, :2] + noise_px * np.stack([normal_draw(11), normal_draw(13)], axis=1)
+    n_out = int(round(outlier_fraction * n))
+    order = np.argsort(_hash3(seed, idx, np.uint64(15) + 0 * idx, 21), kind="stable")
+    inlier = np.ones(n, dtype=bool)
+    inlier[order[:n_out]] = False
+    rand_px = np.stack([TWO_VIEW_IMAGE[1] * uni(16), TWO_VIEW_IMAGE[0] * uni(17)], axis=1)
+    px2[~inlier] = rand_px[~inlier]
+    return (px1[:, ::-1].astype(np.float32), px2[:, ::-1].astype(np.float32), R, t, nrm, dist, inlier)
+
+
 RGBD_BASELINE = 0.4                   # metres between the two views of synth_rgbd_pair
 
 
