@@ -113,7 +113,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   // integer coordinates inside the image: the 32x32 replicate-clamped window [k-16, k+15] holds every
   // box (a clamped centre only moves towards the keypoint).  >= 15 px from the border no centre is
   // clamped and the precomputed corner offsets apply; closer, the corners are computed per pair.
-  const bool onpixel = ky == floorf(ky) && kx == floorf(kx) && ky <= (float)(h - 1) && kx <= (float)(w - 1);
+  // (kx < 0 is a VALID keypoint -- validity is ky's alone -- whose x the reference clamps to 0 first, bad.py:464-465:
+  // the general kernel does that; here the border branch would centre its boxes on clamp(kx + offset) instead)
+  const bool onpixel = ky == floorf(ky) && kx == floorf(kx) && kx >= 0.0f && ky <= (float)(h - 1) && kx <= (float)(w - 1);
   if (!onpixel) {
     if (lane == 0) status[flat] = 0;
     return;

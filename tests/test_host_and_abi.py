@@ -272,6 +272,14 @@ def test_argument_validation_of_the_widened_entries(lib_path):
     assert lib.mi_sparse_bad_oriented(p, 1, 64, 64, p, 4, p, p, p, p, 256, 2, 10.0, 1, 0, 0.0, p, None, None, None) == -1   # two angle sources
     assert lib.mi_sparse_bad_oriented(p, 1, 64, 64, p, 4, p, None, p, p, 100, 2, 10.0, 1, 0, 0.0, p, None, None, None) == -3  # pairs % 64
     assert lib.mi_sparse_bad_oriented(p, 1, 64, 64, p, 4, p, None, p, p, 256, 2, 10.0, 1, 0, -1.0, p, None, None, None) == -3  # negative reach
+    assert lib.mi_sparse_bad_oriented(p, 1, 64, 64, p, 4, None, None, p, p, 256, 2, 10.0, 1, 0, 0.0, p, None, None, None) == -1   # no angle source
+    for pairs in (0, 96, 1088):                                                                     # 64, 128, ..., 1024 only
+        assert lib.mi_sparse_bad_oriented(p, 1, 64, 64, p, 4, p, None, p, p, pairs, 2, 10.0, 1, 0, 0.0, p, None, None, None) == -3
+    for mode in (0, 1):                                                                             # packed bits are the hard mode's
+        assert lib.mi_sparse_bad_oriented(p, 1, 64, 64, p, 4, p, None, p, p, 256, mode, 10.0, 1, 0, 0.0, p, p, None, None) == -3
+    lib.mi_sparse_bad_oriented_pair.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, ci, ci, cf, ci, ci, cf, vp, vp, vp, vp]
+    assert lib.mi_sparse_bad_oriented_pair(p, p, 1, 64, 64, p, 4, None, p, p, 256, 2, 10.0, 1, 0, 0.0, p, None, None, None) == -1  # no angles
+    assert lib.mi_sparse_bad_oriented_pair(p, p, 1, 64, 64, p, 4, p, p, p, 1088, 2, 10.0, 1, 0, 0.0, p, None, None, None) == -3
 
 
 def test_match_pairs_host_side_checks(lib_path):
@@ -472,6 +480,20 @@ def test_argument_validation_of_the_round2_entries(lib_path):
     lib.mi_sparse_bad_u8.argtypes = [vp, ci, ci, ci, vp, ci, vp, vp, ci, ci, cf, ci, vp, vp, vp, vp, vp]
     assert lib.mi_sparse_bad_u8(p, 1, 64, 64, p, 4, p, p, 100, 2, 0.0, 1, p, None, None, None, None) == -3   # pairs % 64
     assert lib.mi_sparse_bad_u8(p, 1, 64, 64, p, 4, p, p, 256, 0, 0.0, 1, p, p, None, None, None) == -3     # bits need HARD
+    lib.mi_sparse_bad.argtypes = lib.mi_sparse_bad_u8.argtypes
+    lib.mi_sparse_bad_pair.argtypes = [vp, vp, ci, ci, ci, ci, vp, ci, vp, vp, ci, ci, cf, ci, vp, vp, vp, vp, vp]
+    lib.mi_bad_plan_build.argtypes = [vp, vp, ci, vp, vp]
+    for pairs in (0, 96, 1088):                                    # num_pairs: 64, 128, ..., 1024 and nothing else
+        assert lib.mi_sparse_bad(p, 1, 64, 64, p, 4, p, p, pairs, 2, 0.0, 1, p, None, None, None, None) == -3
+        assert lib.mi_sparse_bad_u8(p, 1, 64, 64, p, 4, p, p, pairs, 2, 0.0, 1, p, None, None, None, None) == -3
+        assert lib.mi_sparse_bad_pair(p, p, 0, 1, 64, 64, p, 4, p, p, pairs, 2, 0.0, 1, p, None, None, None, None) == -3
+        assert lib.mi_bad_plan_build(p, p, pairs, p, None) == -3
+    for mode in (0, 1):                                            # packed bits exist in the hard mode only
+        assert lib.mi_sparse_bad(p, 1, 64, 64, p, 4, p, p, 256, mode, 0.0, 1, p, p, None, None, None) == -3
+        assert lib.mi_sparse_bad_pair(p, p, 0, 1, 64, 64, p, 4, p, p, 256, mode, 0.0, 1, None, p, None, None, None) == -3
+    aligned = (p.value + 15) & ~15
+    for off in (4, 8):                                             # the plan holds uint4 rows: 16-byte alignment
+        assert lib.mi_bad_plan_build(p, p, 256, ctypes.c_void_p(aligned + off), None) == -5
     lib.mi_match_filter_masks.argtypes = [vp, ci, ci, ci, ci, cf, cf, vp, vp]
     assert lib.mi_match_filter_masks(p, 1, 4, 4, 0, 2.0, 0.3, p, None) == -3        # a margin test needs the dustbin column
     assert lib.mi_match_filter_masks(None, 1, 4, 4, 1, 2.0, 0.3, p, None) == -1
