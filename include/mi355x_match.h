@@ -1488,6 +1488,93 @@ MI_API int mi_two_view_select(const float *e, const float *h, const float *pts1,
                               int batch, int n, float thr_e, float thr_h, float cut, float *score_e, float *score_h,
                               uint8_t *choice, mi_stream_t stream);
 
+/* ---- windowed bundle adjustment (K25): the poses of a window of frames and their shared landmarks, refined jointly -------------
+ * Every pose of the sections above comes from two frames.  This section couples them: Levenberg-Marquardt on the
+ * reprojection error of a window, the landmarks eliminated (Schur complement), `batch` independent windows per call, one
+ * workgroup each.  The host calls users would reach for are g2o, Ceres or cv2.detail.BundleAdjusterReproj.  Four entries
+ * under the contract of the K15 / K23 sections: pure functions of their arguments, no allocation, no synchronisation, no
+ * memset, one stream, no atomics, every sum in a fixed order (the same inputs give the same bits, alone or inside a batch),
+ * capturable into a hipGraph; outputs and workspace may hold anything on entry, every output element is written and outputs
+ * alias nothing; MI_E_* before any launch.
+ *
+ * State.  F frames with poses r (batch, F, 3, 3), t (batch, F, 3), X_c = R X + t (K23's convention), and L landmarks points
+ *   (batch, L, 3) in the model frame, all float32.  Observations: obs (batch, F, L, 2) float32 NORMALISED (u, v) as
+ *   mi_normalise_keypoints writes them, vis (batch, F, L) bytes, non-zero = seen; an entry that is not seen is never read for
+ *   its coordinates.  2 <= F <= MI_BA_MAX_FRAMES, 1 <= L <= MI_BA_MAX_LANDMARKS (below: MI_E_SHAPE, as batch < 1; above:
+ *   MI_E_PARAM, as batch > 65535).  Frames 0 .. num_fixed - 1 are held (the gauge: 1 for metric input, 2 to pin a monocular
+ *   scale, F for structure only); num_fixed outside 1 .. F: MI_E_PARAM.  huber < 0 or not finite: MI_E_PARAM.
+ * Active.  A landmark is ACTIVE when at least 2 of its F vis bytes are set -- a function of vis alone.  An inactive landmark
+ *   adds nothing anywhere and is returned unchanged.  "Observation" below means a seen entry of an active landmark.
+ * Threads.  256 per window.  Thread tid owns the landmarks l = tid, tid + 256, ...  A sum "over the landmarks" is: each
+ *   thread's float32 partial sum over its landmarks in that order, wave_sum_dpp over the 64 lanes of each wave, then the four
+ *   waves' sums added in wave order in float64 starting from 0.
+ * Residual (float32).  (x, y, z), d^2 = e2 of K23's Score; an observation with z <= 0 or a non-finite e2 has e2 = +inf.
+ *   e = sqrt(e2).  With huber > 0 and e > huber: rho = (2 huber) e - huber huber and w = huber / e; otherwise rho = e2, w = 1.
+ *   rho = +inf where e2 = +inf.
+ * Cost.  Each thread adds rho over its landmarks, and for one landmark over the frames in index order; summed over the
+ *   landmarks (above) it is a float64, returned rounded to float32.  Nothing active: 0.
+ * Lines (float32).  An observation with e2 = +inf adds nothing below.  Otherwise with K23's xn, yn, iz: J_u, J_v, r_u, r_v
+ *   of K23's Refit, and the point lines X_u[j] = J_u[3] R_0j + J_u[5] R_2j, X_v[j] = J_v[4] R_1j + J_v[5] R_2j (the rows of
+ *   [[iz, 0, -xn iz], [0, iz, -yn iz]] R).  Per landmark, over its frames in index order, with V kept as (00 01 02 11 12 22):
+ *       V_ij += (w X_u[i]) X_u[j], then V_ij += (w X_v[i]) X_v[j];  h_i += (w X_u[i]) r_u, then h_i += (w X_v[i]) r_v.
+ *   Fixed frames add here too.  W_fl (6 x 3) = [(w J_u[i]) X_u[c] + (w J_v[i]) X_v[c]].
+ * Inverse.  m = V with the diagonal V_ii + lambda V_ii (lambda rounded to float32); cofactors c as in K23's step 2
+ *   (pnp_cof), det = (m00 c00 + m01 c01) + m02 c02, Vi = c / det.  Pivots p0 = m00, p1 = c22 / m00, p2 = det / c22.  The
+ *   landmark is FROZEN for this step -- Vi = 0: it acts as a fixed point -- unless max(m00, m11, m22) > 0, min(p0, p1, p2) >
+ *   1e-6 max(m00, m11, m22) and every Vi element is finite.
+ * Reduced system, n = 6 (F - num_fixed) unknowns, free frame f at offset 6 (f - num_fixed).  For every free f, over the
+ *   landmarks seen in f: Y = W_fl Vi with Y_ic = (W_i0 Vi_0c + W_i1 Vi_1c) + W_i2 Vi_2c;
+ *       U_ij += (w J_u[i]) J_u[j], then += (w J_v[i]) J_v[j] (i <= j);  g_i += (w J_u[i]) r_u, then += (w J_v[i]) r_v;
+ *       Q_ij += (Y_i0 W_j0 + Y_i1 W_j1) + Y_i2 W_j2 (i <= j);  q_i += (Y_i0 h_0 + Y_i1 h_1) + Y_i2 h_2.
+ *   The 54 sums over the landmarks are float64: S_ff = (U + lambda diag U) - Q, b_f = g - q.  For every pair f < f' of free
+ *   frames, over the landmarks seen in both: Q_ij += (Y_i0 W'_j0 + Y_i1 W'_j1) + Y_i2 W'_j2 with Y of f and W' of f';
+ *   S_ff' = -Q.
+ * Solve.  S dp = -b in float64 by LDL^T without pivoting on the packed upper triangle: for column j = 0 .. n - 1 the pivot
+ *   d_j = S_jj (after the updates of the earlier columns), l_ij = S_ji / d_j, S_rc -= (l_rj l_cj) d_j for j < r <= c; then
+ *   y = -b, y_k -= l_ki y_i for i ascending; x_k = y_k / d_k, x_k -= l_ik x_i for i descending.  K18's rule for n unknowns:
+ *   unusable when max diag S <= 0, a pivot is not above 1e-6 max diag S (the diagonal before elimination), or an x is not
+ *   finite.  n = 0 is usable.
+ * Step.  Poses: K18's update of the float64 pose with dp_f, rounded to float32 for every line.  Points (float32, dp
+ *   rounded to float32): s = h; over the FREE frames seen, in index order, su = J_u . dp_f, sv = J_v . dp_f (each
+ *   ((((a0 + a1) + a2) + a3) + a4) + a5), s_a += (w X_u[a]) su, then s_a += (w X_v[a]) sv;
+ *   X_a <- X_a + -((Vi_a0 s_0 + Vi_a1 s_1) + Vi_a2 s_2).
+ * Loop.  lambda = 1e-4 (float64).  `iterations` times: linearise at the state with lambda, solve, step to a candidate,
+ *   evaluate its cost; when the system was usable and the candidate's cost is finite and strictly lower (float64 sums
+ *   compared), the candidate becomes the state and lambda <- max(lambda / 10, 1e-9); otherwise lambda <- min(10 lambda, 1e6).
+ *   Never stops early.  Refusal: the initial cost is not finite, or no landmark is active. */
+#define MI_BA_MAX_FRAMES 16
+#define MI_BA_MAX_LANDMARKS 2048
+#define MI_BA_MAX_ITERATIONS 32
+
+/* Cost alone, the outlier test between rounds: e2 (batch, F, L) float32, the observation's e2 (+inf behind the camera) and
+ * 0 where the entry is not seen or the landmark inactive; cost (batch) float32; active (batch, L) bytes.  One launch. */
+MI_API int mi_ba_cost(const float *r, const float *t, const float *points, const float *obs, const uint8_t *vis, int batch,
+                      int frames, int landmarks, float huber, float *e2, float *cost, uint8_t *active, mi_stream_t stream);
+
+/* Workspace of mi_ba_linearise and mi_ba_refine: 13 floats per landmark (Vi, h, the active flag, the candidate point), L
+ * rounded up to a multiple of 4; 0 for an unsupported shape.  16-byte aligned (MI_E_ALIGN), any content; shorter:
+ * MI_E_CAPACITY.  The alignment is reserved: with it each of a window's 13 arrays starts on a 16-byte boundary, which
+ * four-wide accesses would need; the kernels as built read and write the workspace one float at a time. */
+MI_API size_t mi_ba_workspace_bytes(int batch, int frames, int landmarks);
+
+/* One undamped (lambda = 0) linearisation at the given state: s (batch, 6F, 6F) float32, the full symmetric reduced system
+ * -- the marginal information of the window's poses -- with zero rows and columns for the fixed frames; b (batch, 6F)
+ * float32, zero for the fixed frames; cost (batch).  An observation with e2 = +inf is skipped (and cost = +inf).  One launch. */
+MI_API int mi_ba_linearise(const float *r, const float *t, const float *points, const float *obs, const uint8_t *vis, int batch,
+                           int frames, int landmarks, int num_fixed, float huber, float *s, float *b, float *cost,
+                           void *workspace, size_t workspace_bytes, mi_stream_t stream);
+
+/* The whole loop in one launch.  1 <= iterations <= MI_BA_MAX_ITERATIONS (MI_E_PARAM).  r (batch, F, 3, 3), t (batch, F, 3),
+ * points (batch, L, 3): the final state (fixed frames and inactive landmarks are their inputs' bits); point_ok (batch, L)
+ * bytes: 1 for an active landmark of a window that was not refused; cost0, cost (batch) float32: the cost at the input and
+ * at the result; accepted (batch) int32: the number of accepted steps; info (batch, 6F, 6F): s of mi_ba_linearise at the
+ * result, bit for bit; ok (batch) bytes.  A refused window: ok = 0, the outputs equal the inputs, point_ok = 0, accepted = 0,
+ * info = 0, cost0 = cost = +inf (0 when no landmark is active). */
+MI_API int mi_ba_refine(const float *r0, const float *t0, const float *points0, const float *obs, const uint8_t *vis, int batch,
+                        int frames, int landmarks, int num_fixed, int iterations, float huber, float *r, float *t, float *points,
+                        uint8_t *point_ok, float *cost0, float *cost, int32_t *accepted, float *info, uint8_t *ok,
+                        void *workspace, size_t workspace_bytes, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,13 @@ SIGNATURES = {
                            c_void_p, c_void_p, c_void_p, c_void_p],
     "mi_two_view_select": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_void_p,
                            c_void_p, c_void_p, c_void_p],
+    "mi_ba_cost": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                   c_void_p],
+    "mi_ba_workspace_bytes": [c_int, c_int, c_int],
+    "mi_ba_linearise": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
+                        c_void_p, c_void_p, c_size_t, c_void_p],
+    "mi_ba_refine": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
     "mi_surfel_maps": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p,
                        c_void_p],
     "mi_icp_workspace_bytes": [c_int, c_int, c_int],
@@ -213,6 +220,7 @@ _RESTYPE = {"mi_essential_matrix_workspace_bytes": c_size_t, "mi_sinkhorn_dots_s
             "mi_voxel_downsample_workspace_bytes": c_size_t, "mi_multi_otsu_workspace_bytes": c_size_t,
             "mi_essential_ransac_workspace_bytes": c_size_t, "mi_rigid_ransac_workspace_bytes": c_size_t,
             "mi_pnp_ransac_workspace_bytes": c_size_t, "mi_homography_ransac_workspace_bytes": c_size_t,
+            "mi_ba_workspace_bytes": c_size_t,
             "mi_icp_workspace_bytes": c_size_t, "mi_rgbd_workspace_bytes": c_size_t, "mi_tsdf_surface_workspace_bytes": c_size_t}
 
 MI_BAD_RAW, MI_BAD_SOFT, MI_BAD_HARD = 0, 1, 2

@@ -1463,6 +1463,98 @@ def two_view_select(e: torch.Tensor, h: torch.Tensor, pts1: torch.Tensor, pts2: 
     return se, sh, choice.view(torch.bool)
 
 
+# ---- K25 windowed bundle adjustment (include/mi355x_match.h, "windowed bundle adjustment") -----------------------------------
+
+BA_MAX_FRAMES = 16                         # MI_BA_MAX_FRAMES
+BA_MAX_LANDMARKS = 2048                    # MI_BA_MAX_LANDMARKS
+BA_MAX_ITERATIONS = 32                     # MI_BA_MAX_ITERATIONS
+
+
+def _ba_window(r: torch.Tensor, t: torch.Tensor, points: torch.Tensor, obs: torch.Tensor, vis: torch.Tensor, huber: float, what: str):
+    """The state and the observations of a batch of windows as the C ABI reads them: r (B, F, 3, 3), t (B, F, 3), points
+    (B, L, 3), obs (B, F, L, 2) normalised (u, v), vis (B, F, L)."""
+    rr, tt, xx, oo = (a.float().contiguous() for a in (r, t, points, obs))
+    if rr.dim() != 4 or tuple(rr.shape[2:]) != (3, 3) or xx.dim() != 3 or xx.shape[-1] != 3:
+        raise RuntimeError(f"{what}: poses must be (B, F, 3, 3) and points (B, L, 3), got {tuple(r.shape)} and {tuple(points.shape)}")
+    b, f, l = int(rr.shape[0]), int(rr.shape[1]), int(xx.shape[1])
+    if tuple(tt.shape) != (b, f, 3) or xx.shape[0] != b or tuple(oo.shape) != (b, f, l, 2) or tuple(vis.shape) != (b, f, l):
+        raise RuntimeError(f"{what}: expected t ({b}, {f}, 3), points ({b}, {l}, 3), obs ({b}, {f}, {l}, 2) and vis ({b}, {f}, {l}), got "
+                           f"{tuple(t.shape)}, {tuple(points.shape)}, {tuple(obs.shape)} and {tuple(vis.shape)}")
+    if not 2 <= f <= BA_MAX_FRAMES or not 1 <= l <= BA_MAX_LANDMARKS or b < 1:
+        raise RuntimeError(f"{what}: F = {f} frames and L = {l} landmarks, supported: 2 .. {BA_MAX_FRAMES} and 1 .. {BA_MAX_LANDMARKS}")
+    if not (huber >= 0 and huber < float("inf")):
+        raise RuntimeError(f"{what}: huber must be finite and not negative, got {huber}")
+    vv = _validity_bytes(vis)
+    ptrs = (N.dev(rr, F32, "r"), N.dev(tt, F32, "t"), N.dev(xx, F32, "points"), N.dev(oo, F32, "obs"), N.dev(vv, U8, "vis"))
+    return ptrs, (rr, tt, xx, oo, vv), b, f, l
+
+
+def _ba_workspace(b: int, f: int, l: int, device):
+    wbytes = int(N.load().mi_ba_workspace_bytes(b, f, l))
+    return torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=device), wbytes
+
+
+def ba_cost(r: torch.Tensor, t: torch.Tensor, points: torch.Tensor, obs: torch.Tensor, vis: torch.Tensor, huber: float = 0.0):
+    """`mi_ba_cost`: the reprojection cost of a batch of windows -> (e2 (B, F, L) float32: the squared normalised distance of
+    every seen observation of an active landmark, 0 elsewhere; cost (B,) float32; active (B, L) bool: seen in >= 2 frames)."""
+    ptrs, keep, b, f, l = _ba_window(r, t, points, obs, vis, huber, "ba_cost")
+    dev = keep[0].device
+    e2 = torch.empty((b, f, l), dtype=F32, device=dev)
+    cost = torch.empty((b,), dtype=F32, device=dev)
+    active = torch.empty((b, l), dtype=U8, device=dev)
+    N.call("mi_ba_cost", *ptrs, b, f, l, float(huber), e2.data_ptr(), cost.data_ptr(), active.data_ptr(), N.stream_ptr())
+    return e2, cost, active.view(torch.bool)
+
+
+def _ba_fixed(num_fixed: int, f: int, what: str) -> int:
+    if not 1 <= int(num_fixed) <= f:
+        raise RuntimeError(f"{what}: num_fixed must be in 1 .. {f}, got {num_fixed}")
+    return int(num_fixed)
+
+
+def ba_linearise(r: torch.Tensor, t: torch.Tensor, points: torch.Tensor, obs: torch.Tensor, vis: torch.Tensor, num_fixed: int = 1,
+                 huber: float = 0.0):
+    """`mi_ba_linearise`: one undamped linearisation with the landmarks eliminated -> (S (B, 6F, 6F) float32, the marginal
+    information of the window's poses in (omega, tau) order per frame, zero for the first num_fixed frames; b (B, 6F); cost (B,))."""
+    ptrs, keep, b, f, l = _ba_window(r, t, points, obs, vis, huber, "ba_linearise")
+    nf = _ba_fixed(num_fixed, f, "ba_linearise")
+    dev = keep[0].device
+    s = torch.empty((b, 6 * f, 6 * f), dtype=F32, device=dev)
+    rhs = torch.empty((b, 6 * f), dtype=F32, device=dev)
+    cost = torch.empty((b,), dtype=F32, device=dev)
+    work, wbytes = _ba_workspace(b, f, l, dev)
+    N.call("mi_ba_linearise", *ptrs, b, f, l, nf, float(huber), s.data_ptr(), rhs.data_ptr(), cost.data_ptr(), work.data_ptr(), wbytes,
+           N.stream_ptr())
+    return s, rhs, cost
+
+
+def ba_refine(r: torch.Tensor, t: torch.Tensor, points: torch.Tensor, obs: torch.Tensor, vis: torch.Tensor, num_fixed: int = 1,
+              iterations: int = 10, huber: float = 0.0):
+    """`mi_ba_refine`: `iterations` Levenberg-Marquardt iterations on every window in one launch -> (R (B, F, 3, 3), t (B, F, 3),
+    points (B, L, 3), point_ok (B, L) bool, cost0 (B,), cost (B,), accepted (B,) int32, info (B, 6F, 6F), ok (B,) bool).  The
+    first num_fixed frames and the landmarks seen in fewer than 2 frames come back unchanged; where ok is False (a point
+    behind a camera at the start, or no active landmark) everything does."""
+    ptrs, keep, b, f, l = _ba_window(r, t, points, obs, vis, huber, "ba_refine")
+    nf = _ba_fixed(num_fixed, f, "ba_refine")
+    if not 1 <= int(iterations) <= BA_MAX_ITERATIONS:
+        raise RuntimeError(f"ba_refine: iterations must be in 1 .. {BA_MAX_ITERATIONS}, got {iterations}")
+    dev = keep[0].device
+    ro = torch.empty((b, f, 3, 3), dtype=F32, device=dev)
+    to = torch.empty((b, f, 3), dtype=F32, device=dev)
+    xo = torch.empty((b, l, 3), dtype=F32, device=dev)
+    point_ok = torch.empty((b, l), dtype=U8, device=dev)
+    cost0 = torch.empty((b,), dtype=F32, device=dev)
+    cost = torch.empty((b,), dtype=F32, device=dev)
+    accepted = torch.empty((b,), dtype=I32, device=dev)
+    info = torch.empty((b, 6 * f, 6 * f), dtype=F32, device=dev)
+    ok = torch.empty((b,), dtype=U8, device=dev)
+    work, wbytes = _ba_workspace(b, f, l, dev)
+    N.call("mi_ba_refine", *ptrs, b, f, l, nf, int(iterations), float(huber), ro.data_ptr(), to.data_ptr(), xo.data_ptr(),
+           point_ok.data_ptr(), cost0.data_ptr(), cost.data_ptr(), accepted.data_ptr(), info.data_ptr(), ok.data_ptr(),
+           work.data_ptr(), wbytes, N.stream_ptr())
+    return ro, to, xo, point_ok.view(torch.bool), cost0, cost, accepted, info, ok.view(torch.bool)
+
+
 # ---- K18 dense RGB-D refinement (include/mi355x_match.h, "dense RGB-D refinement") ------------------------------------------
 
 ICP_MAX_STAGES = 4                         # MI_ICP_MAX_STAGES

@@ -1,4 +1,5 @@
 from .absolute_pose import AbsolutePoseEstimator
+from .bundle_adjustment import BundleAdjuster
 from .dense_rgbd import DenseRgbdRefiner
 from .direct_rgbd import DirectRgbdRefiner
 from .direct_tsdf_volume import DirectTsdfVolume
@@ -8,5 +9,5 @@ from .relative_pose import RelativePoseEstimator, triangulate_points
 from .rgbd_pose import RgbdPoseEstimator
 from .tsdf_volume import TsdfVolume
 
-__all__ = ["AbsolutePoseEstimator", "DenseRgbdRefiner", "DirectRgbdRefiner", "DirectTsdfVolume", "EssentialMatrixEstimator", "HomographyEstimator",
+__all__ = ["AbsolutePoseEstimator", "BundleAdjuster", "DenseRgbdRefiner", "DirectRgbdRefiner", "DirectTsdfVolume", "EssentialMatrixEstimator", "HomographyEstimator",
            "PlanarPoseEstimator", "RelativePoseEstimator", "RgbdPoseEstimator", "TsdfVolume", "TwoViewPoseEstimator", "triangulate_points"]

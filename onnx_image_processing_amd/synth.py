@@ -444,3 +444,72 @@ def synth_depth_room(seed: int, height: int, width: int, rotation_deg: float = 2
         return np.where(np.isfinite(best), best, 0.0).astype(np.float32)
 
     return cast(np.zeros(3), np.eye(3)), cast(-R.T @ t, R.T), R, t
+
+
+BA_FRAME_SPACING = 0.15               # metres between neighbouring cameras of synth_ba_window
+
+
+def _rodrigues64(w: np.ndarray) -> np.ndarray:
+    th = float(np.linalg.norm(w))
+    if th == 0.0:
+        return np.eye(3)
+    k = w / th
+    kx = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    return np.eye(3) + np.sin(th) * kx + (1.0 - np.cos(th)) * (kx @ kx)
+
+
+def synth_ba_window(seed: int, frames: int, landmarks: int, visibility: float = 1.0, noise_px: float = 0.5,
+                    outlier_fraction: float = 0.0, pose_noise: float = 0.01, point_noise: float = 0.05, num_fixed: int = 1):
+    """A window for the bundle-adjustment kernels (K25): (R0, t0, X0, keypoints, visible, R, t, X, outlier).
+
+    The truth: X (landmarks, 3) float64 uniform in [-2, 2] x [-1.5, 1.5] x [3, 9] m, synth_rgbd_pair's volume, in the frame
+    of camera 0 (R[0] = I, t[0] = 0); camera f has its centre at f * BA_FRAME_SPACING m along x plus N(0, 0.02^2) m per axis and
+    the Rodrigues rotation of a N(0, 0.04^2) vector; R (frames, 3, 3), t (frames, 3) float64 with X_c = R X + t.
+    keypoints (frames, landmarks, 2) float32 in pixel (y, x) order under rgbd_camera(): the projection plus N(0, noise_px^2)
+    per axis.  visible (frames, landmarks) bool: a hashed uniform below `visibility`, the point in front of the camera and its
+    pixel inside the 480 x 640 frame.  outlier (frames, landmarks) bool marks round(outlier_fraction * visible.sum()) visible
+    observations, chosen by a hashed ranking, whose pixel is uniform over the image instead.
+    The start: the first num_fixed frames at their TRUE poses (they are the gauge; a perturbed gauge moves the optimum away
+    from the truth); every other pose left-multiplied by the rotation of a N(0, pose_noise^2) vector (radians) with
+    N(0, pose_noise^2) metres added to t; N(0, point_noise^2) metres on every point coordinate.  R0, t0, X0 are float32.
+    float64 arithmetic on hashed integers: the same window everywhere."""
+    if not 1 <= num_fixed <= frames:
+        raise ValueError(f"synth_ba_window: num_fixed must be in 1 .. {frames}, got {num_fixed}")
+    height, width = TWO_VIEW_IMAGE
+    K = rgbd_camera(height, width)
+
+    def uni(shape, salt):
+        idx = np.arange(int(np.prod(shape)), dtype=np.uint64)
+        return (((_hash3(seed, idx, np.uint64(salt) + 0 * idx, 29) >> np.uint64(11)).astype(np.float64) + 0.5) / float(1 << 53)).reshape(shape)
+
+    def normal(shape, salt):
+        return np.sqrt(-2.0 * np.log(uni(shape, salt))) * np.cos(2.0 * np.pi * uni(shape, salt + 1))
+
+    X = np.stack([-2.0 + 4.0 * uni((landmarks,), 0), -1.5 + 3.0 * uni((landmarks,), 1), 3.0 + 6.0 * uni((landmarks,), 2)], axis=1)
+    w_true, c_noise = 0.04 * normal((frames, 3), 4), 0.02 * normal((frames, 3), 6)
+    R, t = np.zeros((frames, 3, 3)), np.zeros((frames, 3))
+    for f in range(frames):
+        R[f] = _rodrigues64(w_true[f]) if f else np.eye(3)
+        c = np.array([f * BA_FRAME_SPACING, 0.0, 0.0]) + c_noise[f] if f else np.zeros(3)
+        t[f] = -R[f] @ c
+    xc = np.einsum("fij,lj->fli", R, X) + t[:, None, :]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        px = K[0, 0] * xc[..., 0] / xc[..., 2] + K[0, 2] + noise_px * normal((frames, landmarks), 8)
+        py = K[1, 1] * xc[..., 1] / xc[..., 2] + K[1, 2] + noise_px * normal((frames, landmarks), 10)
+    visible = (uni((frames, landmarks), 12) < visibility) & (xc[..., 2] > 0.1) & (px >= 0) & (px <= width - 1) & (py >= 0) & (py <= height - 1)
+    n_out = int(round(outlier_fraction * int(visible.sum())))
+    rank = _hash3(seed, np.arange(frames * landmarks, dtype=np.uint64), np.full(frames * landmarks, 13, np.uint64), 29).reshape(frames, landmarks)
+    order = np.argsort(np.where(visible, rank, np.uint64(0xFFFFFFFFFFFFFFFF)).ravel(), kind="stable")
+    outlier = np.zeros(frames * landmarks, bool)
+    outlier[order[:n_out]] = True
+    outlier = outlier.reshape(frames, landmarks) & visible
+    px = np.where(outlier, (width - 1) * uni((frames, landmarks), 14), px)
+    py = np.where(outlier, (height - 1) * uni((frames, landmarks), 15), py)
+    keypoints = np.nan_to_num(np.stack([py, px], axis=-1)).astype(np.float32)
+    w0, dt0 = pose_noise * normal((frames, 3), 16), pose_noise * normal((frames, 3), 18)
+    R0, t0 = R.copy(), t.copy()
+    for f in range(num_fixed, frames):
+        E = _rodrigues64(w0[f])
+        R0[f], t0[f] = E @ R[f], E @ t[f] + dt0[f]
+    X0 = X + point_noise * normal((landmarks, 3), 20)
+    return R0.astype(np.float32), t0.astype(np.float32), X0.astype(np.float32), keypoints, visible, R, t, X, outlier
