@@ -1575,6 +1575,51 @@ MI_API int mi_ba_refine(const float *r0, const float *t0, const float *points0, 
                         uint8_t *point_ok, float *cost0, float *cost, int32_t *accepted, float *info, uint8_t *ok,
                         void *workspace, size_t workspace_bytes, mi_stream_t stream);
 
+/* ---- loop-closure retrieval (K26): which of the keyframes already seen is this frame? ------------------------------------------
+ * Every section above is handed the two frames, or the window, that belong together.  This one finds them: a brute-force,
+ * exact vote of a query frame's packed descriptors against every keyframe of a database, the first step of loop closure and
+ * of relocalisation; a host would use a bag-of-words index (DBoW2) and cv2.BFMatcher.knnMatch with Lowe's ratio test.  Two
+ * entries under the contract of the K15 / K23 / K25 sections: pure functions of their arguments, no allocation, no
+ * synchronisation, no memset, no atomics, one stream, exactly one thread writes each output element, capturable into a
+ * hipGraph; outputs may hold anything on entry, every element is written and outputs alias nothing; MI_E_* before any launch.
+ * All arithmetic is on integers (one float32 multiply and compare in the vote), so the results do not depend on any order.
+ *
+ * Descriptors.  The packed hard bits of mi_sparse_bad / mi_sparse_bad_oriented: num_bits in {256, 512} (every other value:
+ *   MI_E_PARAM), W = num_bits / 32 words each.  hamming(a, b) = popcount(a xor b).  ABSENT = num_bits + 1.
+ * One query frame q against one keyframe f.  Query descriptors 0 .. kq - 1 with validity bytes q_valid (q, kq), database
+ *   descriptors 0 .. kd - 1 with db_valid (n, kd); non-zero = valid, a NULL mask = all valid.  1 <= kq, kd <=
+ *   MI_PLACE_MAX_DESCRIPTORS.  For a valid query descriptor i: the key of column j is hamming << 16 | j over the VALID j;
+ *   key1 is the smallest key -- the nearest descriptor, the lowest index on a tie --, key2 the smallest among the other
+ *   columns.  d1 = key1 >> 16, j1 = key1 & 0xffff (ABSENT and -1 with no valid column); d2 = key2 >> 16 (ABSENT with fewer
+ *   than two valid columns).  i VOTES for f iff d1 <= max_distance and (float)d1 < ratio * (float)d2: one float32 multiply,
+ *   one compare.  An invalid query row never votes and reports j1 = -1, d1 = ABSENT.  votes[q, f] = the number of voting rows.
+ *   0 <= max_distance <= num_bits and 0 < ratio <= 1 (MI_E_PARAM otherwise, NaN included).
+ * Extents.  n, kd, q, kq, slots < 1: MI_E_SHAPE; n > MI_PLACE_MAX_KEYFRAMES, kd or kq > MI_PLACE_MAX_DESCRIPTORS, q > 65535:
+ *   MI_E_PARAM.  db_bits 16-byte aligned, the 32-bit arrays 4-byte aligned (MI_E_ALIGN).
+ *
+ * mi_place_votes.  db_bits (n, kd, W), q_bits (q, kq, W) uint32.  frame_index NULL: slots must equal n (MI_E_SHAPE) and slot s
+ *   is keyframe s.  Otherwise frame_index (q, slots) int32 and slot s of query q scores keyframe frame_index[q, s]; a slot of
+ *   -1 (any negative value) gives votes 0, nn_index -1, nn_distance ABSENT, nn_vote 0; an index >= n is the caller's error and
+ *   is not detected.  votes (q, slots) int32.  nn_index, nn_distance (q, slots, kq) int32 and nn_vote (q, slots, kq) bytes: j1,
+ *   d1 and the vote of every query row -- all three or none (a mixture: MI_E_NULL).  One launch; no distance matrix exists in
+ *   memory and a keyframe's descriptors are read once per (query, slot). */
+#define MI_PLACE_MAX_DESCRIPTORS 1024
+#define MI_PLACE_MAX_KEYFRAMES 65536
+#define MI_PLACE_MAX_CANDIDATES 64
+MI_API int mi_place_votes(const uint32_t *db_bits, const uint8_t *db_valid, int n, int kd, const uint32_t *q_bits,
+                          const uint8_t *q_valid, int q, int kq, const int32_t *frame_index, int slots, int num_bits,
+                          int max_distance, float ratio, int32_t *votes, int32_t *nn_index, int32_t *nn_distance,
+                          uint8_t *nn_vote, mi_stream_t stream);
+
+/* Selection, per query.  votes (q, n) int32.  Keyframe f is ELIGIBLE when votes[q, f] >= min_votes and f lies outside
+ * [excl_lo[q], excl_hi[q]) -- the temporal neighbours of the query; excl_lo, excl_hi (q) int32, both NULL (nothing is
+ * excluded) or both given (one of them: MI_E_NULL).  The eligible keyframes ordered by (votes descending, index ascending):
+ * the first num_candidates go to cand_index (q, num_candidates) and cand_votes (q, num_candidates) int32; empty places hold -1
+ * and 0.  1 <= num_candidates <= MI_PLACE_MAX_CANDIDATES and n <= MI_PLACE_MAX_KEYFRAMES (MI_E_PARAM); q, n < 1: MI_E_SHAPE.
+ * One launch, one workgroup per query. */
+MI_API int mi_place_select(const int32_t *votes, int q, int n, const int32_t *excl_lo, const int32_t *excl_hi, int min_votes,
+                           int num_candidates, int32_t *cand_index, int32_t *cand_votes, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,9 @@ SIGNATURES = {
                         c_void_p, c_void_p, c_size_t, c_void_p],
     "mi_ba_refine": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    "mi_place_votes": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float,
+                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "mi_place_select": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "mi_surfel_maps": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p,
                        c_void_p],
     "mi_icp_workspace_bytes": [c_int, c_int, c_int],

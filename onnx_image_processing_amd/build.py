@@ -24,7 +24,7 @@ LIB = os.path.join(LIBDIR, "libmi355x_match.so")
 DEBUG_LIB = os.path.join(LIBDIR, "libmi355x_match_debug.so")
 INCLUDE = os.path.join(os.path.dirname(PKG), "include")
 
-SOURCES = ["corner.hip", "nms.hip", "topk.hip", "bad.hip", "bad_oriented.hip", "bad_dense.hip", "orient.hip", "cost.hip", "sinkhorn.hip", "sinkhorn_dots.hip", "mnn.hip", "akaze.hip", "akaze_stream.hip", "essential.hip", "detectors.hip", "match_pairs.hip", "voxel.hip", "depth.hip", "threshold.hip", "pose.hip", "ingest.hip", "rigid.hip", "icp.hip", "photo.hip", "tsdf.hip", "surface.hip", "tsdf_gray.hip", "pnp.hip", "homography.hip", "ba.hip"]
+SOURCES = ["corner.hip", "nms.hip", "topk.hip", "bad.hip", "bad_oriented.hip", "bad_dense.hip", "orient.hip", "cost.hip", "sinkhorn.hip", "sinkhorn_dots.hip", "mnn.hip", "akaze.hip", "akaze_stream.hip", "essential.hip", "detectors.hip", "match_pairs.hip", "voxel.hip", "depth.hip", "threshold.hip", "pose.hip", "ingest.hip", "rigid.hip", "icp.hip", "photo.hip", "tsdf.hip", "surface.hip", "tsdf_gray.hip", "pnp.hip", "homography.hip", "ba.hip", "place.hip"]
 # sources that read a hook of csrc/hooks.h: compiled a second time for the debug library; every other object is shared
 HOOKED = ["corner.hip", "nms.hip", "topk.hip", "sinkhorn.hip", "sinkhorn_dots.hip", "akaze.hip", "bad_oriented.hip", "cost.hip", "mnn.hip"]
 DEBUG_ONLY = ["hooks.hip"]

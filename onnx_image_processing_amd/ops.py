@@ -1555,6 +1555,97 @@ def ba_refine(r: torch.Tensor, t: torch.Tensor, points: torch.Tensor, obs: torch
     return ro, to, xo, point_ok.view(torch.bool), cost0, cost, accepted, info, ok.view(torch.bool)
 
 
+# ---- K26 loop-closure retrieval (include/mi355x_match.h, "loop-closure retrieval") -------------------------------------------
+
+PLACE_MAX_DESCRIPTORS = 1024               # MI_PLACE_MAX_DESCRIPTORS
+PLACE_MAX_KEYFRAMES = 65536                # MI_PLACE_MAX_KEYFRAMES
+PLACE_MAX_CANDIDATES = 64                  # MI_PLACE_MAX_CANDIDATES
+
+
+def _place_bits(bits: torch.Tensor, valid: torch.Tensor | None, what: str):
+    """Packed descriptors (frames, K, W) int32 -- as `forward_bits` returns them -- or uint32, W = 8 or 16, and their validity
+    (frames, K) or None, as the C ABI reads them."""
+    if bits.dim() != 3 or bits.dtype not in (torch.int32, torch.uint32):
+        raise RuntimeError(f"{what}: packed descriptors must be (frames, K, W) int32, got {tuple(bits.shape)} {bits.dtype}")
+    b = bits.contiguous()
+    if b.dtype != torch.int32:
+        b = b.view(torch.int32)
+    frames, k, words = (int(s) for s in b.shape)
+    if words not in (8, 16):
+        raise RuntimeError(f"{what}: {32 * words}-bit descriptors, supported: 256 and 512")
+    if frames < 1 or not 1 <= k <= PLACE_MAX_DESCRIPTORS:
+        raise RuntimeError(f"{what}: {frames} frames of {k} descriptors, supported: >= 1 and 1 .. {PLACE_MAX_DESCRIPTORS}")
+    if valid is not None and tuple(valid.shape) != (frames, k):
+        raise RuntimeError(f"{what}: expected a validity mask ({frames}, {k}), got {tuple(valid.shape)}")
+    return b, _validity_bytes(valid), frames, k, words
+
+
+def place_votes(db_bits: torch.Tensor, db_valid: torch.Tensor | None, q_bits: torch.Tensor, q_valid: torch.Tensor | None,
+                max_distance: int, ratio: float, frame_index: torch.Tensor | None = None, want_matches: bool = False):
+    """`mi_place_votes`: every query frame's descriptors against the keyframes of a database -> votes (Q, S) int32, the number
+    of query descriptors whose nearest database descriptor is within max_distance bits and passes the ratio test against the
+    second nearest.  db_bits (N, Kd, W), q_bits (Q, Kq, W) packed hard bits, validity (N, Kd) / (Q, Kq) or None.  frame_index
+    None: S = N, slot s is keyframe s; otherwise (Q, S) int32, the keyframe each slot scores, -1 = an empty slot.
+    want_matches: -> (votes, nn_index (Q, S, Kq) int32, nn_distance (Q, S, Kq) int32, nn_vote (Q, S, Kq) bool)."""
+    db, dbv, n, kd, words = _place_bits(db_bits, db_valid, "place_votes: database")
+    qb, qv, q, kq, qwords = _place_bits(q_bits, q_valid, "place_votes: query")
+    if qwords != words:
+        raise RuntimeError(f"place_votes: the database holds {32 * words}-bit descriptors, the query {32 * qwords}-bit ones")
+    if n > PLACE_MAX_KEYFRAMES or q > 65535:
+        raise RuntimeError(f"place_votes: {n} keyframes and {q} queries, supported: <= {PLACE_MAX_KEYFRAMES} and <= 65535")
+    if not 0 <= int(max_distance) <= 32 * words:
+        raise RuntimeError(f"place_votes: max_distance must be in 0 .. {32 * words}, got {max_distance}")
+    if not 0.0 < float(ratio) <= 1.0:
+        raise RuntimeError(f"place_votes: ratio must be in (0, 1], got {ratio}")
+    slots, fi = n, None
+    if frame_index is not None:
+        if frame_index.dim() != 2 or frame_index.shape[0] != q or frame_index.shape[1] < 1:
+            raise RuntimeError(f"place_votes: frame_index must be ({q}, S), got {tuple(frame_index.shape)}")
+        fi = frame_index.to(I32).contiguous()
+        slots = int(fi.shape[1])
+    ptrs = [N.dev(db, I32, "db_bits"), N.dev(dbv, U8, "db_valid") if dbv is not None else None, n, kd, N.dev(qb, I32, "q_bits"),
+            N.dev(qv, U8, "q_valid") if qv is not None else None, q, kq, N.dev(fi, I32, "frame_index") if fi is not None else None,
+            slots, 32 * words, int(max_distance), float(ratio)]
+    dev = db.device
+    votes = torch.empty((q, slots), dtype=I32, device=dev)
+    if not want_matches:
+        N.call("mi_place_votes", *ptrs, votes.data_ptr(), None, None, None, N.stream_ptr())
+        return votes
+    nn_index = torch.empty((q, slots, kq), dtype=I32, device=dev)
+    nn_distance = torch.empty((q, slots, kq), dtype=I32, device=dev)
+    nn_vote = torch.empty((q, slots, kq), dtype=U8, device=dev)
+    N.call("mi_place_votes", *ptrs, votes.data_ptr(), nn_index.data_ptr(), nn_distance.data_ptr(), nn_vote.data_ptr(), N.stream_ptr())
+    return votes, nn_index, nn_distance, nn_vote.view(torch.bool)
+
+
+def place_select(votes: torch.Tensor, num_candidates: int, min_votes: int, excl_lo: torch.Tensor | None = None,
+                 excl_hi: torch.Tensor | None = None):
+    """`mi_place_select`: votes (Q, N) int32 -> (cand_index (Q, C) int32, cand_votes (Q, C) int32): per query the keyframes
+    with votes >= min_votes outside [excl_lo[q], excl_hi[q]), by (votes descending, index ascending); -1 / 0 in empty places."""
+    if votes.dim() != 2 or votes.dtype != I32:
+        raise RuntimeError(f"place_select: votes must be (Q, N) int32, got {tuple(votes.shape)} {votes.dtype}")
+    v = votes.contiguous()
+    q, n = int(v.shape[0]), int(v.shape[1])
+    if q < 1 or not 1 <= n <= PLACE_MAX_KEYFRAMES:
+        raise RuntimeError(f"place_select: {q} queries and {n} keyframes, supported: >= 1 and 1 .. {PLACE_MAX_KEYFRAMES}")
+    if not 1 <= int(num_candidates) <= PLACE_MAX_CANDIDATES:
+        raise RuntimeError(f"place_select: num_candidates must be in 1 .. {PLACE_MAX_CANDIDATES}, got {num_candidates}")
+    if (excl_lo is None) != (excl_hi is None):
+        raise RuntimeError("place_select: excl_lo and excl_hi come together")
+    lo = hi = None
+    if excl_lo is not None:
+        if tuple(excl_lo.shape) != (q,) or tuple(excl_hi.shape) != (q,):
+            raise RuntimeError(f"place_select: excl_lo and excl_hi must be ({q},), got {tuple(excl_lo.shape)} and {tuple(excl_hi.shape)}")
+        lo, hi = excl_lo.to(I32).contiguous(), excl_hi.to(I32).contiguous()
+    ptr = N.dev(v, I32, "votes")
+    cand_index = torch.empty((q, int(num_candidates)), dtype=I32, device=v.device)
+    cand_votes = torch.empty((q, int(num_candidates)), dtype=I32, device=v.device)
+    N.call("mi_place_select", ptr, q, n, N.dev(lo, I32, "excl_lo") if lo is not None else None,
+           N.dev(hi, I32, "excl_hi") if hi is not None else None, int(min_votes), int(num_candidates), cand_index.data_ptr(),
+           cand_votes.data_ptr(), N.stream_ptr())
+    return cand_index, cand_votes
+
+
 # ---- K18 dense RGB-D refinement (include/mi355x_match.h, "dense RGB-D refinement") ------------------------------------------
 
 ICP_MAX_STAGES = 4                         # MI_ICP_MAX_STAGES

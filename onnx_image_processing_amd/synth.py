@@ -513,3 +513,36 @@ def synth_ba_window(seed: int, frames: int, landmarks: int, visibility: float = 
         R0[f], t0[f] = E @ R[f], E @ t[f] + dt0[f]
     X0 = X + point_noise * normal((landmarks, 3), 20)
     return R0.astype(np.float32), t0.astype(np.float32), X0.astype(np.float32), keypoints, visible, R, t, X, outlier
+
+
+def synth_place_descriptors(seed: int, n_frames: int, k: int, num_bits: int, flip: float = 0.1, keep: float = 0.5):
+    """Packed descriptors for the retrieval kernels (K26): (db_bits, q_bits, target, source).
+
+    db_bits (n_frames, k, num_bits / 32) int32: uniform random bits, bit b of a descriptor in bit b % 32 of word b // 32.
+    q_bits (k, num_bits / 32) int32: a REVISIT of keyframe `target` (a hashed choice): round(keep * k) of its descriptors,
+    chosen by a hashed ranking, are kept with every bit flipped with probability `flip`, the others are replaced by fresh
+    random descriptors, and the rows are permuted by a hashed ranking.  source (k,) int64: the row of keyframe `target` a
+    query row was made from, -1 for a replaced one.  Hashed integers only: the same arrays everywhere."""
+    if num_bits % 32 != 0 or num_bits <= 0:
+        raise ValueError(f"synth_place_descriptors: num_bits must be a positive multiple of 32, got {num_bits}")
+    if not (0.0 <= flip <= 1.0 and 0.0 <= keep <= 1.0) or n_frames < 1 or k < 1:
+        raise ValueError("synth_place_descriptors: flip and keep must lie in [0, 1], n_frames and k be positive")
+    words = num_bits // 32
+
+    def draw(rows, cols, salt):                      # (rows, cols) uint64 hashes
+        r, c = np.broadcast_arrays(np.arange(rows, dtype=np.uint64)[:, None], np.arange(cols, dtype=np.uint64)[None, :])
+        return _hash3(seed, r, c, salt)
+
+    db = (draw(n_frames * k, words, 31) & np.uint64(0xFFFFFFFF)).astype(np.uint32).reshape(n_frames, k, words)
+    target = int(_hash3(seed, np.zeros(1, np.uint64), np.zeros(1, np.uint64), 32)[0] % np.uint64(n_frames))
+    n_keep = int(round(keep * k))
+    kept = np.zeros(k, bool)
+    kept[np.argsort(draw(k, 1, 33)[:, 0], kind="stable")[:n_keep]] = True
+    uniform = ((draw(k, num_bits, 34) >> np.uint64(11)).astype(np.float64) + 0.5) / float(1 << 53)
+    flips = (uniform < flip).reshape(k, words, 32)
+    mask = (flips.astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(axis=2).astype(np.uint32)
+    fresh = (draw(k, words, 35) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    rows = np.where(kept[:, None], db[target] ^ mask, fresh)
+    order = np.argsort(draw(k, 1, 36)[:, 0], kind="stable")
+    source = np.where(kept, np.arange(k), -1)[order].astype(np.int64)
+    return db.view(np.int32), np.ascontiguousarray(rows[order]).view(np.int32), target, source

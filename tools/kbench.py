@@ -150,6 +150,9 @@ def main():
         d = bad(img[:32], kp[:32])
         ms = timeit(lambda: ops.cost_logscores_f32(d, torch.roll(d, 1, 0), 0, 0.05), args.iters)
         res["cost_f32(32 pairs)"] = (ms, 2.0 * 32 * K * K * 512 / ms / 1e9)
+    if "place" in args.which:                  # K26 (not in the default list): frame 0 against all n frames, then the selection
+        res["place_votes"] = (timeit(lambda: ops.place_votes(bits, None, bits[:1], None, 32 * bits.shape[2] // 4, 0.8), args.iters), 0.0)
+        res["place_votes + place_select"] =(timeit(lambda: ops.place_select(ops.place_votes(bits, None, bits[:1], None, 32 * bits.shape[2] // 4, 0.8), 4, 20), args.iters), 0.0)
     z, pitch = ops.cost_logscores_bits(bits, b2, True, 0.05)
     if "sinkhorn" in args.which:
         for mode, name in ((1, "sinkhorn_fused log-partials"), (2, "sinkhorn_fused prob-partials v1"),
