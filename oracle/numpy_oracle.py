@@ -786,20 +786,20 @@ def essential_weights(p, valid1=None, valid2=None, top_k=3):
     return core * mask.astype(F32)
 
 
-def _hartley(pts, w):
+def _hartley(pts, w, dtype=F32):
     """_hartley_normalization (essential_matrix_estimator.py:250-300)."""
-    w_sum = w.sum(dtype=F32) + F32(1e-8)
-    c = (w[:, None] * pts).sum(axis=0, dtype=F32) / w_sum
+    w_sum = w.sum(dtype=dtype) + dtype(1e-8)
+    c = (w[:, None] * pts).sum(axis=0, dtype=dtype) / w_sum
     pc = pts - c
-    dist_sq = (pc ** 2).sum(axis=-1, dtype=F32)
-    mean_dist = np.sqrt((w * dist_sq).sum(dtype=F32) / w_sum + F32(1e-8))
-    s = np.sqrt(F32(2.0)) / (mean_dist + F32(1e-8))
-    t = np.array([[s, 0, -s * c[0]], [0, s, -s * c[1]], [0, 0, 1]], F32)
-    return t, F32(s), c.astype(F32)
+    dist_sq = (pc ** 2).sum(axis=-1, dtype=dtype)
+    mean_dist = np.sqrt((w * dist_sq).sum(dtype=dtype) / w_sum + dtype(1e-8))
+    s = np.sqrt(dtype(2.0)) / (mean_dist + dtype(1e-8))
+    t = np.array([[s, 0, -s * c[0]], [0, s, -s * c[1]], [0, 0, 1]], dtype)
+    return t, dtype(s), c.astype(dtype)
 
 
-def _unit(v):
-    return (v / (np.sqrt((v * v).sum(dtype=F32)) + F32(1e-8))).astype(F32)
+def _unit(v, dtype=F32):
+    return (v / (np.sqrt((v * v).sum(dtype=dtype)) + dtype(1e-8))).astype(dtype)
 
 
 def _det3(m):
@@ -814,31 +814,37 @@ def essential_from_weights(weights, pts1_n, pts2_n, n_iter=30, n_iter_manifold=1
     w = np.asarray(weights, dtype)
     p1, p2 = np.asarray(pts1_n, dtype), np.asarray(pts2_n, dtype)
     n, m = w.shape
-    t1, s1, c1 = _hartley(p1, w.sum(axis=1, dtype=dtype))
-    t2, s2, c2 = _hartley(p2, w.sum(axis=0, dtype=dtype))
+    t1, s1, c1 = _hartley(p1, w.sum(axis=1, dtype=dtype), dtype)
+    t2, s2, c2 = _hartley(p2, w.sum(axis=0, dtype=dtype), dtype)
     f1 = np.concatenate([(p1 - c1) * s1, np.ones((n, 1), dtype)], axis=-1)
     f2 = np.concatenate([(p2 - c2) * s2, np.ones((m, 1), dtype)], axis=-1)
     big1 = (f1[:, :, None] * f1[:, None, :]).reshape(n, 9)
     big2 = (f2[:, :, None] * f2[:, None, :]).reshape(m, 9)
-    m_flat = big1.T @ (w @ big2)
+    return essential_from_sums(big1.T @ (w @ big2), t1, t2, n_iter, n_iter_manifold, dtype)
+
+
+def essential_from_sums(m_flat, t1, t2, n_iter=30, n_iter_manifold=10, dtype=F32, shift=True):
+    """The tail of essential_from_weights from the (9, 9) normal-equation sums m_flat[3p+r][3q+s] and the two Hartley
+    transforms (:414-431, :150-248).  shift=False leaves the trace shift out (tests plant that error)."""
+    m_flat = np.asarray(m_flat, dtype)
     m_mat = m_flat.reshape(3, 3, 3, 3).transpose(0, 2, 1, 3).reshape(9, 9).astype(dtype)
-    lam = np.trace(m_mat).astype(dtype)
+    lam = np.trace(m_mat).astype(dtype) if shift else dtype(0.0)
     m_s = (lam * np.eye(9, dtype=dtype) - m_mat).astype(dtype)
     v = (np.ones(9, dtype) / dtype(3.0)).astype(dtype)
     for _ in range(n_iter):
-        v = _unit((m_s @ v).astype(dtype))
+        v = _unit((m_s @ v).astype(dtype), dtype)
     e = (t2.T @ v.reshape(3, 3) @ t1).astype(dtype)
     # manifold projection (:175-248)
     b = (e.T @ e).astype(dtype)
     lam = np.trace(b).astype(dtype)
     v1 = (np.ones(3, dtype) / np.sqrt(dtype(3.0))).astype(dtype)
     for _ in range(n_iter_manifold):
-        v1 = _unit((b @ v1).astype(dtype))
+        v1 = _unit((b @ v1).astype(dtype), dtype)
     b_s = (lam * np.eye(3, dtype=dtype) - b).astype(dtype)
     v3 = (np.ones(3, dtype) / np.sqrt(dtype(3.0))).astype(dtype)
     for _ in range(n_iter_manifold):
-        v3 = _unit((b_s @ v3).astype(dtype))
-    v2 = _unit(np.cross(v3, v1).astype(dtype))
+        v3 = _unit((b_s @ v3).astype(dtype), dtype)
+    v2 = _unit(np.cross(v3, v1).astype(dtype), dtype)
     vm = np.stack([v1, v2, v3], axis=-1).astype(dtype)
     vm = (vm @ np.diag(np.array([1, 1, np.sign(_det3(vm))], dtype))).astype(dtype)
     ev0, ev1 = (e @ vm[:, 0]).astype(dtype), (e @ vm[:, 1]).astype(dtype)
