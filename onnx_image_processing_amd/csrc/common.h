@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "../../include/mi355x_match.h"
 
 #define MI_WAVE 64
@@ -22,6 +24,13 @@ static inline int mi_launch_status() {
   } while (0)
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// every pointer on a 16-byte boundary (null counts as aligned): the float4 / 16-byte accesses of the dense kernels
+static inline bool mi_aligned16(std::initializer_list<const void *> ps) {
+  for (const void *p : ps)
+    if (((uintptr_t)p % 16) != 0) return false;
+  return true;
+}
 
 // Clearing device memory on a stream WITHOUT hipMemsetAsync.  A memset call captured into a hipGraph becomes a memset
 // node, and on this stack (ROCm 7.2, torch 2.10 graphs) such a node zeroes correctly on the first replay only: later

@@ -4,18 +4,16 @@
 // K18m  icp_surfel_kernel   one thread per pixel: the vertex (the ray of mi_lift_keypoints times depth) and the normal from
 //       the four axis neighbours, whose vertices the thread forms itself from their depths (5 depth reads, cached);
 //       two 16-byte records per pixel: (vx, vy, vz, vertex valid) and (nx, ny, nz, normal valid).
-// K18r  icp_reduce_kernel   grid (slabs, pairs), 256 threads.  A slab is ICP_SLAB = 2048 consecutive SAMPLED pixels of the
-//       stride's grid (row-major over ceil(h / s) x ceil(w / s)): a function of (h, w, s) only.  Lane l of the workgroup takes
-//       the samples l, l + 256, ... of its slab in this order (8 of them) into 28 float32 accumulators and an integer count:
-//       the streamed records are read unconditionally, the gathered ones at a clamped address, and a rejected pixel adds
-//       zeros, so the 8 iterations carry no branch and their loads overlap.  Then the DPP tree of wave_sum_dpp per
-//       accumulator, the 4 waves through LDS in wave order in float64, and 29 float64 partials stored with plain stores
-//       into the slab's 256-byte record.  No atomics.
+// K18r  icp_reduce_kernel   the slab reduction of icp_shared.h (grid (slabs, pairs), 256 threads, 8 samples per lane, 29
+//       float64 partials per slab record) around the geometric row, which is this file's: the streamed records of frame 1 are
+//       read unconditionally, frame 2's surfel at a clamped address, and a rejected pixel adds zeros.
 // K18s  icp_solve_kernel    one wave per pair: lane c < 29 adds column c of the pair's slab records in slab order
 //       (float64); lane 0 then solves (LDL^T) and updates the pose in the workspace (mode STEP), or writes the 29 sums
-//       (mode SUMS) or the outputs (mode FINAL).
+//       (mode SUMS) or the outputs (mode FINAL).  The column sum, the step and the pose write are icp_shared.h's.
 // K18i  icp_init_kernel     r0 / t0 -> the float64 pose, state and step words of the workspace.
 // A pair whose solve failed is frozen: its state word is set, and K18r / K18s return at once for it in later iterations.
+// This file's own: K18m, K18i, the row of K18r, the statistics of K18s and the entry points.  Shared with K21 through
+// icp_shared.h: the sample index and the tail of the reduction, the solve step, the workspace, the checks, the refine driver.
 // Built with -ffp-contract=off; every sum has a fixed order: bitwise reproducible, alone or in a batch.
 #include "common.h"
 #include "icp_math.h"
@@ -67,8 +65,7 @@ __global__ __launch_bounds__(64) void icp_init_kernel(const float *__restrict__ 
 }
 
 // ---- K18r ------------------------------------------------------------------------------------------------------------------
-// The pose comes from r / t (float32, mi_icp_linearise) or, when pose64 is given, from the workspace's float64 pose
-// rounded to float32 (mi_icp_refine).
+// icp_shared.h's sequence around the geometric row (its loads: the file header)
 __global__ __launch_bounds__(ICP_THREADS) void icp_reduce_kernel(const float4 *__restrict__ vertex1, const float4 *__restrict__ normal1,
                                                                  const float4 *__restrict__ vertex2, const float4 *__restrict__ normal2,
                                                                  const float *__restrict__ r, const float *__restrict__ t,
@@ -97,11 +94,8 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_reduce_kernel(const float4 *_
   int count = 0;
 #pragma unroll
   for (int it = 0; it < ICP_PER_LANE; ++it) {
-    const int s = slab * ICP_SLAB + it * ICP_THREADS + tid;
-    const bool in = s < samples;
-    const int sc = in ? s : 0;                               // a clamped, always valid address
-    const int ys = sc / ws, xs = sc - ys * ws;
-    const size_t i1 = frame + (size_t)(ys * stride) * (size_t)w + (size_t)(xs * stride);
+    bool in;
+    const size_t i1 = frame + icp_sample_pixel(slab, it, tid, samples, ws, stride, w, &in);
     const float4 n1 = normal1[i1], v1 = vertex1[i1];
     const float p1[3] = {v1.x, v1.y, v1.z}, m1[3] = {n1.x, n1.y, n1.z};
     float q[3], rn[3], px, py;
@@ -124,24 +118,10 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_reduce_kernel(const float4 *_
     icp_accumulate(J, res, acc);
     count += ok ? 1 : 0;
   }
-  const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int k = 0; k < 28; ++k) {
-    const float sum = wave_sum_dpp(acc[k]);
-    if (lane == 0) part[wave][k] = (double)sum;
-  }
-  int c = count;                                             // integers: exact in any order
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-  if (lane == 0) part[wave][28] = (double)c;
-  __syncthreads();
-  if (tid < ICP_SUMS)
-    slabs[((size_t)b * max_slabs + slab) * ICP_REC + tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+  icp_store_slab(acc, count, part, slabs + ((size_t)b * max_slabs + slab) * ICP_REC);
 }
 
 // ---- K18s ------------------------------------------------------------------------------------------------------------------
-enum { ICP_MODE_STEP = 0, ICP_MODE_SUMS = 1, ICP_MODE_FINAL = 2 };
-
 struct IcpOut {
   float *r, *t, *information, *rmse;
   int *count, *steps;
@@ -156,31 +136,14 @@ __global__ __launch_bounds__(64) void icp_solve_kernel(const double *__restrict_
   const int b = blockIdx.x, lane = threadIdx.x;
   if (mode == ICP_MODE_STEP && state[b] != 0) return;        // frozen pair
   if (lane < ICP_SUMS) {
-    double a = 0.0;
-    for (int k = 0; k < nslabs; ++k) a += slabs[((size_t)b * max_slabs + k) * ICP_REC + lane];
+    const double a = icp_column_sum(slabs, b, nslabs, max_slabs, lane);
     s[lane] = a;
     if (mode == ICP_MODE_SUMS) out.sums[(size_t)b * ICP_SUMS + lane] = a;
   }
   __syncthreads();
   if (mode == ICP_MODE_SUMS || lane != 0) return;
   if (mode == ICP_MODE_STEP) {
-    double x[6], ratio;
-    if (icp_solve(s, min_count, x, &ratio)) {
-      double p[12];
-#pragma unroll
-      for (int k = 0; k < 12; ++k) p[k] = pose[(size_t)b * 12 + k];
-      icp_update_pose(p, x);
-      bool finite = true;
-#pragma unroll
-      for (int k = 0; k < 12; ++k) finite = finite && fabs(p[k]) < INFINITY;
-      if (finite) {
-#pragma unroll
-        for (int k = 0; k < 12; ++k) pose[(size_t)b * 12 + k] = p[k];
-        steps[b] += 1;
-        return;
-      }
-    }
-    state[b] = 1;
+    icp_step(s, min_count, b, pose, state, steps);
     return;
   }
   // FINAL: the statistics of the returned pose
@@ -188,16 +151,7 @@ __global__ __launch_bounds__(64) void icp_solve_kernel(const double *__restrict_
   bool finite = true;
   for (int k = 0; k < ICP_SUMS; ++k) finite = finite && fabs(s[k]) < INFINITY;
   const bool good = finite && state[b] == 0 && cnt >= min_count;
-  for (int k = 0; k < 9; ++k) out.r[(size_t)b * 9 + k] = (float)pose[(size_t)b * 12 + k];
-  for (int k = 0; k < 3; ++k) out.t[(size_t)b * 3 + k] = (float)pose[(size_t)b * 12 + 9 + k];
-  int k = 0;
-  for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 6; ++j) {
-      const float v = finite ? (float)s[k] : 0.0f;
-      out.information[(size_t)b * 36 + i * 6 + j] = v;
-      out.information[(size_t)b * 36 + j * 6 + i] = v;
-      ++k;
-    }
+  icp_write_pose(s, finite, b, pose, out.r, out.t, out.information);
   out.rmse[b] = (finite && cnt > 0) ? (float)sqrt(s[27] / (double)cnt) : 0.0f;
   out.count[b] = finite ? cnt : 0;
   out.steps[b] = steps[b];
@@ -205,37 +159,11 @@ __global__ __launch_bounds__(64) void icp_solve_kernel(const double *__restrict_
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-struct IcpWork {
-  double *pose, *slabs;
-  int *state, *steps;
-  int max_slabs;
-  size_t total;
-};
-IcpWork icp_carve(void *ws, int batch, int h, int w) {
-  char *base = static_cast<char *>(ws);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char *q = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
-  IcpWork k;
-  k.max_slabs = ceil_div(h * w, ICP_SLAB);                   // stride 1
-  k.pose = reinterpret_cast<double *>(take((size_t)batch * 12 * sizeof(double)));
-  k.slabs = reinterpret_cast<double *>(take((size_t)batch * k.max_slabs * ICP_REC * sizeof(double)));
-  k.state = reinterpret_cast<int *>(take((size_t)batch * sizeof(int)));
-  k.steps = reinterpret_cast<int *>(take((size_t)batch * sizeof(int)));
-  k.total = off;
-  return k;
-}
-
-// one linearisation: K18r over the slabs of `stride`, then K18s in `mode`
-int icp_linearise_launch(const float4 *v1, const float4 *n1, const float4 *v2, const float4 *n2, const float *r, const float *t,
-                         bool from_workspace, int batch, int h, int w, int stride, IcpCam cam, float thr2, float cos_thr,
-                         int mode, int min_count, const IcpWork &k, IcpOut out, hipStream_t s) {
-  int ws;
-  const int samples = icp_samples(h, w, stride, &ws), nslabs = ceil_div(samples, ICP_SLAB);
-  hipLaunchKernelGGL(icp_reduce_kernel, dim3((unsigned)nslabs, (unsigned)batch), dim3(ICP_THREADS), 0, s, v1, n1, v2, n2, r, t,
-                     from_workspace ? k.pose : nullptr, (from_workspace && mode == ICP_MODE_STEP) ? k.state : nullptr, h, w, stride,
-                     ws, samples, k.max_slabs, cam, thr2, cos_thr, k.slabs);
-  MI_CHECK_LAUNCH();
-  hipLaunchKernelGGL(icp_solve_kernel, dim3((unsigned)batch), dim3(64), 0, s, k.slabs, nslabs, k.max_slabs, mode, min_count,
+// one linearisation: K18r over the job's slabs, then K18s in `mode`
+int icp_linearise_launch(const IcpMaps &m, const IcpReduceJob &job, int batch, int mode, int min_count, const IcpWork &k, IcpOut out,
+                         hipStream_t s) {
+  if (const int e = icp_reduce_launch(m, job, batch, s)) return e;
+  hipLaunchKernelGGL(icp_solve_kernel, dim3((unsigned)batch), dim3(64), 0, s, job.slabs, job.nslabs, job.max_slabs, mode, min_count,
                      k.pose, k.state, k.steps, out);
   return mi_launch_status();
 }
@@ -248,13 +176,10 @@ int icp_init_launch(const float *r0, const float *t0, int batch, double *pose, i
   return mi_launch_status();
 }
 
-int icp_reduce_launch(const float4 *v1, const float4 *n1, const float4 *v2, const float4 *n2, const float *r, const float *t,
-                      const double *pose64, const int *state, int batch, int h, int w, int stride, int max_slabs, IcpCam cam,
-                      float thr2, float cos_thr, double *slabs, hipStream_t s) {
-  int ws;
-  const int samples = icp_samples(h, w, stride, &ws), nslabs = ceil_div(samples, ICP_SLAB);
-  hipLaunchKernelGGL(icp_reduce_kernel, dim3((unsigned)nslabs, (unsigned)batch), dim3(ICP_THREADS), 0, s, v1, n1, v2, n2, r, t,
-                     pose64, state, h, w, stride, ws, samples, max_slabs, cam, thr2, cos_thr, slabs);
+int icp_reduce_launch(const IcpMaps &m, const IcpReduceJob &job, int batch, hipStream_t s) {
+  hipLaunchKernelGGL(icp_reduce_kernel, dim3((unsigned)job.nslabs, (unsigned)batch), dim3(ICP_THREADS), 0, s, m.vertex1, m.normal1,
+                     m.vertex2, m.normal2, job.r, job.t, job.pose64, job.state, job.h, job.w, job.stride, job.ws, job.samples,
+                     job.max_slabs, job.cam, m.thr2, m.cos_thr, job.slabs);
   return mi_launch_status();
 }
 
@@ -267,7 +192,7 @@ extern "C" int mi_surfel_maps(const void *depth, int depth_is_u16, int batch, in
   if (!(min_depth > 0.0f) || !(max_depth >= min_depth) || !(max_depth < INFINITY) || !icp_positive(z_scale) ||
       !icp_positive(normal_max_jump))
     return MI_E_PARAM;
-  if (((uintptr_t)vertex_out % 16) != 0 || ((uintptr_t)normal_out % 16) != 0) return MI_E_ALIGN;
+  if (!mi_aligned16({vertex_out, normal_out})) return MI_E_ALIGN;
   const long long total = (long long)batch * h * w;
   const dim3 grid((unsigned)((total + 255) / 256));
   float4 *v = reinterpret_cast<float4 *>(vertex_out), *n = reinterpret_cast<float4 *>(normal_out);
@@ -282,7 +207,7 @@ extern "C" int mi_surfel_maps(const void *depth, int depth_is_u16, int batch, in
 
 extern "C" size_t mi_icp_workspace_bytes(int batch, int h, int w) {
   if (icp_shape_status(batch, h, w) != MI_OK) return 0;
-  return icp_carve(nullptr, batch, h, w).total;
+  return icp_carve(nullptr, batch, h, w, 1).total;
 }
 
 extern "C" int mi_icp_linearise(const float *vertex1, const float *normal1, const float *vertex2, const float *normal2,
@@ -294,17 +219,14 @@ extern "C" int mi_icp_linearise(const float *vertex1, const float *normal1, cons
   if (const int s = icp_shape_status(batch, h, w)) return s;
   if (!icp_stride_ok(stride)) return MI_E_PARAM;
   if (const int s = icp_gate_status(fx, fy, cx, cy, distance_threshold, angle_threshold)) return s;
-  if (((uintptr_t)workspace % 16) != 0 || ((uintptr_t)vertex1 % 16) != 0 || ((uintptr_t)normal1 % 16) != 0 ||
-      ((uintptr_t)vertex2 % 16) != 0 || ((uintptr_t)normal2 % 16) != 0)
-    return MI_E_ALIGN;
+  if (!mi_aligned16({workspace, vertex1, normal1, vertex2, normal2})) return MI_E_ALIGN;
   if (workspace_bytes < mi_icp_workspace_bytes(batch, h, w)) return MI_E_CAPACITY;
-  const IcpWork k = icp_carve(workspace, batch, h, w);
+  const IcpWork k = icp_carve(workspace, batch, h, w, 1);
   IcpOut out = {};
   out.sums = sums;
-  return icp_linearise_launch(reinterpret_cast<const float4 *>(vertex1), reinterpret_cast<const float4 *>(normal1),
-                              reinterpret_cast<const float4 *>(vertex2), reinterpret_cast<const float4 *>(normal2), r, t, false,
-                              batch, h, w, stride, IcpCam{fx, fy, cx, cy}, distance_threshold * distance_threshold,
-                              (float)cos((double)angle_threshold), ICP_MODE_SUMS, 0, k, out, (hipStream_t)stream);
+  return icp_linearise_launch(icp_maps(vertex1, normal1, vertex2, normal2, distance_threshold, angle_threshold),
+                              icp_reduce_job(r, t, nullptr, nullptr, h, w, stride, IcpCam{fx, fy, cx, cy}, k.max_slabs, k.slabs[0]),
+                              batch, ICP_MODE_SUMS, 0, k, out, (hipStream_t)stream);
 }
 
 extern "C" int mi_icp_refine(const float *vertex1, const float *normal1, const float *vertex2, const float *normal2,
@@ -318,33 +240,19 @@ extern "C" int mi_icp_refine(const float *vertex1, const float *normal1, const f
       !rmse || !count || !steps || !ok || !workspace)
     return MI_E_NULL;
   if (const int s = icp_shape_status(batch, h, w)) return s;
-  if (stages < 1 || stages > MI_ICP_MAX_STAGES || min_correspondences < 1) return MI_E_PARAM;
-  int all = 0;
-  for (int i = 0; i < stages; ++i) {
-    if (!icp_stride_ok(strides[i]) || iterations[i] < 0 || iterations[i] > MI_ICP_MAX_ITERATIONS) return MI_E_PARAM;
-    all += iterations[i];
-  }
-  if (all > MI_ICP_MAX_ITERATIONS) return MI_E_PARAM;
+  if (const int s = icp_schedule_status(strides, iterations, stages, min_correspondences)) return s;
   if (const int s = icp_gate_status(fx, fy, cx, cy, distance_threshold, angle_threshold)) return s;
-  if (((uintptr_t)workspace % 16) != 0 || ((uintptr_t)vertex1 % 16) != 0 || ((uintptr_t)normal1 % 16) != 0 ||
-      ((uintptr_t)vertex2 % 16) != 0 || ((uintptr_t)normal2 % 16) != 0)
-    return MI_E_ALIGN;
+  if (!mi_aligned16({workspace, vertex1, normal1, vertex2, normal2})) return MI_E_ALIGN;
   if (workspace_bytes < mi_icp_workspace_bytes(batch, h, w)) return MI_E_CAPACITY;
-  const IcpWork k = icp_carve(workspace, batch, h, w);
+  const IcpWork k = icp_carve(workspace, batch, h, w, 1);
   hipStream_t s = (hipStream_t)stream;
-  const float4 *v1 = reinterpret_cast<const float4 *>(vertex1), *n1 = reinterpret_cast<const float4 *>(normal1);
-  const float4 *v2 = reinterpret_cast<const float4 *>(vertex2), *n2 = reinterpret_cast<const float4 *>(normal2);
-  const IcpCam cam{fx, fy, cx, cy};
-  const float thr2 = distance_threshold * distance_threshold, cos_thr = (float)cos((double)angle_threshold);
-  hipLaunchKernelGGL(icp_init_kernel, dim3((unsigned)ceil_div(batch, 64)), dim3(64), 0, s, r0, t0, batch, k.pose, k.state, k.steps);
-  MI_CHECK_LAUNCH();
-  IcpOut out = {};
-  for (int st = 0; st < stages; ++st)
-    for (int it = 0; it < iterations[st]; ++it)
-      if (const int e = icp_linearise_launch(v1, n1, v2, n2, nullptr, nullptr, true, batch, h, w, strides[st], cam, thr2, cos_thr,
-                                             ICP_MODE_STEP, min_correspondences, k, out, s))
-        return e;
-  out.r = r; out.t = t; out.information = information; out.rmse = rmse; out.count = count; out.steps = steps; out.ok = ok;
-  return icp_linearise_launch(v1, n1, v2, n2, nullptr, nullptr, true, batch, h, w, strides[stages - 1], cam, thr2, cos_thr,
-                              ICP_MODE_FINAL, min_correspondences, k, out, s);
+  const IcpMaps m = icp_maps(vertex1, normal1, vertex2, normal2, distance_threshold, angle_threshold);
+  if (const int e = icp_init_launch(r0, t0, batch, k.pose, k.state, k.steps, s)) return e;
+  const IcpOut out{r, t, information, rmse, count, steps, ok, nullptr};
+  return icp_refine_drive(strides, iterations, stages, [&](int stride, int mode) {
+    // the freeze words stop a pair's steps only: FINAL reduces every pair at its last pose
+    const IcpReduceJob job = icp_reduce_job(nullptr, nullptr, k.pose, mode == ICP_MODE_STEP ? k.state : nullptr, h, w, stride,
+                                            IcpCam{fx, fy, cx, cy}, k.max_slabs, k.slabs[0]);
+    return icp_linearise_launch(m, job, batch, mode, min_correspondences, k, mode == ICP_MODE_FINAL ? out : IcpOut{}, s);
+  });
 }

@@ -4,16 +4,18 @@
 //
 // K21m  photo_intensity_kernel  one thread per pixel: the gray value and its central differences from the four axis
 //       neighbours (5 reads, cached); one 16-byte record per pixel: (I, gx, gy, valid).
-// K21r  photo_reduce_kernel     K18r's skeleton: grid (slabs, pairs), 256 threads, the same slabs of 2048 sampled pixels, lane
-//       l takes the samples l, l + 256, ... (8 of them) into 28 float32 accumulators and an integer count.  Streamed per
-//       sample: frame 1's vertex and intensity records; gathered at clamped addresses: the four intensity records of the
-//       bilinear footprint in frame 2 and frame 2's vertex at the nearest pixel.  A rejected sample adds zeros, so the 8
-//       iterations carry no branch.  Then wave_sum_dpp per accumulator, the 4 waves through LDS in wave order in float64
-//       and 29 float64 partials stored with plain stores into the slab's 256-byte record.  No atomics.
+// K21r  photo_reduce_kernel     the slab reduction of icp_shared.h (K18r's slabs, lanes and record) around the photometric
+//       row, which is this file's.  Streamed per sample: frame 1's vertex and intensity records; gathered at clamped
+//       addresses: the four intensity records of the bilinear footprint in frame 2 and frame 2's vertex at the nearest
+//       pixel.  A rejected sample adds zeros.
 // K21s  rgbd_solve_kernel       one wave per pair: lane c < 29 adds column c of the pair's geometric and photometric slab
 //       records in slab order (float64); lane 0 forms the joint sums, then solves and updates the pose (mode STEP), or
-//       writes the outputs (mode FINAL); mode SUMS writes the 29 photometric sums.
+//       writes the outputs (mode FINAL); mode SUMS writes the 29 photometric sums.  The column sum, the step and the pose
+//       write are icp_shared.h's.
 // A frozen pair is K18's: its state word is set, and K18r / K21r / K21s return at once for it in later iterations.
+// This file's own: K21m, the row of K21r, the joint sums and the statistics of K21s, and the entry points.  Shared with
+// K18 through icp_shared.h: the sample index and the tail of the reduction, the solve step, the workspace (with a second
+// slab array), the checks and the refine driver.
 // Built with -ffp-contract=off; every sum has a fixed order: bitwise reproducible, alone or in a batch.
 #include "common.h"
 #include "icp_shared.h"
@@ -46,8 +48,7 @@ __global__ __launch_bounds__(256) void photo_intensity_kernel(const G *__restric
 }
 
 // ---- K21r ------------------------------------------------------------------------------------------------------------------
-// The pose comes from r / t (float32, mi_photo_linearise) or, when pose64 is given, from the workspace's float64 pose
-// rounded to float32 (mi_rgbd_refine): K18r's convention.
+// icp_shared.h's sequence around the photometric row (its loads: the file header)
 __global__ __launch_bounds__(ICP_THREADS) void photo_reduce_kernel(const float4 *__restrict__ vertex1, const float4 *__restrict__ inten1,
                                                                    const float4 *__restrict__ vertex2, const float4 *__restrict__ inten2,
                                                                    const float *__restrict__ r, const float *__restrict__ t,
@@ -77,11 +78,8 @@ __global__ __launch_bounds__(ICP_THREADS) void photo_reduce_kernel(const float4 
   int count = 0;
 #pragma unroll
   for (int it = 0; it < ICP_PER_LANE; ++it) {
-    const int s = slab * ICP_SLAB + it * ICP_THREADS + tid;
-    const bool in = s < samples;
-    const int sc = in ? s : 0;                               // a clamped, always valid address
-    const int ys = sc / ws, xs = sc - ys * ws;
-    const size_t i1 = frame + (size_t)(ys * stride) * (size_t)w + (size_t)(xs * stride);
+    bool in;
+    const size_t i1 = frame + icp_sample_pixel(slab, it, tid, samples, ws, stride, w, &in);
     const float4 v1 = vertex1[i1], g1 = inten1[i1];
     const float p1[3] = {v1.x, v1.y, v1.z};
     float q[3], x0, y0, a, bb, px, py;
@@ -108,24 +106,10 @@ __global__ __launch_bounds__(ICP_THREADS) void photo_reduce_kernel(const float4 
     icp_accumulate(J, res, acc);
     count += ok ? 1 : 0;
   }
-  const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int k = 0; k < 28; ++k) {
-    const float sum = wave_sum_dpp(acc[k]);
-    if (lane == 0) part[wave][k] = (double)sum;
-  }
-  int c = count;                                             // integers: exact in any order
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-  if (lane == 0) part[wave][28] = (double)c;
-  __syncthreads();
-  if (tid < ICP_SUMS)
-    slabs[((size_t)b * max_slabs + slab) * ICP_REC + tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+  icp_store_slab(acc, count, part, slabs + ((size_t)b * max_slabs + slab) * ICP_REC);
 }
 
 // ---- K21s ------------------------------------------------------------------------------------------------------------------
-enum { RGBD_MODE_STEP = 0, RGBD_MODE_SUMS = 1, RGBD_MODE_FINAL = 2 };
-
 struct RgbdOut {
   float *r, *t, *information, *rmse, *rmse_photo;
   int *count, *count_photo, *steps;
@@ -141,39 +125,20 @@ __global__ __launch_bounds__(64) void rgbd_solve_kernel(const double *__restrict
                                                         int *__restrict__ steps, RgbdOut out) {
   __shared__ double sg[ICP_REC], sp[ICP_REC];
   const int b = blockIdx.x, lane = threadIdx.x;
-  if (mode == RGBD_MODE_STEP && state[b] != 0) return;       // frozen pair
+  if (mode == ICP_MODE_STEP && state[b] != 0) return;        // frozen pair
   if (lane < ICP_SUMS) {
-    double g = 0.0, p = 0.0;
-    if (slabs_g)
-      for (int k = 0; k < nslabs; ++k) g += slabs_g[((size_t)b * max_slabs + k) * ICP_REC + lane];
-    if (slabs_p)
-      for (int k = 0; k < nslabs; ++k) p += slabs_p[((size_t)b * max_slabs + k) * ICP_REC + lane];
+    const double g = slabs_g ? icp_column_sum(slabs_g, b, nslabs, max_slabs, lane) : 0.0;
+    const double p = slabs_p ? icp_column_sum(slabs_p, b, nslabs, max_slabs, lane) : 0.0;
     sg[lane] = g;
     sp[lane] = p;
-    if (mode == RGBD_MODE_SUMS) out.sums[(size_t)b * ICP_SUMS + lane] = p;
+    if (mode == ICP_MODE_SUMS) out.sums[(size_t)b * ICP_SUMS + lane] = p;
   }
   __syncthreads();
-  if (mode == RGBD_MODE_SUMS || lane != 0) return;
+  if (mode == ICP_MODE_SUMS || lane != 0) return;
   double s[ICP_SUMS];
   photo_joint(sg, slabs_p ? sp : nullptr, w2, s);
-  if (mode == RGBD_MODE_STEP) {
-    double x[6], ratio;
-    if (icp_solve(s, min_count, x, &ratio)) {
-      double p[12];
-#pragma unroll
-      for (int k = 0; k < 12; ++k) p[k] = pose[(size_t)b * 12 + k];
-      icp_update_pose(p, x);
-      bool finite = true;
-#pragma unroll
-      for (int k = 0; k < 12; ++k) finite = finite && fabs(p[k]) < INFINITY;
-      if (finite) {
-#pragma unroll
-        for (int k = 0; k < 12; ++k) pose[(size_t)b * 12 + k] = p[k];
-        steps[b] += 1;
-        return;
-      }
-    }
-    state[b] = 1;
+  if (mode == ICP_MODE_STEP) {
+    icp_step(s, min_count, b, pose, state, steps);
     return;
   }
   // FINAL: the statistics of the returned pose
@@ -181,16 +146,7 @@ __global__ __launch_bounds__(64) void rgbd_solve_kernel(const double *__restrict
   bool finite = true;
   for (int k = 0; k < ICP_SUMS; ++k) finite = finite && fabs(s[k]) < INFINITY && fabs(sg[k]) < INFINITY && fabs(sp[k]) < INFINITY;
   const bool good = finite && state[b] == 0 && cnt_g + cnt_p >= min_count;
-  for (int k = 0; k < 9; ++k) out.r[(size_t)b * 9 + k] = (float)pose[(size_t)b * 12 + k];
-  for (int k = 0; k < 3; ++k) out.t[(size_t)b * 3 + k] = (float)pose[(size_t)b * 12 + 9 + k];
-  int k = 0;
-  for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 6; ++j) {
-      const float v = finite ? (float)s[k] : 0.0f;
-      out.information[(size_t)b * 36 + i * 6 + j] = v;
-      out.information[(size_t)b * 36 + j * 6 + i] = v;
-      ++k;
-    }
+  icp_write_pose(s, finite, b, pose, out.r, out.t, out.information);
   out.rmse[b] = (finite && cnt_g > 0) ? (float)sqrt(sg[27] / (double)cnt_g) : 0.0f;
   out.count[b] = finite ? cnt_g : 0;
   out.rmse_photo[b] = (finite && cnt_p > 0) ? (float)sqrt(sp[27] / (double)cnt_p) : 0.0f;
@@ -199,62 +155,32 @@ __global__ __launch_bounds__(64) void rgbd_solve_kernel(const double *__restrict
   out.ok[b] = good ? 1 : 0;
 }
 
-// ---- host ------------------------------------------------------------------------------------------------------------------
-struct RgbdWork {
-  double *pose, *slabs_g, *slabs_p;
-  int *state, *steps;
-  int max_slabs;
-  size_t total;
+// ---- host: the workspace is K18's with two slab arrays, slabs[0] the geometric records, slabs[1] the photometric ones ------------
+// K21r's maps and gates
+struct PhotoMaps {
+  const float4 *vertex1, *inten1, *vertex2, *inten2;
+  float dist_thr, int_thr;
 };
-RgbdWork rgbd_carve(void *ws, int batch, int h, int w) {
-  char *base = static_cast<char *>(ws);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char *q = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
-  RgbdWork k;
-  k.max_slabs = ceil_div(h * w, ICP_SLAB);                   // stride 1
-  k.pose = reinterpret_cast<double *>(take((size_t)batch * 12 * sizeof(double)));
-  k.slabs_g = reinterpret_cast<double *>(take((size_t)batch * k.max_slabs * ICP_REC * sizeof(double)));
-  k.slabs_p = reinterpret_cast<double *>(take((size_t)batch * k.max_slabs * ICP_REC * sizeof(double)));
-  k.state = reinterpret_cast<int *>(take((size_t)batch * sizeof(int)));
-  k.steps = reinterpret_cast<int *>(take((size_t)batch * sizeof(int)));
-  k.total = off;
-  return k;
+PhotoMaps photo_maps(const float *vertex1, const float *intensity1, const float *vertex2, const float *intensity2,
+                     float distance_threshold, float intensity_threshold) {
+  return PhotoMaps{reinterpret_cast<const float4 *>(vertex1), reinterpret_cast<const float4 *>(intensity1),
+                   reinterpret_cast<const float4 *>(vertex2), reinterpret_cast<const float4 *>(intensity2), distance_threshold,
+                   intensity_threshold};
 }
 
-struct RgbdMaps {
-  const float4 *v1, *n1, *g1, *v2, *n2, *g2;
-};
-
-int photo_reduce_launch(const RgbdMaps &m, const float *r, const float *t, const double *pose64, const int *state, int batch,
-                        int h, int w, int stride, int max_slabs, IcpCam cam, float dist_thr, float int_thr, double *slabs,
-                        hipStream_t s) {
-  int ws;
-  const int samples = icp_samples(h, w, stride, &ws), nslabs = ceil_div(samples, ICP_SLAB);
-  hipLaunchKernelGGL(photo_reduce_kernel, dim3((unsigned)nslabs, (unsigned)batch), dim3(ICP_THREADS), 0, s, m.v1, m.g1, m.v2, m.g2,
-                     r, t, pose64, state, h, w, stride, ws, samples, max_slabs, cam, dist_thr, int_thr, slabs);
+int photo_reduce_launch(const PhotoMaps &m, const IcpReduceJob &job, int batch, hipStream_t s) {
+  hipLaunchKernelGGL(photo_reduce_kernel, dim3((unsigned)job.nslabs, (unsigned)batch), dim3(ICP_THREADS), 0, s, m.vertex1,
+                     m.inten1, m.vertex2, m.inten2, job.r, job.t, job.pose64, job.state, job.h, job.w, job.stride, job.ws,
+                     job.samples, job.max_slabs, job.cam, m.dist_thr, m.int_thr, job.slabs);
   return mi_launch_status();
 }
 
-// one joint linearisation from the workspace's pose: K18r, K21r (when `photo`), then K21s in `mode`
-int rgbd_linearise_launch(const RgbdMaps &m, int batch, int h, int w, int stride, IcpCam cam, float dist_thr, float cos_thr,
-                          float int_thr, bool photo, double w2, int mode, int min_count, const RgbdWork &k, RgbdOut out,
-                          hipStream_t s) {
-  int ws;
-  const int nslabs = ceil_div(icp_samples(h, w, stride, &ws), ICP_SLAB);
-  const int *state = mode == RGBD_MODE_STEP ? k.state : nullptr;
-  if (const int e = icp_reduce_launch(m.v1, m.n1, m.v2, m.n2, nullptr, nullptr, k.pose, state, batch, h, w, stride, k.max_slabs,
-                                      cam, dist_thr * dist_thr, cos_thr, k.slabs_g, s))
-    return e;
-  if (photo)
-    if (const int e = photo_reduce_launch(m, nullptr, nullptr, k.pose, state, batch, h, w, stride, k.max_slabs, cam, dist_thr,
-                                          int_thr, k.slabs_p, s))
-      return e;
-  hipLaunchKernelGGL(rgbd_solve_kernel, dim3((unsigned)batch), dim3(64), 0, s, k.slabs_g, photo ? k.slabs_p : nullptr, nslabs,
-                     k.max_slabs, mode, min_count, w2, k.pose, k.state, k.steps, out);
+int rgbd_solve_launch(const double *slabs_g, const double *slabs_p, const IcpReduceJob &job, int batch, int mode, int min_count,
+                      double w2, const IcpWork &k, RgbdOut out, hipStream_t s) {
+  hipLaunchKernelGGL(rgbd_solve_kernel, dim3((unsigned)batch), dim3(64), 0, s, slabs_g, slabs_p, job.nslabs, job.max_slabs, mode,
+                     min_count, w2, k.pose, k.state, k.steps, out);
   return mi_launch_status();
 }
-
-bool aligned16(const void *p) { return ((uintptr_t)p % 16) == 0; }
 
 }  // namespace
 
@@ -263,7 +189,7 @@ extern "C" int mi_intensity_maps(const void *gray, int gray_is_u8, int batch, in
   MI_ENTER();
   if (!gray || !intensity_out) return MI_E_NULL;
   if (const int s = icp_shape_status(batch, h, w)) return s;
-  if (!aligned16(intensity_out)) return MI_E_ALIGN;
+  if (!mi_aligned16({intensity_out})) return MI_E_ALIGN;
   const long long total = (long long)batch * h * w;
   const dim3 grid((unsigned)((total + 255) / 256));
   float4 *o = reinterpret_cast<float4 *>(intensity_out);
@@ -278,7 +204,7 @@ extern "C" int mi_intensity_maps(const void *gray, int gray_is_u8, int batch, in
 
 extern "C" size_t mi_rgbd_workspace_bytes(int batch, int h, int w) {
   if (icp_shape_status(batch, h, w) != MI_OK) return 0;
-  return rgbd_carve(nullptr, batch, h, w).total;
+  return icp_carve(nullptr, batch, h, w, 2).total;
 }
 
 extern "C" int mi_photo_linearise(const float *vertex1, const float *intensity1, const float *vertex2, const float *intensity2,
@@ -291,24 +217,17 @@ extern "C" int mi_photo_linearise(const float *vertex1, const float *intensity1,
   if (!icp_stride_ok(stride)) return MI_E_PARAM;
   if (const int s = icp_gate_status(fx, fy, cx, cy, distance_threshold, 1.0f)) return s;   // no angle gate here
   if (!icp_positive(intensity_threshold)) return MI_E_PARAM;
-  if (!aligned16(workspace) || !aligned16(vertex1) || !aligned16(intensity1) || !aligned16(vertex2) || !aligned16(intensity2))
-    return MI_E_ALIGN;
+  if (!mi_aligned16({workspace, vertex1, intensity1, vertex2, intensity2})) return MI_E_ALIGN;
   if (workspace_bytes < mi_rgbd_workspace_bytes(batch, h, w)) return MI_E_CAPACITY;
-  const RgbdWork k = rgbd_carve(workspace, batch, h, w);
+  const IcpWork k = icp_carve(workspace, batch, h, w, 2);
   hipStream_t s = (hipStream_t)stream;
-  RgbdMaps m = {};
-  m.v1 = reinterpret_cast<const float4 *>(vertex1); m.g1 = reinterpret_cast<const float4 *>(intensity1);
-  m.v2 = reinterpret_cast<const float4 *>(vertex2); m.g2 = reinterpret_cast<const float4 *>(intensity2);
-  if (const int e = photo_reduce_launch(m, r, t, nullptr, nullptr, batch, h, w, stride, k.max_slabs, IcpCam{fx, fy, cx, cy},
-                                        distance_threshold, intensity_threshold, k.slabs_p, s))
+  const IcpReduceJob job = icp_reduce_job(r, t, nullptr, nullptr, h, w, stride, IcpCam{fx, fy, cx, cy}, k.max_slabs, k.slabs[1]);
+  if (const int e = photo_reduce_launch(photo_maps(vertex1, intensity1, vertex2, intensity2, distance_threshold, intensity_threshold),
+                                        job, batch, s))
     return e;
-  int ws;
-  const int nslabs = ceil_div(icp_samples(h, w, stride, &ws), ICP_SLAB);
   RgbdOut out = {};
   out.sums = sums;
-  hipLaunchKernelGGL(rgbd_solve_kernel, dim3((unsigned)batch), dim3(64), 0, s, nullptr, k.slabs_p, nslabs, k.max_slabs,
-                     RGBD_MODE_SUMS, 0, 0.0, k.pose, k.state, k.steps, out);
-  return mi_launch_status();
+  return rgbd_solve_launch(nullptr, k.slabs[1], job, batch, ICP_MODE_SUMS, 0, 0.0, k, out, s);
 }
 
 extern "C" int mi_rgbd_refine(const float *vertex1, const float *normal1, const float *intensity1, const float *vertex2,
@@ -323,38 +242,28 @@ extern "C" int mi_rgbd_refine(const float *vertex1, const float *normal1, const 
       !t || !information || !rmse || !count || !rmse_photo || !count_photo || !steps || !ok || !workspace)
     return MI_E_NULL;
   if (const int s = icp_shape_status(batch, h, w)) return s;
-  if (stages < 1 || stages > MI_ICP_MAX_STAGES || min_correspondences < 1) return MI_E_PARAM;
-  int all = 0;
-  for (int i = 0; i < stages; ++i) {
-    if (!icp_stride_ok(strides[i]) || iterations[i] < 0 || iterations[i] > MI_ICP_MAX_ITERATIONS) return MI_E_PARAM;
-    all += iterations[i];
-  }
-  if (all > MI_ICP_MAX_ITERATIONS) return MI_E_PARAM;
+  if (const int s = icp_schedule_status(strides, iterations, stages, min_correspondences)) return s;
   if (const int s = icp_gate_status(fx, fy, cx, cy, distance_threshold, angle_threshold)) return s;
   if (!(photo_weight >= 0.0f) || !(photo_weight < INFINITY) || !icp_positive(intensity_threshold)) return MI_E_PARAM;
-  if (!aligned16(workspace) || !aligned16(vertex1) || !aligned16(normal1) || !aligned16(intensity1) || !aligned16(vertex2) ||
-      !aligned16(normal2) || !aligned16(intensity2))
-    return MI_E_ALIGN;
+  if (!mi_aligned16({workspace, vertex1, normal1, intensity1, vertex2, normal2, intensity2})) return MI_E_ALIGN;
   if (workspace_bytes < mi_rgbd_workspace_bytes(batch, h, w)) return MI_E_CAPACITY;
-  const RgbdWork k = rgbd_carve(workspace, batch, h, w);
+  const IcpWork k = icp_carve(workspace, batch, h, w, 2);
   hipStream_t s = (hipStream_t)stream;
-  RgbdMaps m;
-  m.v1 = reinterpret_cast<const float4 *>(vertex1); m.n1 = reinterpret_cast<const float4 *>(normal1);
-  m.g1 = reinterpret_cast<const float4 *>(intensity1); m.v2 = reinterpret_cast<const float4 *>(vertex2);
-  m.n2 = reinterpret_cast<const float4 *>(normal2); m.g2 = reinterpret_cast<const float4 *>(intensity2);
-  const IcpCam cam{fx, fy, cx, cy};
-  const float cos_thr = (float)cos((double)angle_threshold);
+  const IcpMaps geo = icp_maps(vertex1, normal1, vertex2, normal2, distance_threshold, angle_threshold);
+  const PhotoMaps pho = photo_maps(vertex1, intensity1, vertex2, intensity2, distance_threshold, intensity_threshold);
   const bool photo = photo_weight != 0.0f;
   const double w2 = photo_weight2(photo_weight);
   if (const int e = icp_init_launch(r0, t0, batch, k.pose, k.state, k.steps, s)) return e;
-  RgbdOut out = {};
-  for (int st = 0; st < stages; ++st)
-    for (int it = 0; it < iterations[st]; ++it)
-      if (const int e = rgbd_linearise_launch(m, batch, h, w, strides[st], cam, distance_threshold, cos_thr, intensity_threshold,
-                                              photo, w2, RGBD_MODE_STEP, min_correspondences, k, out, s))
-        return e;
-  out.r = r; out.t = t; out.information = information; out.rmse = rmse; out.count = count; out.rmse_photo = rmse_photo;
-  out.count_photo = count_photo; out.steps = steps; out.ok = ok;
-  return rgbd_linearise_launch(m, batch, h, w, strides[stages - 1], cam, distance_threshold, cos_thr, intensity_threshold, photo,
-                               w2, RGBD_MODE_FINAL, min_correspondences, k, out, s);
+  const RgbdOut out{r, t, information, rmse, rmse_photo, count, count_photo, steps, ok, nullptr};
+  // one joint linearisation from the workspace's pose: K18r, K21r (when `photo`), then K21s in `mode`
+  return icp_refine_drive(strides, iterations, stages, [&](int stride, int mode) {
+    IcpReduceJob job = icp_reduce_job(nullptr, nullptr, k.pose, mode == ICP_MODE_STEP ? k.state : nullptr, h, w, stride,
+                                      IcpCam{fx, fy, cx, cy}, k.max_slabs, k.slabs[0]);
+    if (const int e = icp_reduce_launch(geo, job, batch, s)) return e;
+    job.slabs = k.slabs[1];
+    if (photo)
+      if (const int e = photo_reduce_launch(pho, job, batch, s)) return e;
+    return rgbd_solve_launch(k.slabs[0], photo ? k.slabs[1] : nullptr, job, batch, mode, min_correspondences, w2, k,
+                             mode == ICP_MODE_FINAL ? out : RgbdOut{}, s);
+  });
 }

@@ -23,6 +23,7 @@
 // graph replay; every output element is written.  Built with -ffp-contract=off.
 #include "common.h"
 #include "surface_math.h"
+#include "tsdf_shared.h"
 
 #include <math.h>
 
@@ -305,16 +306,13 @@ __global__ __launch_bounds__(256) void surface_emit_kernel(const float2 *__restr
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-bool surface_positive(float v) { return v > 0.0f && v < INFINITY; }
-bool surface_finite(float v) { return fabsf(v) < INFINITY; }
 size_t surface_align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
-// K19's volume checks, and ids that fit int32: 12 * voxels of one volume < 2^31
+// K19's volume checks (tsdf_shared.h), and ids that fit int32: 12 * voxels of one volume < 2^31.  The id bound comes after
+// K19's batch bound here and still wins over it: a batch above 65535 of volumes that large fails K19's element bound first.
 int surface_volume_status(int batch, int nz, int ny, int nx) {
-  if (batch < 1 || nz < 2 || ny < 2 || nx < 2) return MI_E_SHAPE;
-  if ((double)batch * (double)nz * (double)ny * (double)nx >= 2147483648.0) return MI_E_SHAPE;
+  if (const int s = tsdf_volume_status(batch, nz, ny, nx)) return s;
   if (12.0 * (double)nz * (double)ny * (double)nx >= 2147483648.0) return MI_E_SHAPE;
-  if (batch > 65535) return MI_E_PARAM;
   return MI_OK;
 }
 
@@ -335,11 +333,11 @@ extern "C" int mi_tsdf_surface(const float *volume, int batch, int nz, int ny, i
   if ((!vertex_out && max_vertices != 0) || (!triangle_out && max_triangles != 0)) return MI_E_NULL;
   if (const int s = surface_volume_status(batch, nz, ny, nx)) return s;
   if ((double)batch * (double)max_vertices >= 2147483648.0 || (double)batch * (double)max_triangles >= 2147483648.0) return MI_E_SHAPE;
-  if (!surface_finite(origin_x) || !surface_finite(origin_y) || !surface_finite(origin_z) || !surface_positive(voxel_size) ||
-      !surface_positive(min_weight) || max_vertices < 0 || max_triangles < 0)
+  if (tsdf_origin_status(origin_x, origin_y, origin_z, voxel_size) != MI_OK || !tsdf_positive(min_weight) || max_vertices < 0 ||
+      max_triangles < 0)
     return MI_E_PARAM;
-  if (((uintptr_t)volume % 16) != 0 || ((uintptr_t)vertex_out % 16) != 0 || ((uintptr_t)normal_out % 16) != 0 ||
-      ((uintptr_t)triangle_out % 4) != 0 || ((uintptr_t)counts_out % 4) != 0 || ((uintptr_t)workspace % 16) != 0)
+  if (!mi_aligned16({volume, vertex_out, normal_out, workspace}) || ((uintptr_t)triangle_out % 4) != 0 ||
+      ((uintptr_t)counts_out % 4) != 0)
     return MI_E_ALIGN;
   if (workspace_bytes < mi_tsdf_surface_workspace_bytes(batch, nz, ny, nx)) return MI_E_CAPACITY;
 

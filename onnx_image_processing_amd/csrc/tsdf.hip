@@ -13,21 +13,16 @@
 //       over the fixed grid of depths, restricted to the range of k whose samples can lie inside the volume's box (the
 //       slab test, widened by two samples); a sample is four 16-byte loads (two x-adjacent corners each).
 // K19c  tsdf_compose_kernel    one thread per pose pair.
+// This file's own: the kernels above and the entry points.  Shared with K22 and K20 through tsdf_shared.h: the grid and camera
+// structs and every host check of a volume, a grid, a depth range and an integration.
 // No atomics, no memset, nothing allocated; every output element is written.  Built with -ffp-contract=off.
 #include "common.h"
 #include "tsdf_math.h"
+#include "tsdf_shared.h"
 
 #include <math.h>
 
 namespace {
-
-struct TsdfGrid {
-  int nx, ny, nz;
-  float origin[3], voxel_size, truncation;
-};
-struct TsdfCam {
-  float fx, fy, cx, cy, z_scale, min_depth, max_depth;
-};
 
 // ---- K19z ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tsdf_reset_kernel(float *__restrict__ vol, long long voxels) {
@@ -154,32 +149,15 @@ __global__ __launch_bounds__(64) void tsdf_compose_kernel(const float *__restric
   for (int e = 0; e < 3; ++e) t[(size_t)b * 3 + e] = to[e];
 }
 
-// ---- host ------------------------------------------------------------------------------------------------------------------
-bool tsdf_positive(float v) { return v > 0.0f && v < INFINITY; }
-bool tsdf_finite(float v) { return fabsf(v) < INFINITY; }
-
-int tsdf_volume_status(int batch, int nz, int ny, int nx) {
-  if (batch < 1 || nz < 2 || ny < 2 || nx < 2) return MI_E_SHAPE;
-  if ((double)batch * (double)nz * (double)ny * (double)nx >= 2147483648.0) return MI_E_SHAPE;
-  if (batch > 65535) return MI_E_PARAM;
-  return MI_OK;
-}
-int tsdf_grid_status(float ox, float oy, float oz, float voxel_size, float truncation) {
-  if (!tsdf_finite(ox) || !tsdf_finite(oy) || !tsdf_finite(oz) || !tsdf_positive(voxel_size) || !tsdf_positive(truncation))
-    return MI_E_PARAM;
-  return MI_OK;
-}
-bool tsdf_depth_range_ok(float min_depth, float max_depth) {
-  return min_depth > 0.0f && max_depth >= min_depth && max_depth < INFINITY;
-}
-
 }  // namespace
+
+// ---- host (the checks are tsdf_shared.h's) -----------------------------------------------------------------------------------
 
 extern "C" int mi_tsdf_reset(float *volume, int batch, int nz, int ny, int nx, mi_stream_t stream) {
   MI_ENTER();
   if (!volume) return MI_E_NULL;
   if (const int s = tsdf_volume_status(batch, nz, ny, nx)) return s;
-  if (((uintptr_t)volume % 16) != 0) return MI_E_ALIGN;
+  if (!mi_aligned16({volume})) return MI_E_ALIGN;
   const long long voxels = (long long)batch * nz * ny * nx, threads = (voxels >> 1) + 1;
   hipLaunchKernelGGL(tsdf_reset_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, volume, voxels);
   return mi_launch_status();
@@ -193,15 +171,12 @@ extern "C" int mi_tsdf_integrate(float *volume, int batch, int nz, int ny, int n
   MI_ENTER();
   if (!volume || !depth || !r || !t) return MI_E_NULL;
   if (const int s = tsdf_volume_status(batch, nz, ny, nx)) return s;
-  if (frames < 1 || h < 3 || w < 3) return MI_E_SHAPE;
-  if ((double)batch * (double)frames * (double)h * (double)w >= 2147483648.0) return MI_E_SHAPE;
+  if (const int s = tsdf_frames_status(batch, frames, h, w)) return s;
   if (const int s = tsdf_grid_status(origin_x, origin_y, origin_z, voxel_size, truncation)) return s;
-  if (!tsdf_positive(max_weight) || !tsdf_positive(fx) || !tsdf_positive(fy) || !tsdf_finite(cx) || !tsdf_finite(cy) ||
-      !tsdf_positive(z_scale) || !tsdf_depth_range_ok(min_depth, max_depth))
-    return MI_E_PARAM;
-  if (((uintptr_t)volume % 16) != 0) return MI_E_ALIGN;
-  const TsdfGrid g{nx, ny, nz, {origin_x, origin_y, origin_z}, voxel_size, truncation};
   const TsdfCam cam{fx, fy, cx, cy, z_scale, min_depth, max_depth};
+  if (const int s = tsdf_fusion_status(max_weight, cam)) return s;
+  if (!mi_aligned16({volume})) return MI_E_ALIGN;
+  const TsdfGrid g{nx, ny, nz, {origin_x, origin_y, origin_z}, voxel_size, truncation};
   const dim3 grid((unsigned)ceil_div(nz * ny, 4), (unsigned)batch);
   float2 *vol = reinterpret_cast<float2 *>(volume);
   if (depth_is_u16)
@@ -227,7 +202,7 @@ extern "C" int mi_tsdf_raycast(const float *volume, int batch, int nz, int ny, i
   const float step = step_fraction * truncation;
   const float count = ceilf((max_depth - min_depth) / step);
   if (!tsdf_positive(step) || !(count < 16777216.0f)) return MI_E_PARAM;   // k must stay exact in float32
-  if (((uintptr_t)volume % 16) != 0 || ((uintptr_t)vertex_out % 16) != 0 || ((uintptr_t)normal_out % 16) != 0) return MI_E_ALIGN;
+  if (!mi_aligned16({volume, vertex_out, normal_out})) return MI_E_ALIGN;
   const TsdfGrid g{nx, ny, nz, {origin_x, origin_y, origin_z}, voxel_size, truncation};
   const dim3 grid((unsigned)ceil_div(w, 16), (unsigned)ceil_div(h, 16), (unsigned)batch);
   hipLaunchKernelGGL(tsdf_raycast_kernel, grid, dim3(256), 0, (hipStream_t)stream, volume, g, step, (int)count, min_depth, r, t, h,

@@ -11,21 +11,16 @@
 //       depth sample's own pixel.  Four instances: depth float / uint16 x gray float / uint8.
 // K22s  tsdf_sample_gray_kernel     grid (ceil(n / 256), batch), one thread per point on a linear index (neighbouring points of
 //       a raycast row or of a mesh are neighbours in the volume); a point is four 16-byte loads (two x-adjacent corners each).
+// This file's own: the kernels above and the entry points.  K19's, through tsdf_shared.h: the grid and camera structs and
+// every host check of a volume, a grid, a depth range and an integration.
 // No atomics, no memset, nothing allocated; every output element is written.  Built with -ffp-contract=off.
 #include "common.h"
 #include "tsdf_gray_math.h"
+#include "tsdf_shared.h"
 
 #include <math.h>
 
 namespace {
-
-struct GrayGrid {
-  int nx, ny, nz;
-  float origin[3], voxel_size, truncation;
-};
-struct GrayCam {
-  float fx, fy, cx, cy, z_scale, min_depth, max_depth;
-};
 
 // ---- K22z ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tsdf_gray_reset_kernel(float *__restrict__ ivol, long long voxels) {
@@ -36,10 +31,10 @@ __global__ __launch_bounds__(256) void tsdf_gray_reset_kernel(float *__restrict_
 
 // ---- K22i ------------------------------------------------------------------------------------------------------------------
 template <typename D, typename G>
-__global__ __launch_bounds__(256) void tsdf_integrate_gray_kernel(float2 *__restrict__ vol, float2 *__restrict__ ivol, GrayGrid g,
+__global__ __launch_bounds__(256) void tsdf_integrate_gray_kernel(float2 *__restrict__ vol, float2 *__restrict__ ivol, TsdfGrid g,
                                                                   float max_weight, const D *__restrict__ depth,
                                                                   const G *__restrict__ gray, int frames, int h, int w,
-                                                                  GrayCam cam, const float *__restrict__ r,
+                                                                  TsdfCam cam, const float *__restrict__ r,
                                                                   const float *__restrict__ t,
                                                                   const uint8_t *__restrict__ active) {
   const int b = blockIdx.y, lane = threadIdx.x & 63;
@@ -82,7 +77,7 @@ __global__ __launch_bounds__(256) void tsdf_integrate_gray_kernel(float2 *__rest
 }
 
 // ---- K22s ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void tsdf_sample_gray_kernel(const float *__restrict__ ivol, GrayGrid g,
+__global__ __launch_bounds__(256) void tsdf_sample_gray_kernel(const float *__restrict__ ivol, TsdfGrid g,
                                                                const float4 *__restrict__ points, int n,
                                                                const float *__restrict__ r, const float *__restrict__ t,
                                                                float4 *__restrict__ out) {
@@ -110,21 +105,10 @@ __global__ __launch_bounds__(256) void tsdf_sample_gray_kernel(const float *__re
   out[o] = res;
 }
 
-// ---- host ------------------------------------------------------------------------------------------------------------------
-bool gray_positive(float v) { return v > 0.0f && v < INFINITY; }
-bool gray_finite(float v) { return fabsf(v) < INFINITY; }
-
-// K19's checks, word for word (tsdf.hip)
-int gray_volume_status(int batch, int nz, int ny, int nx) {
-  if (batch < 1 || nz < 2 || ny < 2 || nx < 2) return MI_E_SHAPE;
-  if ((double)batch * (double)nz * (double)ny * (double)nx >= 2147483648.0) return MI_E_SHAPE;
-  if (batch > 65535) return MI_E_PARAM;
-  return MI_OK;
-}
-
+// ---- host (the checks are K19's own: tsdf_shared.h) ---------------------------------------------------------------------------
 template <typename D>
-void launch_integrate_gray(dim3 grid, hipStream_t stream, float2 *vol, float2 *ivol, const GrayGrid &g, float max_weight,
-                           const D *depth, const void *gray, int gray_is_u8, int frames, int h, int w, const GrayCam &cam,
+void launch_integrate_gray(dim3 grid, hipStream_t stream, float2 *vol, float2 *ivol, const TsdfGrid &g, float max_weight,
+                           const D *depth, const void *gray, int gray_is_u8, int frames, int h, int w, const TsdfCam &cam,
                            const float *r, const float *t, const uint8_t *active) {
   if (gray_is_u8)
     hipLaunchKernelGGL((tsdf_integrate_gray_kernel<D, uint8_t>), grid, dim3(256), 0, stream, vol, ivol, g, max_weight, depth,
@@ -139,8 +123,8 @@ void launch_integrate_gray(dim3 grid, hipStream_t stream, float2 *vol, float2 *i
 extern "C" int mi_tsdf_gray_reset(float *intensity_volume, int batch, int nz, int ny, int nx, mi_stream_t stream) {
   MI_ENTER();
   if (!intensity_volume) return MI_E_NULL;
-  if (const int s = gray_volume_status(batch, nz, ny, nx)) return s;
-  if (((uintptr_t)intensity_volume % 16) != 0) return MI_E_ALIGN;
+  if (const int s = tsdf_volume_status(batch, nz, ny, nx)) return s;
+  if (!mi_aligned16({intensity_volume})) return MI_E_ALIGN;
   const long long voxels = (long long)batch * nz * ny * nx, threads = (voxels >> 1) + 1;
   hipLaunchKernelGGL(tsdf_gray_reset_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      intensity_volume, voxels);
@@ -155,18 +139,13 @@ extern "C" int mi_tsdf_integrate_gray(float *volume, float *intensity_volume, in
                                       mi_stream_t stream) {
   MI_ENTER();
   if (!volume || !intensity_volume || !depth || !gray || !r || !t) return MI_E_NULL;
-  if (const int s = gray_volume_status(batch, nz, ny, nx)) return s;
-  if (frames < 1 || h < 3 || w < 3) return MI_E_SHAPE;
-  if ((double)batch * (double)frames * (double)h * (double)w >= 2147483648.0) return MI_E_SHAPE;
-  if (!gray_finite(origin_x) || !gray_finite(origin_y) || !gray_finite(origin_z) || !gray_positive(voxel_size) ||
-      !gray_positive(truncation))
-    return MI_E_PARAM;
-  if (!gray_positive(max_weight) || !gray_positive(fx) || !gray_positive(fy) || !gray_finite(cx) || !gray_finite(cy) ||
-      !gray_positive(z_scale) || !(min_depth > 0.0f && max_depth >= min_depth && max_depth < INFINITY))
-    return MI_E_PARAM;
-  if (((uintptr_t)volume % 16) != 0 || ((uintptr_t)intensity_volume % 16) != 0) return MI_E_ALIGN;
-  const GrayGrid g{nx, ny, nz, {origin_x, origin_y, origin_z}, voxel_size, truncation};
-  const GrayCam cam{fx, fy, cx, cy, z_scale, min_depth, max_depth};
+  if (const int s = tsdf_volume_status(batch, nz, ny, nx)) return s;
+  if (const int s = tsdf_frames_status(batch, frames, h, w)) return s;
+  if (const int s = tsdf_grid_status(origin_x, origin_y, origin_z, voxel_size, truncation)) return s;
+  const TsdfCam cam{fx, fy, cx, cy, z_scale, min_depth, max_depth};
+  if (const int s = tsdf_fusion_status(max_weight, cam)) return s;
+  if (!mi_aligned16({volume, intensity_volume})) return MI_E_ALIGN;
+  const TsdfGrid g{nx, ny, nz, {origin_x, origin_y, origin_z}, voxel_size, truncation};
   const dim3 grid((unsigned)ceil_div(nz * ny, 4), (unsigned)batch);
   float2 *vol = reinterpret_cast<float2 *>(volume), *ivol = reinterpret_cast<float2 *>(intensity_volume);
   if (depth_is_u16)
@@ -183,12 +162,11 @@ extern "C" int mi_tsdf_sample_gray(const float *intensity_volume, int batch, int
                                    float *intensity_out, mi_stream_t stream) {
   MI_ENTER();
   if (!intensity_volume || !points || !intensity_out || (r == nullptr) != (t == nullptr)) return MI_E_NULL;
-  if (const int s = gray_volume_status(batch, nz, ny, nx)) return s;
+  if (const int s = tsdf_volume_status(batch, nz, ny, nx)) return s;
   if (n < 1 || (double)batch * (double)n >= 2147483648.0) return MI_E_SHAPE;
-  if (!gray_finite(origin_x) || !gray_finite(origin_y) || !gray_finite(origin_z) || !gray_positive(voxel_size)) return MI_E_PARAM;
-  if (((uintptr_t)intensity_volume % 16) != 0 || ((uintptr_t)points % 16) != 0 || ((uintptr_t)intensity_out % 16) != 0)
-    return MI_E_ALIGN;
-  const GrayGrid g{nx, ny, nz, {origin_x, origin_y, origin_z}, voxel_size, 0.0f};
+  if (const int s = tsdf_origin_status(origin_x, origin_y, origin_z, voxel_size)) return s;
+  if (!mi_aligned16({intensity_volume, points, intensity_out})) return MI_E_ALIGN;
+  const TsdfGrid g{nx, ny, nz, {origin_x, origin_y, origin_z}, voxel_size, 0.0f};
   const dim3 grid((unsigned)(((long long)n + 255) / 256), (unsigned)batch);
   hipLaunchKernelGGL(tsdf_sample_gray_kernel, grid, dim3(256), 0, (hipStream_t)stream, intensity_volume, g,
                      reinterpret_cast<const float4 *>(points), n, r, t, reinterpret_cast<float4 *>(intensity_out));

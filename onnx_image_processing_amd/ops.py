@@ -1680,26 +1680,53 @@ def surfel_maps(depth: torch.Tensor, k_inv: torch.Tensor, z_scale: float = 1.0, 
     return vertex, normal
 
 
-def _icp_inputs(maps1, maps2, r: torch.Tensor, t: torch.Tensor, camera, what: str):
-    v1, n1 = maps1
-    v2, n2 = maps2
-    if not v1.is_cuda:
-        raise RuntimeError(f"{what}: the maps must live on the GPU (got device {v1.device}); this package has no CPU path")
-    if v1.dim() != 4 or v1.shape[-1] != 4 or any(x.shape != v1.shape or x.dtype != F32 for x in (n1, v2, n2)):
-        raise RuntimeError(f"{what}: the four maps must be float32 (B, H, W, 4) of one shape, got {tuple(v1.shape)}, "
-                           f"{tuple(n1.shape)}, {tuple(v2.shape)}, {tuple(n2.shape)}")
-    b, h, w = int(v1.shape[0]), int(v1.shape[1]), int(v1.shape[2])
+def _rgbd_inputs(named_maps, r: torch.Tensor, t: torch.Tensor, camera, what: str, workspace: str):
+    """The checks and conversions every dense linearisation / refinement shares.  named_maps: [(name, (B, H, W, 4) float32
+    map)]; workspace: the entry that sizes the call's workspace (`mi_icp_workspace_bytes` or `mi_rgbd_workspace_bytes`)."""
+    first = named_maps[0][1]
+    if not first.is_cuda:
+        raise RuntimeError(f"{what}: the maps must live on the GPU (got device {first.device}); this package has no CPU path")
+    if first.dim() != 4 or first.shape[-1] != 4 or any(x.shape != first.shape or x.dtype != F32 for _, x in named_maps):
+        raise RuntimeError(f"{what}: the maps must be float32 (B, H, W, 4) of one shape, got "
+                           + ", ".join(f"{n} {x.dtype} {tuple(x.shape)}" for n, x in named_maps))
+    b, h, w = int(first.shape[0]), int(first.shape[1]), int(first.shape[2])
     rr, tt = r.float().contiguous(), t.float().contiguous()
     if tuple(rr.shape) != (b, 3, 3) or tuple(tt.shape) != (b, 3):
         raise RuntimeError(f"{what}: the pose must be ({b}, 3, 3) and ({b}, 3), got {tuple(r.shape)} and {tuple(t.shape)}")
-    keep = tuple(x.contiguous() for x in (v1, n1, v2, n2))
-    maps = tuple(N.dev(x, F32, "maps") for x in keep)
-    fx, fy, cx, cy = (float(x) for x in camera)
-    wbytes = int(N.load().mi_icp_workspace_bytes(b, h, w))
+    keep = tuple(x.contiguous() for _, x in named_maps)
+    maps = tuple(N.dev(x, F32, n) for (n, _), x in zip(named_maps, keep))
+    cam = tuple(float(x) for x in camera)
+    if len(cam) != 4:
+        raise RuntimeError(f"{what}: camera must be (fx, fy, cx, cy), got {camera!r}")
+    wbytes = int(getattr(N.load(), workspace)(b, h, w))
     if wbytes == 0:
         raise RuntimeError(f"{what}: unsupported request (batch {b}, {h} x {w})")
-    work = torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=v1.device)
-    return keep, maps, rr, tt, (fx, fy, cx, cy), b, h, w, work, wbytes
+    work = torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=first.device)
+    return keep, maps, rr, tt, cam, b, h, w, work, wbytes
+
+
+def _surfel_named(maps1, maps2):
+    (v1, n1), (v2, n2) = maps1, maps2
+    return [("vertex1", v1), ("normal1", n1), ("vertex2", v2), ("normal2", n2)]
+
+
+def _icp_schedule(schedule, what: str):
+    """schedule of (stride, iterations) stages -> (strides, iterations, stages): the two c_int32 arrays as the pointers the
+    C ABI takes (each keeps its array alive) and their length"""
+    import ctypes
+    sched = [(int(s), int(i)) for s, i in schedule]
+    if not 1 <= len(sched) <= ICP_MAX_STAGES:
+        raise RuntimeError(f"{what}: the schedule needs 1 .. {ICP_MAX_STAGES} stages, got {len(sched)}")
+    strides = (ctypes.c_int32 * len(sched))(*[s for s, _ in sched])
+    iters = (ctypes.c_int32 * len(sched))(*[i for _, i in sched])
+    return ctypes.cast(strides, ctypes.c_void_p), ctypes.cast(iters, ctypes.c_void_p), len(sched)
+
+
+def _refine_outputs(b: int, dev):
+    """the outputs every refinement has: r, t, information, rmse, count, steps, ok (uint8)"""
+    return (torch.empty((b, 3, 3), dtype=F32, device=dev), torch.empty((b, 3), dtype=F32, device=dev),
+            torch.empty((b, 6, 6), dtype=F32, device=dev), torch.empty((b,), dtype=F32, device=dev),
+            torch.empty((b,), dtype=I32, device=dev), torch.empty((b,), dtype=I32, device=dev), torch.empty((b,), dtype=U8, device=dev))
 
 
 def icp_linearise(maps1, maps2, r: torch.Tensor, t: torch.Tensor, camera, stride: int = 1, distance_threshold: float = 0.1,
@@ -1707,7 +1734,8 @@ def icp_linearise(maps1, maps2, r: torch.Tensor, t: torch.Tensor, camera, stride
     """`mi_icp_linearise`: one point-to-plane linearisation of frame 1's surfels (maps1 = (vertex, normal) of `surfel_maps`)
     against frame 2's at the pose r (B, 3, 3), t (B, 3), camera = (fx, fy, cx, cy), over every stride-th source pixel ->
     sums (B, 29) float64: A's upper triangle row-major (21), b (6), sum r^2, count.  angle_threshold in radians."""
-    keep, maps, rr, tt, cam, b, h, w, work, wbytes = _icp_inputs(maps1, maps2, r, t, camera, "icp_linearise")
+    keep, maps, rr, tt, cam, b, h, w, work, wbytes = _rgbd_inputs(_surfel_named(maps1, maps2), r, t, camera, "icp_linearise",
+                                                                  "mi_icp_workspace_bytes")
     sums = torch.empty((b, ICP_SUMS), dtype=torch.float64, device=rr.device)
     N.call("mi_icp_linearise", *maps, N.dev(rr, F32, "r"), N.dev(tt, F32, "t"), b, h, w, *cam, int(stride),
            float(distance_threshold), float(angle_threshold), sums.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
@@ -1719,25 +1747,13 @@ def icp_refine(maps1, maps2, r0: torch.Tensor, t0: torch.Tensor, camera, schedul
     """`mi_icp_refine`: projective point-to-plane ICP from (r0, t0) over the schedule's (stride, iterations) stages ->
     (R (B, 3, 3), t (B, 3), information (B, 6, 6) float32, rmse (B,) float32, count (B,) int32, steps (B,) int32,
     ok (B,) bool).  X2 = R X1 + t.  A pair whose system is degenerate keeps the pose before the failed solve, ok = False."""
-    import ctypes
-    keep, maps, rr, tt, cam, b, h, w, work, wbytes = _icp_inputs(maps1, maps2, r0, t0, camera, "icp_refine")
-    sched = [(int(s), int(i)) for s, i in schedule]
-    if not 1 <= len(sched) <= ICP_MAX_STAGES:
-        raise RuntimeError(f"icp_refine: the schedule needs 1 .. {ICP_MAX_STAGES} stages, got {len(sched)}")
-    strides = (ctypes.c_int32 * len(sched))(*[s for s, _ in sched])
-    iters = (ctypes.c_int32 * len(sched))(*[i for _, i in sched])
-    dev = rr.device
-    r = torch.empty((b, 3, 3), dtype=F32, device=dev)
-    t = torch.empty((b, 3), dtype=F32, device=dev)
-    info = torch.empty((b, 6, 6), dtype=F32, device=dev)
-    rmse = torch.empty((b,), dtype=F32, device=dev)
-    count = torch.empty((b,), dtype=I32, device=dev)
-    steps = torch.empty((b,), dtype=I32, device=dev)
-    ok = torch.empty((b,), dtype=U8, device=dev)
-    N.call("mi_icp_refine", *maps, N.dev(rr, F32, "r0"), N.dev(tt, F32, "t0"), b, h, w, *cam,
-           ctypes.cast(strides, ctypes.c_void_p), ctypes.cast(iters, ctypes.c_void_p), len(sched), float(distance_threshold),
-           float(angle_threshold), int(min_correspondences), r.data_ptr(), t.data_ptr(), info.data_ptr(), rmse.data_ptr(),
-           count.data_ptr(), steps.data_ptr(), ok.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    keep, maps, rr, tt, cam, b, h, w, work, wbytes = _rgbd_inputs(_surfel_named(maps1, maps2), r0, t0, camera, "icp_refine",
+                                                                  "mi_icp_workspace_bytes")
+    strides, iters, stages = _icp_schedule(schedule, "icp_refine")
+    r, t, info, rmse, count, steps, ok = _refine_outputs(b, rr.device)
+    N.call("mi_icp_refine", *maps, N.dev(rr, F32, "r0"), N.dev(tt, F32, "t0"), b, h, w, *cam, strides, iters, stages,
+           float(distance_threshold), float(angle_threshold), int(min_correspondences), r.data_ptr(), t.data_ptr(), info.data_ptr(),
+           rmse.data_ptr(), count.data_ptr(), steps.data_ptr(), ok.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
     return r, t, info, rmse, count, steps, ok.view(torch.bool)
 
 
@@ -1760,29 +1776,6 @@ def intensity_maps(gray: torch.Tensor):
     return out
 
 
-def _rgbd_inputs(named_maps, r: torch.Tensor, t: torch.Tensor, camera, what: str):
-    first = named_maps[0][1]
-    if not first.is_cuda:
-        raise RuntimeError(f"{what}: the maps must live on the GPU (got device {first.device}); this package has no CPU path")
-    if first.dim() != 4 or first.shape[-1] != 4 or any(x.shape != first.shape or x.dtype != F32 for _, x in named_maps):
-        raise RuntimeError(f"{what}: the maps must be float32 (B, H, W, 4) of one shape, got "
-                           + ", ".join(f"{n} {x.dtype} {tuple(x.shape)}" for n, x in named_maps))
-    b, h, w = int(first.shape[0]), int(first.shape[1]), int(first.shape[2])
-    rr, tt = r.float().contiguous(), t.float().contiguous()
-    if tuple(rr.shape) != (b, 3, 3) or tuple(tt.shape) != (b, 3):
-        raise RuntimeError(f"{what}: the pose must be ({b}, 3, 3) and ({b}, 3), got {tuple(r.shape)} and {tuple(t.shape)}")
-    keep = tuple(x.contiguous() for _, x in named_maps)
-    maps = tuple(N.dev(x, F32, n) for (n, _), x in zip(named_maps, keep))
-    cam = tuple(float(x) for x in camera)
-    if len(cam) != 4:
-        raise RuntimeError(f"{what}: camera must be (fx, fy, cx, cy), got {camera!r}")
-    wbytes = int(N.load().mi_rgbd_workspace_bytes(b, h, w))
-    if wbytes == 0:
-        raise RuntimeError(f"{what}: unsupported request (batch {b}, {h} x {w})")
-    work = torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=first.device)
-    return keep, maps, rr, tt, cam, b, h, w, work, wbytes
-
-
 def photo_linearise(vertex1: torch.Tensor, intensity1: torch.Tensor, vertex2: torch.Tensor, intensity2: torch.Tensor,
                     r: torch.Tensor, t: torch.Tensor, camera, stride: int = 1, distance_threshold: float = 0.1,
                     intensity_threshold: float = 30.0):
@@ -1791,7 +1784,7 @@ def photo_linearise(vertex1: torch.Tensor, intensity1: torch.Tensor, vertex2: to
     stride-th source pixel -> sums (B, 29) float64 in `icp_linearise`'s layout.  distance_threshold is the occlusion gate
     on depth, intensity_threshold the gate on the residual in gray levels."""
     named = [("vertex1", vertex1), ("intensity1", intensity1), ("vertex2", vertex2), ("intensity2", intensity2)]
-    keep, maps, rr, tt, cam, b, h, w, work, wbytes = _rgbd_inputs(named, r, t, camera, "photo_linearise")
+    keep, maps, rr, tt, cam, b, h, w, work, wbytes = _rgbd_inputs(named, r, t, camera, "photo_linearise", "mi_rgbd_workspace_bytes")
     sums = torch.empty((b, ICP_SUMS), dtype=torch.float64, device=rr.device)
     N.call("mi_photo_linearise", *maps, N.dev(rr, F32, "r"), N.dev(tt, F32, "t"), b, h, w, *cam, int(stride),
            float(distance_threshold), float(intensity_threshold), sums.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
@@ -1806,32 +1799,19 @@ def rgbd_refine(maps1, maps2, r0: torch.Tensor, t0: torch.Tensor, camera, schedu
     system, rmse (B,) float32 and count (B,) int32 of the geometric term, rmse_photo (B,) float32 and count_photo (B,) int32
     of the photometric term, steps (B,) int32, ok (B,) bool).  photo_weight is the depth's unit per gray level; 0 gives
     `icp_refine`'s bits."""
-    import ctypes
     names = ("vertex", "normal", "intensity")
     if len(maps1) != 3 or len(maps2) != 3:
         raise RuntimeError("rgbd_refine: maps1 and maps2 must each be (vertex, normal, intensity)")
     named = [(f"{n}{i}", x) for i, maps in ((1, maps1), (2, maps2)) for n, x in zip(names, maps)]
-    keep, maps, rr, tt, cam, b, h, w, work, wbytes = _rgbd_inputs(named, r0, t0, camera, "rgbd_refine")
-    sched = [(int(s), int(i)) for s, i in schedule]
-    if not 1 <= len(sched) <= ICP_MAX_STAGES:
-        raise RuntimeError(f"rgbd_refine: the schedule needs 1 .. {ICP_MAX_STAGES} stages, got {len(sched)}")
-    strides = (ctypes.c_int32 * len(sched))(*[s for s, _ in sched])
-    iters = (ctypes.c_int32 * len(sched))(*[i for _, i in sched])
-    dev = rr.device
-    r = torch.empty((b, 3, 3), dtype=F32, device=dev)
-    t = torch.empty((b, 3), dtype=F32, device=dev)
-    info = torch.empty((b, 6, 6), dtype=F32, device=dev)
-    rmse = torch.empty((b,), dtype=F32, device=dev)
-    count = torch.empty((b,), dtype=I32, device=dev)
-    rmse_photo = torch.empty((b,), dtype=F32, device=dev)
-    count_photo = torch.empty((b,), dtype=I32, device=dev)
-    steps = torch.empty((b,), dtype=I32, device=dev)
-    ok = torch.empty((b,), dtype=U8, device=dev)
-    N.call("mi_rgbd_refine", *maps, N.dev(rr, F32, "r0"), N.dev(tt, F32, "t0"), b, h, w, *cam,
-           ctypes.cast(strides, ctypes.c_void_p), ctypes.cast(iters, ctypes.c_void_p), len(sched), float(distance_threshold),
-           float(angle_threshold), float(photo_weight), float(intensity_threshold), int(min_correspondences), r.data_ptr(),
-           t.data_ptr(), info.data_ptr(), rmse.data_ptr(), count.data_ptr(), rmse_photo.data_ptr(), count_photo.data_ptr(),
-           steps.data_ptr(), ok.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    keep, maps, rr, tt, cam, b, h, w, work, wbytes = _rgbd_inputs(named, r0, t0, camera, "rgbd_refine", "mi_rgbd_workspace_bytes")
+    strides, iters, stages = _icp_schedule(schedule, "rgbd_refine")
+    r, t, info, rmse, count, steps, ok = _refine_outputs(b, rr.device)
+    rmse_photo = torch.empty((b,), dtype=F32, device=rr.device)
+    count_photo = torch.empty((b,), dtype=I32, device=rr.device)
+    N.call("mi_rgbd_refine", *maps, N.dev(rr, F32, "r0"), N.dev(tt, F32, "t0"), b, h, w, *cam, strides, iters, stages,
+           float(distance_threshold), float(angle_threshold), float(photo_weight), float(intensity_threshold),
+           int(min_correspondences), r.data_ptr(), t.data_ptr(), info.data_ptr(), rmse.data_ptr(), count.data_ptr(),
+           rmse_photo.data_ptr(), count_photo.data_ptr(), steps.data_ptr(), ok.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
     return r, t, info, rmse, count, rmse_photo, count_photo, steps, ok.view(torch.bool)
 
 

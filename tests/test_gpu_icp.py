@@ -13,6 +13,10 @@ values, 2 for angles).  Nothing here was taken from the kernels.
     because b crosses zero at the truth; sum r^2: itself) the sums deviate by at most 1.02e-6, 4.742e-4 (a stride-4 case of
     86 rows at the truth, where b is the rounding of a cancelled sum) and 3.832e-5 -> SUMS_A_TOL = 4.08e-6, SUMS_B_TOL =
     1.90e-3, SUMS_RR_TOL = 1.53e-4.
+  - the same at stride 8 (18 more cases; 35 samples at (37, 53): one slab, most of it past the end): equal counts again (0
+    flips), 0.486 .. 0.877 of the sampled pixels.  With so few rows the float32 oracle's own deviation is larger than at
+    strides 1 2 4: at most 1.524e-6 (A), 6.158e-4 (b), 2.634e-4 (sum r^2) -> STRIDE8_SUMS_TOL = 6.10e-6, 2.46e-3, 1.05e-3.
+    The tolerances of strides 1 2 4 are not widened for it.
   - refinement from identity, default schedule, seeds 0 1 2 (all 14 steps applied in both runs, the float64 run's last step
     below 3e-16, smallest pivot ratio 7.3e-3):
       (48, 64):   float64 oracle from the truth 5.2624e-2 deg, 1.6994e-3 m (the bias of crease and sphere normals at this size);
@@ -42,6 +46,7 @@ SEEDS = (0, 1, 2)
 FLIP_CAP = 0.005                         # of the source pixels
 NORMAL_TOL = {False: 7.05e-6, True: 9.46e-6}               # keyed by u16
 SUMS_A_TOL, SUMS_B_TOL, SUMS_RR_TOL, COUNT_ALLOWANCE = 4.08e-6, 1.90e-3, 1.53e-4, 0
+STRIDE8_SUMS_TOL = (6.10e-6, 2.46e-3, 1.05e-3)             # 4 x (1.524e-6, 6.158e-4, 2.634e-4), measured at stride 8
 # (truth deg, truth m, oracle deg, oracle m, information relative, rmse relative)
 REFINE_TOL = {(48, 64): (5.2631e-2, 1.6998e-3, 6.52e-6, 4.03e-7, 8.18e-7, 1.54e-5),
               (120, 160): (5.3683e-3, 1.8789e-4, 4.24e-6, 4.72e-7, 4.26e-7, 3.56e-5)}
@@ -143,15 +148,16 @@ def test_surfel_maps_match_the_oracle(h, w, u16):
 
 # ---- 2. one linearisation --------------------------------------------------------------------------------------------------------
 
-def check_sums(got, ref, nsrc, what):
+def check_sums(got, ref, nsrc, what, tol=(SUMS_A_TOL, SUMS_B_TOL, SUMS_RR_TOL)):
     dev = IO.sums_deviation(got, ref)
-    print(f"{what}: count {int(ref[28])}, deviation A {dev[0]:.2e} b {dev[1]:.2e} r^2 {dev[2]:.2e} count {dev[3]}")
+    print(f"{what}: count {int(ref[28])}, deviation A {dev[0]:.2e} b {dev[1]:.2e} r^2 {dev[2]:.2e} count {dev[3]} (tolerance "
+          f"{tol[0]:.2e} {tol[1]:.2e} {tol[2]:.2e})")
     assert dev[3] <= min(COUNT_ALLOWANCE, FLIP_CAP * nsrc)
-    assert dev[0] <= SUMS_A_TOL and dev[1] <= SUMS_B_TOL and dev[2] <= SUMS_RR_TOL
+    assert dev[0] <= tol[0] and dev[1] <= tol[1] and dev[2] <= tol[2]
 
 
 @pytest.mark.parametrize("h,w", [(37, 53), (120, 160)])
-@pytest.mark.parametrize("stride", [1, 2, 4])
+@pytest.mark.parametrize("stride", [1, 2, 4, 8])
 @pytest.mark.parametrize("variant", [0, 1, 2])
 def test_linearise_matches_the_oracle(h, w, stride, variant):
     m1, m2 = room_maps_gpu(h, w)
@@ -167,7 +173,11 @@ def test_linearise_matches_the_oracle(h, w, stride, variant):
         flips = abs(IO.linearise(f1, f2, ps[b][0], ps[b][1], cam, stride, dtype=F32)[28] - ref[28])
         assert flips <= min(COUNT_ALLOWANCE, FLIP_CAP * nsrc)                         # the float32 oracle alone stays inside
         assert ref[28] > 0.5 * 0.8 * nsrc
-        check_sums(sums[b], ref, nsrc, f"{h}x{w} stride {stride} pair {b} pose kind {(b + variant) % 3}")
+        what = f"{h}x{w} stride {stride} pair {b} pose kind {(b + variant) % 3}"
+        if stride == 8:
+            check_sums(sums[b], ref, nsrc, what, STRIDE8_SUMS_TOL)
+        else:
+            check_sums(sums[b], ref, nsrc, what)
         assert np.isfinite(sums[b]).all()
 
 
