@@ -3,233 +3,110 @@
 PyTorch is plumbing only: it owns device memory and the HIP stream; every compute call
 goes through the C ABI with raw device pointers.  There is no CPU or eager fallback: if the
 library is missing or a tensor is not on the GPU the call raises.
+
+The binding is DERIVED from the two headers at import (read_header): argument and return types of every MI_API
+declaration, the fields of mi_match_params, and every MI_* enum member and numeric macro as a module attribute.
+Declaring an entry point or a limit in the header is all a new kernel needs here.
 """
 from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_size_t, c_uint32, c_void_p
+import re
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_size_t, c_uint32, c_void_p
 
 import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
+_INCLUDE = os.path.join(os.path.dirname(_PKG), "include")
 # MI355X_MATCH_LIB: development hook (A/B timing of two builds on one box); the default is the in-tree build
 LIB_PATH = os.environ.get("MI355X_MATCH_LIB") or os.path.join(_PKG, "lib", "libmi355x_match.so")
 
-# name -> argtypes (return type is int unless listed in _RESTYPE); mirrors include/mi355x_match.h
-SIGNATURES = {
-    "mi_abi_version": [],
-    "mi_sinkhorn_dots_schedule": [c_void_p, c_int, c_int, c_int, c_int],
-    "mi_sinkhorn_dots_set_schedule": [c_void_p, c_int],
-    "mi_error_string": [c_int],
-    "mi_release_stream_resources": [c_void_p],
-    "mi_corner_response": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    "mi_corner_response_u8": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    "mi_convert_u8_f32": [c_void_p, ctypes.c_longlong, c_void_p, c_void_p],
-    "mi_corner_response_balanced": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "mi_corner_response_pair": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "mi_nms_mask": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    "mi_candidate_layout": [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
-    "mi_nms_candidates": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p],
-    "mi_select_candidates": [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p],
-    "mi_topk_keypoints": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "mi_bad_plan_bytes": [c_int],
-    "mi_bad_plan_build": [c_void_p, c_void_p, c_int, c_void_p, c_void_p],
-    "mi_sparse_bad": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int,
-                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "mi_sparse_bad_u8": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int,
-                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "mi_sparse_bad_pair": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
-                           c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "mi_bad_dense": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p],
-    "mi_bad_dense_oriented": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p,
-                              c_void_p],
-    "mi_gather_descriptors": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p],
-    "mi_angle_map": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "mi_angle_at_keypoints": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "mi_sparse_bad_oriented": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                               c_int, c_int, c_float, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
-    "mi_angle_at_keypoints_pair": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                                   c_void_p],
-    "mi_sparse_bad_oriented_pair": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                    c_int, c_int, c_float, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
-    "mi_cost_logscores_bits": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_void_p, c_int, c_void_p],
-    "mi_cost_logscores_f32": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_void_p, c_int, c_void_p],
-    "mi_sinkhorn_workspace_bytes": [c_int, c_int, c_int],
-    "mi_sinkhorn": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                    c_size_t, c_void_p],
-    "mi_cost_dots_bits": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                          c_void_p],
-    "mi_sinkhorn_dots_workspace_bytes": [c_int, c_int, c_int],
-    "mi_sinkhorn_dots": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_double, c_int,
-                         c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p],
-    "mi_sinkhorn_dots_status_word": [c_void_p, c_int, c_int, c_int],
-    "mi_match_filters": [c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p],
-    "mi_match_filter_masks": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p],
-    "mi_mnn_extract": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p,
-                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "mi_mnn_duals_workspace_bytes": [c_int, c_int, c_int],
-    "mi_mnn_from_duals": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
-                          c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "mi_mnn_from_duals_dots": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p,
-                               c_void_p, c_void_p, c_int, c_float, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
-                               c_void_p, c_void_p, c_void_p, c_void_p],
-    "mi_mnn_from_duals_records": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                  c_float, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p],
-    "mi_mnn_from_duals_dots_records": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p,
-                                       c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_size_t, c_void_p, c_int,
-                                       c_void_p, c_void_p, c_void_p, c_void_p],
-    "mi_core_maxima": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "mi_normalise_keypoints": [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p],
-    "mi_essential_matrix_workspace_bytes": [c_int, c_int, c_int, c_int],
-    "mi_essential_matrix": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                            c_void_p, c_void_p, c_size_t, c_void_p],
-    "mi_essential_matrix_dots": [c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_int, c_int, c_int,
-                                 c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
-                                 c_void_p],
-    "mi_fast_score": [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p],
-    "mi_dog_responses": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "mi_akaze_diffuse": [c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p],
-    "mi_akaze_scale_fused": [c_int, c_int],
-    "mi_akaze_scale": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p,
-                       c_void_p],
-    "mi_akaze_scale_sets": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_void_p, c_void_p,
-                            c_void_p, c_void_p],
-    "mi_akaze_scale_select": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_void_p, c_void_p,
-                              c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "mi_akaze_orientation_from_attain": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
-                                         c_void_p],
-    "mi_akaze_orientation_select": [c_void_p, c_size_t, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int,
-                                    c_void_p, c_void_p, c_void_p],
-    "mi_akaze_hessian_scores": [c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p],
-    "mi_akaze_combine": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "mi_akaze_orientation_at_keypoints": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
-                                          c_void_p],
-    "mi_voxel_downsample_workspace_bytes": [c_int, ctypes.c_int64, c_int],
-    "mi_voxel_downsample": [c_void_p, c_void_p, c_int, ctypes.c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                            c_void_p, c_size_t, c_void_p],
-    "mi_depth_to_points": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p],
-    "mi_depth_align": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float,
-                       c_void_p, c_void_p, c_void_p, c_void_p],
-    "mi_histogram": [c_void_p, c_int, c_int, ctypes.c_longlong, c_int, c_int, c_void_p, c_void_p],
-    "mi_otsu_threshold": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
-    "mi_multi_otsu_workspace_bytes": [c_int, c_int, c_int],
-    "mi_multi_otsu_threshold": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p],
-    "mi_threshold_apply": [c_void_p, c_int, c_int, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                           c_void_p],
-    "mi_essential_hypotheses": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_uint32, c_void_p, c_void_p,
-                                c_void_p, c_void_p],
-    "mi_essential_refit": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "mi_essential_ransac_workspace_bytes": [c_int, c_int, c_int],
-    "mi_essential_ransac": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_uint32, c_void_p, c_void_p,
-                            c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
-    "mi_recover_pose": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
-                        c_void_p, c_void_p],
-    "mi_triangulate": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "mi_ingest_frames": [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_longlong, ctypes.c_longlong, c_int, c_void_p, c_int,
-                         c_int, c_int, c_void_p],
-    "mi_lift_keypoints": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_float, c_float, c_float, c_void_p,
-                          c_void_p, c_void_p, c_void_p],
-    "mi_rigid_hypotheses": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_uint32, c_void_p, c_void_p, c_void_p,
-                            c_void_p],
-    "mi_rigid_refit": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "mi_rigid_ransac_workspace_bytes": [c_int, c_int, c_int],
-    "mi_rigid_ransac": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_uint32, c_void_p, c_void_p, c_void_p,
-                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
-    "mi_pnp_hypotheses": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_uint32, c_void_p, c_void_p, c_void_p,
-                          c_void_p],
-    "mi_pnp_refit": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                     c_void_p],
-    "mi_pnp_ransac_workspace_bytes": [c_int, c_int, c_int],
-    "mi_pnp_ransac": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_uint32, c_void_p, c_void_p, c_void_p,
-                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
-    "mi_homography_hypotheses": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_uint32, c_void_p, c_void_p,
-                                 c_void_p, c_void_p],
-    "mi_homography_refit": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "mi_homography_ransac_workspace_bytes": [c_int, c_int, c_int],
-    "mi_homography_ransac": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_uint32, c_void_p, c_void_p,
-                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
-    "mi_homography_pose": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                           c_void_p, c_void_p, c_void_p, c_void_p],
-    "mi_two_view_select": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_void_p,
-                           c_void_p, c_void_p, c_void_p],
-    "mi_ba_cost": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
-                   c_void_p],
-    "mi_ba_workspace_bytes": [c_int, c_int, c_int],
-    "mi_ba_linearise": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
-                        c_void_p, c_void_p, c_size_t, c_void_p],
-    "mi_ba_refine": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
-                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
-    "mi_place_votes": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float,
-                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "mi_place_select": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "mi_surfel_maps": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p,
-                       c_void_p],
-    "mi_icp_workspace_bytes": [c_int, c_int, c_int],
-    "mi_icp_linearise": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
-                         c_float, c_float, c_int, c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p],
-    "mi_icp_refine": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float,
-                      c_float, c_void_p, c_void_p, c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
-    "mi_intensity_maps": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    "mi_rgbd_workspace_bytes": [c_int, c_int, c_int],
-    "mi_photo_linearise": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
-                           c_float, c_float, c_int, c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p],
-    "mi_rgbd_refine": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                       c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_int,
-                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                       c_size_t, c_void_p],
-    "mi_tsdf_reset": [c_void_p, c_int, c_int, c_int, c_int, c_void_p],
-    "mi_tsdf_integrate": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p,
-                          c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p,
-                          c_void_p, c_void_p, c_void_p],
-    "mi_tsdf_raycast": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p,
-                        c_void_p, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p],
-    "mi_pose_compose": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
-    "mi_tsdf_surface_workspace_bytes": [c_int, c_int, c_int, c_int],
-    "mi_tsdf_surface": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p,
-                        c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
-    "mi_tsdf_gray_reset": [c_void_p, c_int, c_int, c_int, c_int, c_void_p],
-    "mi_tsdf_integrate_gray": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float,
-                               c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
-                               c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
-    "mi_tsdf_sample_gray": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_void_p, c_int, c_void_p,
-                            c_void_p, c_void_p, c_void_p],
-}
-
 
 class MatchParams(ctypes.Structure):
-    """mi_match_params (include/mi355x_match.h): the hyper-parameters of the whole path for mi_match_pairs."""
-    _fields_ = [("block_size", c_int), ("nms_radius", c_int), ("max_keypoints", c_int), ("score_threshold", c_float),
-                ("border_margin", c_int), ("num_pairs", c_int), ("pair_geom", c_void_p), ("pair_thr", c_void_p),
-                ("bad_plan", c_void_p), ("normalize_descriptors", c_int), ("epsilon", c_double),
-                ("unused_score", c_double), ("sinkhorn_iterations", c_int), ("max_matches", c_int),
-                ("match_threshold", c_float), ("flags", c_int)]
+    """mi_match_params (include/mi355x_match.h): the hyper-parameters of the whole path for mi_match_pairs.  Its
+    _fields_ are read from the header's typedef below."""
 
 
-SIGNATURES["mi_match_pairs_workspace_bytes"] = [c_int, c_int, c_int, ctypes.POINTER(MatchParams)]
-SIGNATURES["mi_match_pairs"] = [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(MatchParams), c_void_p, c_void_p,
-                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+# The closed type map of the headers.  Anything else is an error at import, not a guess.
+_SCALARS = {"int": c_int, "float": c_float, "double": c_double, "size_t": c_size_t, "uint32_t": c_uint32,
+            "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "long long": ctypes.c_longlong, "mi_stream_t": c_void_p}
+# Pointer parameters: `[const] int *` and `const double *` are the header's HOST-array convention (device integers are
+# declared int32_t / uint32_t there, and a `double *` the library writes is device memory: the fp64 sums of the
+# linearisations); every other pointer is an address handed through as c_void_p.
+_POINTER_ARGS = {"int": POINTER(c_int), "const int": POINTER(c_int), "const double": POINTER(c_double),
+                 "const mi_match_params": POINTER(MatchParams)}
+_NUMBER = re.compile(r"[-+]?(?:(\d+)|(?:\d+\.?\d*|\.\d+)(?:[eE][-+]?\d+)?f?)$")
+
+
+def _ctype(text: str, where: str, returns: bool = False):
+    """The ctypes type of a C type as the headers spell it (`const float *`, `long long`, ...)."""
+    spelled = " ".join(text.replace("*", " ").split())
+    base = spelled.removeprefix("const ")
+    if "*" in text:
+        if returns:
+            return c_char_p if base == "char" else c_void_p
+        return _POINTER_ARGS.get(spelled, c_void_p)
+    if base not in _SCALARS:
+        raise TypeError(f"{where}: the type '{text.strip()}' is outside the binding's type map")
+    return _SCALARS[base]
+
+
+def _typed_names(decls: list, where: str) -> list:
+    """['const float *image', 'int n', ...] -> [('image', c_void_p), ('n', c_int), ...]"""
+    out = []
+    for d in decls:
+        m = re.fullmatch(r"(.*?)(\w+)", d.strip(), flags=re.S)
+        if m is None:
+            raise TypeError(f"{where}: cannot read '{d.strip()}'")
+        out.append((m.group(2), _ctype(m.group(1), where)))
+    return out
+
+
+def read_header(text: str):
+    """C header text -> (signatures: name -> argtypes, restypes: name -> return type, struct fields of mi_match_params or
+    None, constants: MI_* name -> number).  Plain regular expressions over the comment-stripped text; every MI_API token
+    must end up as one parsed declaration."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(MI_\w+)[ \t]+(\S+)[ \t]*$", text, flags=re.M):
+        m = _NUMBER.match(value)
+        if m:                                                 # MI_API's value is no number: not a constant
+            constants[name] = int(value) if m.group(1) else float(value.rstrip("f"))
+    for body in re.findall(r"\benum\s*\{([^}]*)\}", text):
+        for member in filter(None, (s.strip() for s in body.split(","))):
+            m = re.fullmatch(r"(MI_\w+)\s*=\s*(-?\d+)", member)
+            if m is None:
+                raise TypeError(f"enum member '{member}': expected MI_NAME = integer")
+            constants[m.group(1)] = int(m.group(2))
+    text = re.sub(r"^[ \t]*#[^\n]*$", " ", text, flags=re.M)       # the MI_API tokens left are the declarations'
+    fields = None
+    m = re.search(r"typedef\s+struct\s+mi_match_params\s*\{([^}]*)\}", text)
+    if m:
+        fields = _typed_names([f for f in m.group(1).split(";") if f.strip()], "mi_match_params")
+    signatures, restypes = {}, {}
+    for ret, name, params in re.findall(r"\bMI_API\s+([\w\s*]*?)(\w+)\s*\(([^;()]*)\)\s*;", text):
+        restypes[name] = _ctype(ret, name, returns=True)
+        args = [] if params.strip() == "void" else params.split(",")
+        signatures[name] = [t for _, t in _typed_names(args, name)]
+    tokens = len(re.findall(r"\bMI_API\b", text))
+    if tokens != len(signatures):
+        raise TypeError(f"{tokens} MI_API declarations, {len(signatures)} of them read: a declaration does not fit the reader")
+    return signatures, restypes, fields, constants
+
+
+def _read(name: str):
+    with open(os.path.join(_INCLUDE, name)) as f:
+        return read_header(f.read())
+
+
+# name -> argtypes / name -> return type, as tests and tools read them
+SIGNATURES, RESTYPES, MatchParams._fields_, _constants = _read("mi355x_match.h")
+globals().update(_constants)            # MI_OK, MI_BAD_HARD, MI_SOLVER_NO_FORK, MI_POSE_MAX_N, MI_DOTS_MIN_EPSILON, ...
 # include/mi355x_match_debug.h: test / tooling hooks -- exported only by lib/libmi355x_match_debug.so (debug_library()),
 # not part of the product ABI; nothing in this package calls them
-DEBUG_SIGNATURES = {"mi_debug_set": [c_int, c_int], "mi_debug_topk_stamps": [c_void_p], "mi_debug_clock_probe": [c_void_p],
-                    "mi_debug_bad_plan_passes": [c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
-                    "mi_debug_sinkhorn_dots_form": [c_int, c_int, c_int, c_int, c_int, c_int],
-                    "mi_debug_tuner_script": [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int)],
-                    "mi_debug_akaze_math_check": [c_int, c_float, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p]}
-SIGNATURES["mi_match_pairs_u8"] = SIGNATURES["mi_match_pairs"]
-_RESTYPE = {"mi_essential_matrix_workspace_bytes": c_size_t, "mi_sinkhorn_dots_status_word": c_void_p, "mi_match_pairs_workspace_bytes": c_size_t, "mi_error_string": c_char_p, "mi_sinkhorn_workspace_bytes": c_size_t, "mi_bad_plan_bytes": c_size_t,
-            "mi_sinkhorn_dots_workspace_bytes": c_size_t, "mi_mnn_duals_workspace_bytes": c_size_t,
-            "mi_voxel_downsample_workspace_bytes": c_size_t, "mi_multi_otsu_workspace_bytes": c_size_t,
-            "mi_essential_ransac_workspace_bytes": c_size_t, "mi_rigid_ransac_workspace_bytes": c_size_t,
-            "mi_pnp_ransac_workspace_bytes": c_size_t, "mi_homography_ransac_workspace_bytes": c_size_t,
-            "mi_ba_workspace_bytes": c_size_t,
-            "mi_icp_workspace_bytes": c_size_t, "mi_rgbd_workspace_bytes": c_size_t, "mi_tsdf_surface_workspace_bytes": c_size_t}
-
-MI_BAD_RAW, MI_BAD_SOFT, MI_BAD_HARD = 0, 1, 2
-MI_DIST_L2, MI_DIST_L1 = 0, 1
-MI_PIX_U8, MI_PIX_U16, MI_PIX_I32, MI_PIX_F32 = 0, 1, 2, 3
-MI_INGEST_BGR, MI_INGEST_RGB = 0, 1
+DEBUG_SIGNATURES, _debug_restypes, _, _ = _read("mi355x_match_debug.h")
+RESTYPES.update(_debug_restypes)
 
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_debug.so")
 
@@ -248,7 +125,7 @@ def _open(path: str, signatures: dict) -> ctypes.CDLL:
     for name, argtypes in signatures.items():
         fn = getattr(lib, name)            # AttributeError if the ABI and the binding diverge
         fn.argtypes = argtypes
-        fn.restype = _RESTYPE.get(name, c_int)
+        fn.restype = RESTYPES[name]
     return lib
 
 
@@ -309,6 +186,11 @@ def dev(t: torch.Tensor, dtype: torch.dtype, what: str) -> int:
     if not t.is_contiguous():
         raise RuntimeError(f"{what} must be contiguous")
     return t.data_ptr()
+
+
+def opt(t: torch.Tensor | None, dtype: torch.dtype, what: str) -> int | None:
+    """dev() of an optional tensor: None (a NULL pointer) for None."""
+    return None if t is None else dev(t, dtype, what)
 
 
 _timers: dict | None = None

@@ -65,16 +65,26 @@ def _images(image, what: str, keep_u8: bool = False):
     return image.float().contiguous()
 
 
-TILE_COUNTER_BYTES = 16640          # include/mi355x_match.h MI_TILE_COUNTER_BYTES
+def _workspace(query: str, *args, device, refusal: str | None = None):
+    """The library workspace of one call, sized by the `*_workspace_bytes` entry `query`(*args) -> (int64 tensor of
+    ceil(bytes / 16) * 2 words, bytes).  The library is told the queried count, not the rounded one.  A size of 0 means
+    the request is outside what the entry point covers: RuntimeError(refusal) for the ops that have a refusal text."""
+    wbytes = int(getattr(N.load(), query)(*args))
+    if wbytes == 0 and refusal is not None:
+        raise RuntimeError(refusal)
+    return torch.empty(((wbytes + 15) // 16 * 2,), dtype=torch.int64, device=device), wbytes
+
+
+TILE_COUNTER_BYTES = N.MI_TILE_COUNTER_BYTES
 
 # Sinkhorn solver flags handed to mi_sinkhorn_dots / mi_match_pairs (include/mi355x_match.h, "co-residency"):
 # 0 = MI_SOLVER_DEFAULT; MI_SOLVER_MULTI_LAUNCH for a process that shares its GPU with long-running foreign kernels;
 # MI_SOLVER_NO_FORK keeps the >= 64-pair Sinkhorn on the caller's stream (no helper streams, no events, no tuning).
 # A preference of this Python layer (the C library has no process-wide switch); results are identical either way.
-MI_SOLVER_DEFAULT, MI_SOLVER_MULTI_LAUNCH, MI_SOLVER_NO_FORK = 0, 1, 2
+MI_SOLVER_DEFAULT, MI_SOLVER_MULTI_LAUNCH, MI_SOLVER_NO_FORK = N.MI_SOLVER_DEFAULT, N.MI_SOLVER_MULTI_LAUNCH, N.MI_SOLVER_NO_FORK
 # (not a preference: sinkhorn_bits sets it by itself when the descriptors have fewer than 1024 bits, which is what lets
 # mi_sinkhorn_dots' row kernel read the uint16 dot products as fp16 denormals)
-MI_SOLVER_DOTS_BELOW_1024 = 4
+MI_SOLVER_DOTS_BELOW_1024 = N.MI_SOLVER_DOTS_BELOW_1024
 _solver_flags = MI_SOLVER_DEFAULT
 
 
@@ -86,7 +96,8 @@ def set_solver_flags(flags: int) -> None:
     _solver_flags = int(flags)
 
 
-MI_SCHEDULE_UNDECIDED, MI_SCHEDULE_CALLER_HELPER, MI_SCHEDULE_TWO_HELPERS, MI_SCHEDULE_UNSPLIT = -1, 0, 1, 2
+MI_SCHEDULE_UNDECIDED, MI_SCHEDULE_CALLER_HELPER, MI_SCHEDULE_TWO_HELPERS, MI_SCHEDULE_UNSPLIT = (
+    N.MI_SCHEDULE_UNDECIDED, N.MI_SCHEDULE_CALLER_HELPER, N.MI_SCHEDULE_TWO_HELPERS, N.MI_SCHEDULE_UNSPLIT)
 
 
 def sinkhorn_schedule(batch: int, n: int, m: int, iterations: int) -> int:
@@ -362,15 +373,15 @@ def sinkhorn(z: torch.Tensor, m: int, pitch: int, dustbin_logscore: float, itera
     u = torch.empty((b, n + 1), dtype=F32, device=z.device)
     v = torch.empty((b, m + 1), dtype=F32, device=z.device)
     p = torch.empty((b, n + 1, m + 1), dtype=F32, device=z.device) if want_p else None
-    wbytes = int(N.load().mi_sinkhorn_workspace_bytes(b, n, m))
-    work = torch.empty((max(wbytes, 8) // 8,), dtype=torch.int64, device=z.device) if use_workspace else None
+    # no workspace (by choice, or M > 1024 where the query answers 0): the two-pass form
+    work, wbytes = _workspace("mi_sinkhorn_workspace_bytes", b, n, m, device=z.device) if use_workspace else (None, 0)
     N.call("mi_sinkhorn", N.dev(z, F32, "z"), b, n, m, pitch, float(dustbin_logscore), int(iterations),
            u.data_ptr(), v.data_ptr(), p.data_ptr() if p is not None else None,
-           work.data_ptr() if work is not None else None, wbytes if work is not None else 0, N.stream_ptr())
+           work.data_ptr() if wbytes else None, wbytes, N.stream_ptr())
     return (p, u, v) if (return_duals or not want_p) else p
 
 
-DOTS_MIN_EPSILON = 0.005      # MI_DOTS_MIN_EPSILON (include/mi355x_match.h): below it the clamped fp32-Z form runs
+DOTS_MIN_EPSILON = N.MI_DOTS_MIN_EPSILON      # below it the clamped fp32-Z form runs
 
 
 def dots_supported(b: int, n: int, m: int, epsilon: float = 1.0) -> bool:
@@ -394,7 +405,8 @@ def sinkhorn_bits(bits1: torch.Tensor, bits2: torch.Tensor, normalized: bool, ep
     b, n, words = bits1.shape
     m = bits2.shape[1]
     dev = bits1.device
-    wbytes = int(N.load().mi_sinkhorn_dots_workspace_bytes(b, n, m)) if epsilon >= DOTS_MIN_EPSILON else 0
+    work, wbytes = (_workspace("mi_sinkhorn_dots_workspace_bytes", b, n, m, device=dev) if epsilon >= DOTS_MIN_EPSILON
+                    else (None, 0))
     if wbytes == 0:
         if return_state or not want_p:
             raise RuntimeError(f"the dot-product Sinkhorn form supports M <= 1024 and epsilon >= {DOTS_MIN_EPSILON}, "
@@ -411,7 +423,6 @@ def sinkhorn_bits(bits1: torch.Tensor, bits2: torch.Tensor, normalized: bool, ep
     u = torch.empty((b, n + 1), dtype=F32, device=dev)
     v = torch.empty((b, m + 1), dtype=F32, device=dev)
     p = torch.empty((b, n + 1, m + 1), dtype=F32, device=dev) if want_p else None
-    work = torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=dev)
     N.call("mi_sinkhorn_dots", dots.data_ptr(), row_info.data_ptr(), col_info.data_ptr(), b, n, m, pitch,
            float(epsilon), float(unused_score), 1.0 if normalized else float(words * 32), int(iterations),
            u.data_ptr(), v.data_ptr(), p.data_ptr() if p is not None else None, work.data_ptr(), wbytes,
@@ -492,10 +503,8 @@ def mnn_from_duals(z: torch.Tensor, m: int, pitch: int, u: torch.Tensor, v: torc
     """mnn_extract(P) with P = exp(Z + u + v) evaluated on the fly (P never written)."""
     b, n, _ = z.shape
     k1, k2 = kpts1.float().contiguous(), kpts2.float().contiguous()
-    wbytes = int(N.load().mi_mnn_duals_workspace_bytes(b, n, m))
-    if wbytes == 0:
-        raise RuntimeError(f"mnn_from_duals supports N <= 4096 and M <= 1024, got ({n}, {m})")
-    work = torch.empty((wbytes // 8,), dtype=torch.int64, device=z.device)
+    work, wbytes = _workspace("mi_mnn_duals_workspace_bytes", b, n, m, device=z.device,
+                              refusal=f"mnn_from_duals supports N <= 4096 and M <= 1024, got ({n}, {m})")
     rec, valid, ij = _mnn_record_outputs(b, max_matches, z.device)
     N.call("mi_mnn_from_duals_records", N.dev(z, F32, "z"), b, n, m, pitch, N.dev(u, F32, "u"), N.dev(v, F32, "v"),
            N.dev(k1, F32, "keypoints1"), N.dev(k2, F32, "keypoints2"), int(max_matches), float(threshold),
@@ -515,10 +524,8 @@ def mnn_from_duals_dots(state, m: int, epsilon: float, u: torch.Tensor, v: torch
         dots_below_1024 = num_bits is not None and num_bits < 1024
     b, n, _ = dots.shape
     k1, k2 = kpts1.float().contiguous(), kpts2.float().contiguous()
-    wbytes = int(N.load().mi_mnn_duals_workspace_bytes(b, n, m))
-    if wbytes == 0:
-        raise RuntimeError(f"mnn_from_duals_dots supports N <= 4096 and M <= 1024, got ({n}, {m})")
-    work = torch.empty((wbytes // 8,), dtype=torch.int64, device=dots.device)
+    work, wbytes = _workspace("mi_mnn_duals_workspace_bytes", b, n, m, device=dots.device,
+                              refusal=f"mnn_from_duals_dots supports N <= 4096 and M <= 1024, got ({n}, {m})")
     rec, valid, ij = _mnn_record_outputs(b, max_matches, dots.device)
     N.call("mi_mnn_from_duals_dots_records", dots.data_ptr(), row_info.data_ptr(), col_info.data_ptr(), b, n, m, pitch,
            float(epsilon), N.dev(u, F32, "u"), N.dev(v, F32, "v"), N.dev(k1, F32, "keypoints1"),
@@ -580,7 +587,7 @@ def akaze_scale_sets(image1: torch.Tensor, image2: torch.Tensor, iterations: int
     return image_out, scores_out
 
 
-AKAZE_KAPPA_MIN, AKAZE_KAPPA_MAX = 1e-3, 1e6          # include/mi355x_match.h MI_AKAZE_KAPPA_MIN / _MAX
+AKAZE_KAPPA_MIN, AKAZE_KAPPA_MAX = N.MI_AKAZE_KAPPA_MIN, N.MI_AKAZE_KAPPA_MAX
 
 
 def akaze_kappa_fused(kappa: float) -> bool:
@@ -664,7 +671,7 @@ def akaze_combine(scale_scores: torch.Tensor, scale_orientations: torch.Tensor |
     scores = torch.empty((n, 1, h, w), dtype=F32, device=scale_scores.device)
     oris = torch.empty_like(scores) if scale_orientations is not None else None
     N.call("mi_akaze_combine", N.dev(scale_scores, F32, "scale_scores"),
-           N.dev(scale_orientations, F32, "scale_orientations") if scale_orientations is not None else None,
+           N.opt(scale_orientations, F32, "scale_orientations"),
            s, n, h, w, scores.data_ptr(), oris.data_ptr() if oris is not None else None, N.stream_ptr())
     return scores, oris
 
@@ -709,12 +716,12 @@ def essential_matrix(p: torch.Tensor, pts1_n: torch.Tensor, pts2_n: torch.Tensor
         raise RuntimeError("valid1 and valid2 must be given together")
     v1, v2 = _validity_bytes(valid1), _validity_bytes(valid2)
     e = torch.empty((b, 3, 3), dtype=F32, device=pp.device)
-    wbytes = int(N.load().mi_essential_matrix_workspace_bytes(b, n, m, int(top_k))) if banded else 0
-    work = torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=pp.device) if wbytes else None
+    # no workspace (by choice, or top_k > 4 where the query answers 0): the single-launch dense form
+    work, wbytes = (_workspace("mi_essential_matrix_workspace_bytes", b, n, m, int(top_k), device=pp.device) if banded
+                    else (None, 0))
     N.call("mi_essential_matrix", N.dev(pp, F32, "P"), b, n, m, N.dev(q1, F32, "pts1"), N.dev(q2, F32, "pts2"),
-           N.dev(v1, torch.uint8, "valid1") if v1 is not None else None,
-           N.dev(v2, torch.uint8, "valid2") if v2 is not None else None, int(top_k), int(n_iter), int(n_iter_manifold),
-           e.data_ptr(), work.data_ptr() if work is not None else None, wbytes, N.stream_ptr())
+           N.opt(v1, U8, "valid1"), N.opt(v2, U8, "valid2"), int(top_k), int(n_iter), int(n_iter_manifold),
+           e.data_ptr(), work.data_ptr() if wbytes else None, wbytes, N.stream_ptr())
     return e
 
 
@@ -733,13 +740,12 @@ def essential_matrix_dots(state, m: int, epsilon: float, u: torch.Tensor, v: tor
         raise RuntimeError("valid1 and valid2 must be given together")
     v1, v2 = _validity_bytes(valid1), _validity_bytes(valid2)
     e = torch.empty((b, 3, 3), dtype=F32, device=dots.device)
-    wbytes = int(N.load().mi_essential_matrix_workspace_bytes(b, n, m, int(top_k))) if banded else 0
-    work = torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=dots.device) if wbytes else None
+    work, wbytes = (_workspace("mi_essential_matrix_workspace_bytes", b, n, m, int(top_k), device=dots.device) if banded
+                    else (None, 0))
     N.call("mi_essential_matrix_dots", dots.data_ptr(), row_info.data_ptr(), col_info.data_ptr(), int(pitch), float(epsilon),
            N.dev(u, F32, "u"), N.dev(v, F32, "v"), b, n, m, N.dev(q1, F32, "pts1"), N.dev(q2, F32, "pts2"),
-           N.dev(v1, torch.uint8, "valid1") if v1 is not None else None,
-           N.dev(v2, torch.uint8, "valid2") if v2 is not None else None, int(top_k), int(n_iter), int(n_iter_manifold),
-           e.data_ptr(), work.data_ptr() if work is not None else None, wbytes, N.stream_ptr())
+           N.opt(v1, U8, "valid1"), N.opt(v2, U8, "valid2"), int(top_k), int(n_iter), int(n_iter_manifold),
+           e.data_ptr(), work.data_ptr() if wbytes else None, wbytes, N.stream_ptr())
     return e
 
 
@@ -806,10 +812,8 @@ def match_pairs(image1: torch.Tensor, image2: torch.Tensor, *, block_size: int, 
                         float(unused_score), int(sinkhorn_iterations), int(max_matches), float(match_threshold),
                         _solver_flags)
     import ctypes
-    wbytes = int(N.load().mi_match_pairs_workspace_bytes(n, h, w, ctypes.byref(prm)))
-    if wbytes == 0:
-        raise RuntimeError("mi_match_pairs does not cover these parameters (K <= 1024, P % 64 == 0, odd block size ...)")
-    work = torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=dev)
+    work, wbytes = _workspace("mi_match_pairs_workspace_bytes", n, h, w, ctypes.byref(prm), device=dev,
+                              refusal="mi_match_pairs does not cover these parameters (K <= 1024, P % 64 == 0, odd block size ...)")
     k, mx = int(max_keypoints), int(max_matches)
     kp1 = torch.empty((n, k, 2), dtype=F32, device=dev)
     kp2 = torch.empty((n, k, 2), dtype=F32, device=dev)
@@ -859,11 +863,10 @@ def _voxel_launch(pts: torch.Tensor, offsets: torch.Tensor, batch: int, leaf: to
     out = torch.empty((total, d), dtype=F32, device=dev)
     mask = torch.empty((total,), dtype=torch.bool, device=dev)
     counts = torch.empty((batch,), dtype=torch.int64, device=dev)
-    wbytes = N.load().mi_voxel_downsample_workspace_bytes(batch, total, d)
-    work = torch.empty(((wbytes + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+    work, wbytes = _workspace("mi_voxel_downsample_workspace_bytes", batch, total, d, device=dev)
     N.call("mi_voxel_downsample", pts.data_ptr() if total else None, N.dev(offsets, torch.int64, "offsets"), batch, total,
            d, N.dev(leaf, F32, "leaf_size"), out.data_ptr() if total else None, mask.data_ptr() if total else None,
-           counts.data_ptr(), work.data_ptr(), work.numel() * 8, N.stream_ptr())
+           counts.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
     return out, mask, counts
 
 
@@ -994,8 +997,8 @@ def depth_align(depth: torch.Tensor, u_tab: torch.Tensor, v_tab: torch.Tensor, z
 I32 = torch.int32
 I64 = torch.int64
 _PIX = {U8: N.MI_PIX_U8, U16: N.MI_PIX_U16, I32: N.MI_PIX_I32, F32: N.MI_PIX_F32}
-THRESHOLD_MAX_BINS = 65536
-THRESHOLD_MAX_CLASSES = 5
+THRESHOLD_MAX_BINS = N.MI_THRESHOLD_MAX_BINS
+THRESHOLD_MAX_CLASSES = N.MI_THRESHOLD_MAX_CLASSES
 
 
 def _threshold_frames(frames: torch.Tensor, what: str):
@@ -1073,12 +1076,10 @@ def multi_otsu_threshold(hist: torch.Tensor, min_val: int, n_class: int = 3) -> 
     all C(bins - 1, n_class - 1) candidates, the first in itertools.combinations order among equals."""
     h, batch, bins, batched = _histograms(hist, "multi_otsu_threshold")
     multi_otsu_combinations(bins, n_class)
-    lib = N.load()
-    ws_bytes = lib.mi_multi_otsu_workspace_bytes(batch, bins, int(n_class))
-    ws = torch.empty(ws_bytes, dtype=U8, device=h.device)
+    work, wbytes = _workspace("mi_multi_otsu_workspace_bytes", batch, bins, int(n_class), device=h.device)
     out = torch.empty((batch, n_class - 1) if batched else (n_class - 1,), dtype=I32, device=h.device)
-    N.call("mi_multi_otsu_threshold", h.data_ptr(), batch, bins, int(min_val), int(n_class), out.data_ptr(), ws.data_ptr(),
-           ws_bytes, N.stream_ptr())
+    N.call("mi_multi_otsu_threshold", h.data_ptr(), batch, bins, int(min_val), int(n_class), out.data_ptr(), work.data_ptr(),
+           wbytes, N.stream_ptr())
     return out
 
 
@@ -1121,8 +1122,8 @@ def otsu(frames: torch.Tensor, min_val: int, max_val: int, dtype: torch.dtype = 
 
 # ---- relative pose (K15: vo/pose_estimation.py:53-162 on the GPU) ---------------------------------------------------------
 
-POSE_MAX_N = 2048                          # MI_POSE_MAX_N
-POSE_MAX_REFINE_ROUNDS = 8                 # MI_POSE_MAX_REFINE_ROUNDS
+POSE_MAX_N = N.MI_POSE_MAX_N
+POSE_MAX_REFINE_ROUNDS = N.MI_POSE_MAX_REFINE_ROUNDS
 
 
 def _row_pairs(a: torch.Tensor, b: torch.Tensor, valid: torch.Tensor | None, what: str, widths: tuple, limit: int, names: tuple,
@@ -1154,18 +1155,41 @@ def _hypotheses(entry: str, qa: torch.Tensor, qb: torch.Tensor, v, b: int, n: in
     m_h = torch.empty((b, h, *floats), dtype=F32, device=qa.device)
     cost = torch.empty((b, h), dtype=F32, device=qa.device)
     count = torch.empty((b, h), dtype=I32, device=qa.device)
-    N.call(entry, qa.data_ptr(), qb.data_ptr(), N.dev(v, U8, "valid") if v is not None else None, b, n, h, float(threshold),
+    N.call(entry, qa.data_ptr(), qb.data_ptr(), N.opt(v, U8, "valid"), b, n, h, float(threshold),
            int(seed) & 0xFFFFFFFF, m_h.data_ptr(), cost.data_ptr(), count.data_ptr(), N.stream_ptr())
     return m_h, cost, count
 
 
-def _ransac_workspace(entry: str, what: str, b: int, n: int, num_hypotheses: int, device):
-    """(H, the workspace `mi_*_ransac` wants as an int64 tensor, its size in bytes)"""
+def _pose_outputs(b: int, dev):
+    """R (B, 3, 3) and t (B, 3) float32"""
+    return torch.empty((b, 3, 3), dtype=F32, device=dev), torch.empty((b, 3), dtype=F32, device=dev)
+
+
+def _ransac_outputs(b: int, n: int, dev):
+    """what every `mi_*_ransac` reports: inlier (B, N) uint8, best_h (B,) int32, count (B,) int32"""
+    return (torch.empty((b, n), dtype=U8, device=dev), torch.empty((b,), dtype=I32, device=dev),
+            torch.empty((b,), dtype=I32, device=dev))
+
+
+def _ransac(entry: str, what: str, rows, num_hypotheses: int, threshold: float, refine_rounds: int, seed: int, outputs: tuple):
+    """`mi_*_ransac` share one signature around their outputs (given in the ABI's order); rows: what _row_pairs returned"""
+    qa, qb, v, b, n = rows
     h = int(num_hypotheses)
-    wbytes = int(getattr(N.load(), entry)(b, n, h))
-    if wbytes == 0:
-        raise RuntimeError(f"{what}: unsupported request (batch {b}, N {n}, {h} hypotheses)")
-    return h, torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=device), wbytes
+    work, wbytes = _workspace(f"{entry}_workspace_bytes", b, n, h, device=qa.device,
+                              refusal=f"{what}: unsupported request (batch {b}, N {n}, {h} hypotheses)")
+    N.call(entry, qa.data_ptr(), qb.data_ptr(), N.opt(v, U8, "valid"), b, n, h, float(threshold), int(refine_rounds),
+           int(seed) & 0xFFFFFFFF, *(o.data_ptr() for o in outputs), work.data_ptr(), wbytes, N.stream_ptr())
+
+
+def _matrix_refit(entry: str, what: str, pts1: torch.Tensor, pts2: torch.Tensor, mask: torch.Tensor):
+    """`mi_essential_refit` / `mi_homography_refit`: a 3 x 3 matrix over the masked correspondences -> (matrix, ok bool)"""
+    q1, q2, v, b, n = _correspondences(pts1, pts2, mask, what)
+    if v is None:
+        raise RuntimeError(f"{what} needs a mask")
+    mat = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
+    ok = torch.empty((b,), dtype=U8, device=q1.device)
+    N.call(entry, q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "mask"), b, n, mat.data_ptr(), ok.data_ptr(), N.stream_ptr())
+    return mat, ok.view(torch.bool)
 
 
 def essential_hypotheses(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, num_hypotheses: int,
@@ -1178,29 +1202,19 @@ def essential_hypotheses(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Te
 
 def essential_refit(pts1: torch.Tensor, pts2: torch.Tensor, mask: torch.Tensor):
     """`mi_essential_refit`: the linear 8-point E over the masked correspondences -> (E (B, 3, 3), ok (B,) bool)."""
-    q1, q2, v, b, n = _correspondences(pts1, pts2, mask, "essential_refit")
-    if v is None:
-        raise RuntimeError("essential_refit needs a mask")
-    e = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
-    ok = torch.empty((b,), dtype=U8, device=q1.device)
-    N.call("mi_essential_refit", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "mask"), b, n, e.data_ptr(), ok.data_ptr(),
-           N.stream_ptr())
-    return e, ok.view(torch.bool)
+    return _matrix_refit("mi_essential_refit", "essential_refit", pts1, pts2, mask)
 
 
 def essential_ransac(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, num_hypotheses: int,
                      threshold: float, refine_rounds: int = 3, seed: int = 0):
     """`mi_essential_ransac`: hypotheses, MSAC selection and refine_rounds rounds of refit-and-rescore in two launches ->
     (E (B, 3, 3), inlier (B, N) bool, best_h (B,) int32, count (B,) int32)."""
-    q1, q2, v, b, n = _correspondences(pts1, pts2, valid, "essential_ransac")
-    h, work, wbytes = _ransac_workspace("mi_essential_ransac_workspace_bytes", "essential_ransac", b, n, num_hypotheses, q1.device)
-    e = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
-    inlier = torch.empty((b, n), dtype=U8, device=q1.device)
-    best_h = torch.empty((b,), dtype=I32, device=q1.device)
-    count = torch.empty((b,), dtype=I32, device=q1.device)
-    N.call("mi_essential_ransac", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "valid") if v is not None else None, b, n, h,
-           float(threshold), int(refine_rounds), int(seed) & 0xFFFFFFFF, e.data_ptr(), inlier.data_ptr(), best_h.data_ptr(),
-           count.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    rows = _correspondences(pts1, pts2, valid, "essential_ransac")
+    b, n, dev = rows[3], rows[4], rows[0].device
+    e = torch.empty((b, 3, 3), dtype=F32, device=dev)
+    inlier, best_h, count = _ransac_outputs(b, n, dev)
+    _ransac("mi_essential_ransac", "essential_ransac", rows, num_hypotheses, threshold, refine_rounds, seed,
+            (e, inlier, best_h, count))
     return e, inlier.view(torch.bool), best_h, count
 
 
@@ -1212,12 +1226,11 @@ def recover_pose(e: torch.Tensor, pts1: torch.Tensor, pts2: torch.Tensor, mask: 
     ee = e.float().contiguous()
     if tuple(ee.shape) != (b, 3, 3):
         raise RuntimeError(f"recover_pose: E must be ({b}, 3, 3), got {tuple(e.shape)}")
-    r = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
-    t = torch.empty((b, 3), dtype=F32, device=q1.device)
+    r, t = _pose_outputs(b, q1.device)
     pose_mask = torch.empty((b, n), dtype=U8, device=q1.device)
     count = torch.empty((b,), dtype=I32, device=q1.device)
     ok = torch.empty((b,), dtype=U8, device=q1.device)
-    N.call("mi_recover_pose", N.dev(ee, F32, "E"), q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "mask") if v is not None else None,
+    N.call("mi_recover_pose", N.dev(ee, F32, "E"), q1.data_ptr(), q2.data_ptr(), N.opt(v, U8, "mask"),
            b, n, float(distance_threshold), r.data_ptr(), t.data_ptr(), pose_mask.data_ptr(), count.data_ptr(), ok.data_ptr(),
            N.stream_ptr())
     return r, t, pose_mask.view(torch.bool), count, ok.view(torch.bool)
@@ -1242,7 +1255,7 @@ def triangulate(proj1: torch.Tensor, proj2: torch.Tensor, pts1: torch.Tensor, pt
 
 # ---- K17 metric RGB-D pose (include/mi355x_match.h, "metric RGB-D pose") ---------------------------------------------------
 
-RIGID_MAX_N = 2048                         # MI_RIGID_MAX_N
+RIGID_MAX_N = N.MI_RIGID_MAX_N
 
 
 def lift_keypoints(keypoints: torch.Tensor, depth: torch.Tensor, k_inv: torch.Tensor, z_scale: float = 1.0,
@@ -1274,7 +1287,7 @@ def lift_keypoints(keypoints: torch.Tensor, depth: torch.Tensor, k_inv: torch.Te
     ok = torch.empty((b, n), dtype=U8, device=d.device)
     N.call("mi_lift_keypoints", N.dev(kp, F32, "keypoints"), d.data_ptr(), int(d.dtype == U16), b, n, int(d.shape[1]),
            int(d.shape[2]), N.dev(ki, F32, "K_inv"), float(z_scale), float(min_depth), float(max_depth),
-           N.dev(v, U8, "valid") if v is not None else None, pts.data_ptr(), ok.data_ptr(), N.stream_ptr())
+           N.opt(v, U8, "valid"), pts.data_ptr(), ok.data_ptr(), N.stream_ptr())
     return pts, ok.view(torch.bool)
 
 
@@ -1296,8 +1309,7 @@ def rigid_refit(pts1: torch.Tensor, pts2: torch.Tensor, mask: torch.Tensor):
     q1, q2, v, b, n = _point_pairs(pts1, pts2, mask, "rigid_refit")
     if v is None:
         raise RuntimeError("rigid_refit needs a mask")
-    r = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
-    t = torch.empty((b, 3), dtype=F32, device=q1.device)
+    r, t = _pose_outputs(b, q1.device)
     ok = torch.empty((b,), dtype=U8, device=q1.device)
     N.call("mi_rigid_refit", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "mask"), b, n, r.data_ptr(), t.data_ptr(),
            ok.data_ptr(), N.stream_ptr())
@@ -1308,24 +1320,20 @@ def rigid_ransac(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | N
                  refine_rounds: int = 3, seed: int = 0):
     """`mi_rigid_ransac`: hypotheses, MSAC selection and refine_rounds rounds of refit-and-rescore in two launches ->
     (R (B, 3, 3), t (B, 3), inlier (B, N) bool, best_h (B,) int32, count (B,) int32, rmse (B,) float32, ok (B,) bool)."""
-    q1, q2, v, b, n = _point_pairs(pts1, pts2, valid, "rigid_ransac")
-    h, work, wbytes = _ransac_workspace("mi_rigid_ransac_workspace_bytes", "rigid_ransac", b, n, num_hypotheses, q1.device)
-    r = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
-    t = torch.empty((b, 3), dtype=F32, device=q1.device)
-    inlier = torch.empty((b, n), dtype=U8, device=q1.device)
-    best_h = torch.empty((b,), dtype=I32, device=q1.device)
-    count = torch.empty((b,), dtype=I32, device=q1.device)
-    rmse = torch.empty((b,), dtype=F32, device=q1.device)
-    ok = torch.empty((b,), dtype=U8, device=q1.device)
-    N.call("mi_rigid_ransac", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "valid") if v is not None else None, b, n, h,
-           float(threshold), int(refine_rounds), int(seed) & 0xFFFFFFFF, r.data_ptr(), t.data_ptr(), inlier.data_ptr(),
-           best_h.data_ptr(), count.data_ptr(), rmse.data_ptr(), ok.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    rows = _point_pairs(pts1, pts2, valid, "rigid_ransac")
+    b, n, dev = rows[3], rows[4], rows[0].device
+    r, t = _pose_outputs(b, dev)
+    inlier, best_h, count = _ransac_outputs(b, n, dev)
+    rmse = torch.empty((b,), dtype=F32, device=dev)
+    ok = torch.empty((b,), dtype=U8, device=dev)
+    _ransac("mi_rigid_ransac", "rigid_ransac", rows, num_hypotheses, threshold, refine_rounds, seed,
+            (r, t, inlier, best_h, count, rmse, ok))
     return r, t, inlier.view(torch.bool), best_h, count, rmse, ok.view(torch.bool)
 
 
 # ---- K23 absolute pose (include/mi355x_match.h, "absolute pose") ------------------------------------------------------------
 
-PNP_MAX_N = 2048                           # MI_PNP_MAX_N
+PNP_MAX_N = N.MI_PNP_MAX_N
 
 
 def _model_matches(pts3, pts2, valid, what: str):
@@ -1352,8 +1360,7 @@ def pnp_refit(pts3: torch.Tensor, pts2: torch.Tensor, mask: torch.Tensor, r0: to
     ra, ta = r0.float().contiguous(), t0.float().contiguous()
     if tuple(ra.shape) != (b, 3, 3) or tuple(ta.shape) != (b, 3):
         raise RuntimeError(f"pnp_refit: the starting pose must be ({b}, 3, 3) and ({b}, 3), got {tuple(r0.shape)} and {tuple(t0.shape)}")
-    r = torch.empty((b, 3, 3), dtype=F32, device=q3.device)
-    t = torch.empty((b, 3), dtype=F32, device=q3.device)
+    r, t = _pose_outputs(b, q3.device)
     info = torch.empty((b, 6, 6), dtype=F32, device=q3.device)
     ok = torch.empty((b,), dtype=U8, device=q3.device)
     N.call("mi_pnp_refit", q3.data_ptr(), q2.data_ptr(), N.dev(v, U8, "mask"), N.dev(ra, F32, "r0"), N.dev(ta, F32, "t0"), b, n,
@@ -1366,20 +1373,15 @@ def pnp_ransac(pts3: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | Non
     """`mi_pnp_ransac`: hypotheses, MSAC selection and refine_rounds rounds of refit-and-rescore in two launches ->
     (R (B, 3, 3), t (B, 3), inlier (B, N) bool, best_h (B,) int32, count (B,) int32, rmse (B,) float32 in normalised units,
     info (B, 6, 6) float32, ok (B,) bool)."""
-    q3, q2, v, b, n = _model_matches(pts3, pts2, valid, "pnp_ransac")
-    h, work, wbytes = _ransac_workspace("mi_pnp_ransac_workspace_bytes", "pnp_ransac", b, n, num_hypotheses, q3.device)
-    r = torch.empty((b, 3, 3), dtype=F32, device=q3.device)
-    t = torch.empty((b, 3), dtype=F32, device=q3.device)
-    inlier = torch.empty((b, n), dtype=U8, device=q3.device)
-    best_h = torch.empty((b,), dtype=I32, device=q3.device)
-    count = torch.empty((b,), dtype=I32, device=q3.device)
-    rmse = torch.empty((b,), dtype=F32, device=q3.device)
-    info = torch.empty((b, 6, 6), dtype=F32, device=q3.device)
-    ok = torch.empty((b,), dtype=U8, device=q3.device)
-    N.call("mi_pnp_ransac", q3.data_ptr(), q2.data_ptr(), N.dev(v, U8, "valid") if v is not None else None, b, n, h,
-           float(threshold), int(refine_rounds), int(seed) & 0xFFFFFFFF, r.data_ptr(), t.data_ptr(), inlier.data_ptr(),
-           best_h.data_ptr(), count.data_ptr(), rmse.data_ptr(), info.data_ptr(), ok.data_ptr(), work.data_ptr(), wbytes,
-           N.stream_ptr())
+    rows = _model_matches(pts3, pts2, valid, "pnp_ransac")
+    b, n, dev = rows[3], rows[4], rows[0].device
+    r, t = _pose_outputs(b, dev)
+    inlier, best_h, count = _ransac_outputs(b, n, dev)
+    rmse = torch.empty((b,), dtype=F32, device=dev)
+    info = torch.empty((b, 6, 6), dtype=F32, device=dev)
+    ok = torch.empty((b,), dtype=U8, device=dev)
+    _ransac("mi_pnp_ransac", "pnp_ransac", rows, num_hypotheses, threshold, refine_rounds, seed,
+            (r, t, inlier, best_h, count, rmse, info, ok))
     return r, t, inlier.view(torch.bool), best_h, count, rmse, info, ok.view(torch.bool)
 
 
@@ -1396,31 +1398,20 @@ def homography_hypotheses(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.T
 
 def homography_refit(pts1: torch.Tensor, pts2: torch.Tensor, mask: torch.Tensor):
     """`mi_homography_refit`: the normalised DLT homography over the masked correspondences -> (H (B, 3, 3), ok (B,) bool)."""
-    q1, q2, v, b, n = _correspondences(pts1, pts2, mask, "homography_refit")
-    if v is None:
-        raise RuntimeError("homography_refit needs a mask")
-    h = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
-    ok = torch.empty((b,), dtype=U8, device=q1.device)
-    N.call("mi_homography_refit", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "mask"), b, n, h.data_ptr(), ok.data_ptr(),
-           N.stream_ptr())
-    return h, ok.view(torch.bool)
+    return _matrix_refit("mi_homography_refit", "homography_refit", pts1, pts2, mask)
 
 
 def homography_ransac(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, num_hypotheses: int,
                       threshold: float, refine_rounds: int = 3, seed: int = 0):
     """`mi_homography_ransac`: hypotheses, MSAC selection and refine_rounds rounds of refit-and-rescore in two launches ->
     (H (B, 3, 3), inlier (B, N) bool, best_h (B,) int32, count (B,) int32, MSAC cost (B,) float32)."""
-    q1, q2, v, b, n = _correspondences(pts1, pts2, valid, "homography_ransac")
-    h, work, wbytes = _ransac_workspace("mi_homography_ransac_workspace_bytes", "homography_ransac", b, n, num_hypotheses,
-                                        q1.device)
-    hm = torch.empty((b, 3, 3), dtype=F32, device=q1.device)
-    inlier = torch.empty((b, n), dtype=U8, device=q1.device)
-    best_h = torch.empty((b,), dtype=I32, device=q1.device)
-    count = torch.empty((b,), dtype=I32, device=q1.device)
-    cost = torch.empty((b,), dtype=F32, device=q1.device)
-    N.call("mi_homography_ransac", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "valid") if v is not None else None, b, n, h,
-           float(threshold), int(refine_rounds), int(seed) & 0xFFFFFFFF, hm.data_ptr(), inlier.data_ptr(), best_h.data_ptr(),
-           count.data_ptr(), cost.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    rows = _correspondences(pts1, pts2, valid, "homography_ransac")
+    b, n, dev = rows[3], rows[4], rows[0].device
+    hm = torch.empty((b, 3, 3), dtype=F32, device=dev)
+    inlier, best_h, count = _ransac_outputs(b, n, dev)
+    cost = torch.empty((b,), dtype=F32, device=dev)
+    _ransac("mi_homography_ransac", "homography_ransac", rows, num_hypotheses, threshold, refine_rounds, seed,
+            (hm, inlier, best_h, count, cost))
     return hm, inlier.view(torch.bool), best_h, count, cost
 
 
@@ -1439,7 +1430,7 @@ def homography_pose(h: torch.Tensor, pts1: torch.Tensor, pts2: torch.Tensor, mas
     pose_mask = torch.empty((b, n), dtype=U8, device=q1.device)
     rot = torch.empty((b,), dtype=U8, device=q1.device)
     ok = torch.empty((b,), dtype=U8, device=q1.device)
-    N.call("mi_homography_pose", N.dev(hh, F32, "H"), q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "mask") if v is not None else None,
+    N.call("mi_homography_pose", N.dev(hh, F32, "H"), q1.data_ptr(), q2.data_ptr(), N.opt(v, U8, "mask"),
            b, n, r.data_ptr(), t.data_ptr(), normal.data_ptr(), count.data_ptr(), pose_mask.data_ptr(), rot.data_ptr(),
            ok.data_ptr(), N.stream_ptr())
     return r, t, normal, count, pose_mask.view(torch.bool), rot.view(torch.bool), ok.view(torch.bool)
@@ -1458,16 +1449,16 @@ def two_view_select(e: torch.Tensor, h: torch.Tensor, pts1: torch.Tensor, pts2: 
     sh = torch.empty((b,), dtype=F32, device=q1.device)
     choice = torch.empty((b,), dtype=U8, device=q1.device)
     N.call("mi_two_view_select", N.dev(ee, F32, "E"), N.dev(hh, F32, "H"), q1.data_ptr(), q2.data_ptr(),
-           N.dev(v, U8, "valid") if v is not None else None, b, n, float(threshold_e), float(threshold_h), float(cut),
+           N.opt(v, U8, "valid"), b, n, float(threshold_e), float(threshold_h), float(cut),
            se.data_ptr(), sh.data_ptr(), choice.data_ptr(), N.stream_ptr())
     return se, sh, choice.view(torch.bool)
 
 
 # ---- K25 windowed bundle adjustment (include/mi355x_match.h, "windowed bundle adjustment") -----------------------------------
 
-BA_MAX_FRAMES = 16                         # MI_BA_MAX_FRAMES
-BA_MAX_LANDMARKS = 2048                    # MI_BA_MAX_LANDMARKS
-BA_MAX_ITERATIONS = 32                     # MI_BA_MAX_ITERATIONS
+BA_MAX_FRAMES = N.MI_BA_MAX_FRAMES
+BA_MAX_LANDMARKS = N.MI_BA_MAX_LANDMARKS
+BA_MAX_ITERATIONS = N.MI_BA_MAX_ITERATIONS
 
 
 def _ba_window(r: torch.Tensor, t: torch.Tensor, points: torch.Tensor, obs: torch.Tensor, vis: torch.Tensor, huber: float, what: str):
@@ -1487,11 +1478,6 @@ def _ba_window(r: torch.Tensor, t: torch.Tensor, points: torch.Tensor, obs: torc
     vv = _validity_bytes(vis)
     ptrs = (N.dev(rr, F32, "r"), N.dev(tt, F32, "t"), N.dev(xx, F32, "points"), N.dev(oo, F32, "obs"), N.dev(vv, U8, "vis"))
     return ptrs, (rr, tt, xx, oo, vv), b, f, l
-
-
-def _ba_workspace(b: int, f: int, l: int, device):
-    wbytes = int(N.load().mi_ba_workspace_bytes(b, f, l))
-    return torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=device), wbytes
 
 
 def ba_cost(r: torch.Tensor, t: torch.Tensor, points: torch.Tensor, obs: torch.Tensor, vis: torch.Tensor, huber: float = 0.0):
@@ -1522,7 +1508,7 @@ def ba_linearise(r: torch.Tensor, t: torch.Tensor, points: torch.Tensor, obs: to
     s = torch.empty((b, 6 * f, 6 * f), dtype=F32, device=dev)
     rhs = torch.empty((b, 6 * f), dtype=F32, device=dev)
     cost = torch.empty((b,), dtype=F32, device=dev)
-    work, wbytes = _ba_workspace(b, f, l, dev)
+    work, wbytes = _workspace("mi_ba_workspace_bytes", b, f, l, device=dev)
     N.call("mi_ba_linearise", *ptrs, b, f, l, nf, float(huber), s.data_ptr(), rhs.data_ptr(), cost.data_ptr(), work.data_ptr(), wbytes,
            N.stream_ptr())
     return s, rhs, cost
@@ -1548,7 +1534,7 @@ def ba_refine(r: torch.Tensor, t: torch.Tensor, points: torch.Tensor, obs: torch
     accepted = torch.empty((b,), dtype=I32, device=dev)
     info = torch.empty((b, 6 * f, 6 * f), dtype=F32, device=dev)
     ok = torch.empty((b,), dtype=U8, device=dev)
-    work, wbytes = _ba_workspace(b, f, l, dev)
+    work, wbytes = _workspace("mi_ba_workspace_bytes", b, f, l, device=dev)
     N.call("mi_ba_refine", *ptrs, b, f, l, nf, int(iterations), float(huber), ro.data_ptr(), to.data_ptr(), xo.data_ptr(),
            point_ok.data_ptr(), cost0.data_ptr(), cost.data_ptr(), accepted.data_ptr(), info.data_ptr(), ok.data_ptr(),
            work.data_ptr(), wbytes, N.stream_ptr())
@@ -1557,9 +1543,9 @@ def ba_refine(r: torch.Tensor, t: torch.Tensor, points: torch.Tensor, obs: torch
 
 # ---- K26 loop-closure retrieval (include/mi355x_match.h, "loop-closure retrieval") -------------------------------------------
 
-PLACE_MAX_DESCRIPTORS = 1024               # MI_PLACE_MAX_DESCRIPTORS
-PLACE_MAX_KEYFRAMES = 65536                # MI_PLACE_MAX_KEYFRAMES
-PLACE_MAX_CANDIDATES = 64                  # MI_PLACE_MAX_CANDIDATES
+PLACE_MAX_DESCRIPTORS = N.MI_PLACE_MAX_DESCRIPTORS
+PLACE_MAX_KEYFRAMES = N.MI_PLACE_MAX_KEYFRAMES
+PLACE_MAX_CANDIDATES = N.MI_PLACE_MAX_CANDIDATES
 
 
 def _place_bits(bits: torch.Tensor, valid: torch.Tensor | None, what: str):
@@ -1603,8 +1589,8 @@ def place_votes(db_bits: torch.Tensor, db_valid: torch.Tensor | None, q_bits: to
             raise RuntimeError(f"place_votes: frame_index must be ({q}, S), got {tuple(frame_index.shape)}")
         fi = frame_index.to(I32).contiguous()
         slots = int(fi.shape[1])
-    ptrs = [N.dev(db, I32, "db_bits"), N.dev(dbv, U8, "db_valid") if dbv is not None else None, n, kd, N.dev(qb, I32, "q_bits"),
-            N.dev(qv, U8, "q_valid") if qv is not None else None, q, kq, N.dev(fi, I32, "frame_index") if fi is not None else None,
+    ptrs = [N.dev(db, I32, "db_bits"), N.opt(dbv, U8, "db_valid"), n, kd, N.dev(qb, I32, "q_bits"),
+            N.opt(qv, U8, "q_valid"), q, kq, N.opt(fi, I32, "frame_index"),
             slots, 32 * words, int(max_distance), float(ratio)]
     dev = db.device
     votes = torch.empty((q, slots), dtype=I32, device=dev)
@@ -1640,16 +1626,16 @@ def place_select(votes: torch.Tensor, num_candidates: int, min_votes: int, excl_
     ptr = N.dev(v, I32, "votes")
     cand_index = torch.empty((q, int(num_candidates)), dtype=I32, device=v.device)
     cand_votes = torch.empty((q, int(num_candidates)), dtype=I32, device=v.device)
-    N.call("mi_place_select", ptr, q, n, N.dev(lo, I32, "excl_lo") if lo is not None else None,
-           N.dev(hi, I32, "excl_hi") if hi is not None else None, int(min_votes), int(num_candidates), cand_index.data_ptr(),
+    N.call("mi_place_select", ptr, q, n, N.opt(lo, I32, "excl_lo"),
+           N.opt(hi, I32, "excl_hi"), int(min_votes), int(num_candidates), cand_index.data_ptr(),
            cand_votes.data_ptr(), N.stream_ptr())
     return cand_index, cand_votes
 
 
 # ---- K18 dense RGB-D refinement (include/mi355x_match.h, "dense RGB-D refinement") ------------------------------------------
 
-ICP_MAX_STAGES = 4                         # MI_ICP_MAX_STAGES
-ICP_MAX_ITERATIONS = 64                    # MI_ICP_MAX_ITERATIONS
+ICP_MAX_STAGES = N.MI_ICP_MAX_STAGES
+ICP_MAX_ITERATIONS = N.MI_ICP_MAX_ITERATIONS
 ICP_STRIDES = (1, 2, 4, 8)
 ICP_SUMS = 29
 
@@ -1698,10 +1684,7 @@ def _rgbd_inputs(named_maps, r: torch.Tensor, t: torch.Tensor, camera, what: str
     cam = tuple(float(x) for x in camera)
     if len(cam) != 4:
         raise RuntimeError(f"{what}: camera must be (fx, fy, cx, cy), got {camera!r}")
-    wbytes = int(getattr(N.load(), workspace)(b, h, w))
-    if wbytes == 0:
-        raise RuntimeError(f"{what}: unsupported request (batch {b}, {h} x {w})")
-    work = torch.empty(((wbytes + 7) // 8,), dtype=torch.int64, device=first.device)
+    work, wbytes = _workspace(workspace, b, h, w, device=first.device, refusal=f"{what}: unsupported request (batch {b}, {h} x {w})")
     return keep, maps, rr, tt, cam, b, h, w, work, wbytes
 
 
@@ -1870,7 +1853,7 @@ def tsdf_integrate(volume: torch.Tensor, depth: torch.Tensor, r: torch.Tensor, t
     fx, fy, cx, cy = (float(x) for x in camera)
     N.call("mi_tsdf_integrate", ptr, *dims, *grid, float(max_weight), d.data_ptr(), int(d.dtype == U16), f, h, w, fx, fy, cx, cy,
            float(z_scale), float(min_depth), float(max_depth), N.dev(rr, F32, "r"), N.dev(tt, F32, "t"),
-           N.dev(act, U8, "active") if act is not None else None, N.stream_ptr())
+           N.opt(act, U8, "active"), N.stream_ptr())
     return volume
 
 
@@ -1928,10 +1911,8 @@ def _tsdf_surface_call(volume: torch.Tensor, origin, voxel_size: float, min_weig
     if mv < 0 or mt < 0:
         raise RuntimeError(f"{what}: the capacities must not be negative, got {max_vertices} and {max_triangles}")
     b, dev = dims[0], volume.device
-    wbytes = int(N.load().mi_tsdf_surface_workspace_bytes(*dims))
-    if wbytes == 0:
-        raise RuntimeError(f"{what}: unsupported volume {tuple(volume.shape)}: vertex ids need 12 * NZ * NY * NX < 2^31")
-    work = torch.empty((wbytes // 8,), dtype=torch.int64, device=dev)
+    work, wbytes = _workspace("mi_tsdf_surface_workspace_bytes", *dims, device=dev,
+                              refusal=f"{what}: unsupported volume {tuple(volume.shape)}: vertex ids need 12 * NZ * NY * NX < 2^31")
     counts = torch.empty((b, 2), dtype=torch.int32, device=dev)
     vertex = torch.empty((b, mv, 4), dtype=F32, device=dev) if mv else None
     normal = torch.empty((b, mv, 4), dtype=F32, device=dev) if mv and normals else None
@@ -2022,7 +2003,7 @@ def tsdf_integrate_gray(volume: torch.Tensor, intensity: torch.Tensor, depth: to
     fx, fy, cx, cy = (float(x) for x in camera)
     N.call("mi_tsdf_integrate_gray", ptr, iptr, *dims, *grid, float(max_weight), d.data_ptr(), int(d.dtype == U16), g.data_ptr(),
            int(g.dtype == U8), f, h, w, fx, fy, cx, cy, float(z_scale), float(min_depth), float(max_depth), N.dev(rr, F32, "r"),
-           N.dev(tt, F32, "t"), N.dev(act, U8, "active") if act is not None else None, N.stream_ptr())
+           N.dev(tt, F32, "t"), N.opt(act, U8, "active"), N.stream_ptr())
     return volume, intensity
 
 
@@ -2065,7 +2046,7 @@ def tsdf_sample_gray(intensity: torch.Tensor, points: torch.Tensor, origin, voxe
 
 # ---- K16 frame ingest (sample/visual_odometry.py:65-92 load_image_from_array) ------------------------------------------
 
-INGEST_MAX_DIM = 16384             # include/mi355x_match.h MI_INGEST_MAX_DIM
+INGEST_MAX_DIM = N.MI_INGEST_MAX_DIM
 _CHANNEL_ORDERS = {"bgr": N.MI_INGEST_BGR, "rgb": N.MI_INGEST_RGB}
 
 

@@ -46,6 +46,138 @@ def test_binding_covers_the_header(lib_path):
     _native.load()
     with _native.debug_library() as dbg:                     # the debug build exports both headers
         assert dbg.mi_abi_version() == 3
+    # the binding is derived from the header, so the names above agree by construction: what is pinned by hand is one
+    # entry of every kind the reader's type map knows, and that no MI_API declaration went unread
+    from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_longlong, c_size_t, c_uint32, c_void_p
+    vp, i, f, prm = c_void_p, c_int, c_float, POINTER(_native.MatchParams)
+    pinned = {
+        "mi_cost_logscores_bits": ([vp, vp, i, i, i, i, i, c_double, vp, i, vp], i),                        # double
+        "mi_voxel_downsample": ([vp, vp, i, c_int64, i, vp, vp, vp, vp, vp, c_size_t, vp], i),                 # int64_t, size_t
+        "mi_histogram": ([vp, i, i, c_longlong, i, i, vp, vp], i),                                             # long long
+        "mi_essential_hypotheses": ([vp, vp, vp, i, i, i, f, c_uint32, vp, vp, vp, vp], i),                    # uint32_t
+        "mi_candidate_layout": ([i, i, POINTER(i), POINTER(i)], i),                                            # host int *
+        "mi_match_pairs_workspace_bytes": ([i, i, i, prm], c_size_t),                                          # struct *, size_t
+        "mi_error_string": ([i], c_char_p),                                                                    # char * return
+        "mi_sinkhorn_dots_status_word": ([vp, i, i, i], vp),                                                   # pointer return
+        "mi_abi_version": ([], i),                                                                             # (void)
+        "mi_icp_linearise": ([vp] * 6 + [i, i, i, f, f, f, f, i, f, f, vp, vp, c_size_t, vp], i),              # device double *
+    }
+    for name, (argtypes, restype) in pinned.items():
+        assert _native.SIGNATURES[name] == argtypes and _native.RESTYPES[name] is restype, name
+    assert _native.DEBUG_SIGNATURES["mi_debug_tuner_script"] == [i, POINTER(i), POINTER(i), POINTER(c_double), POINTER(i)]
+    assert _native.RESTYPES["mi_debug_tuner_script"] is i                                                  # host const double *
+
+    def api_tokens(path):                                    # outside comments and the preprocessor lines that define it
+        text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+        return len(re.findall(r"\bMI_API\b", re.sub(r"^\s*#.*$", "", text, flags=re.M)))
+
+    assert len(_native.SIGNATURES) == api_tokens(HEADER) == 118
+    assert len(_native.DEBUG_SIGNATURES) == api_tokens(DEBUG_HEADER) == 7
+    for name in _native.SIGNATURES:                          # the types reach the loaded functions
+        fn = getattr(_native.load(), name)
+        assert list(fn.argtypes) == _native.SIGNATURES[name] and fn.restype is _native.RESTYPES[name], name
+
+
+def test_header_reader_fails_loudly():
+    """A type outside the reader's map names the function it stands in; a declaration the pattern cannot read is counted
+    and refused, never skipped."""
+    from onnx_image_processing_amd._native import read_header
+    good = "#define MI_API x\nMI_API int mi_a(const float *p, int n);\nMI_API size_t mi_b(void);\n"
+    sigs, res, fields, consts = read_header(good)
+    assert sigs == {"mi_a": [ctypes.c_void_p, ctypes.c_int], "mi_b": []} and res["mi_b"] is ctypes.c_size_t
+    assert fields is None and consts == {}
+    with pytest.raises(TypeError, match="mi_bad_arg.*unsigned short"):
+        read_header(good + "MI_API int mi_bad_arg(int n, unsigned short k);\n")
+    with pytest.raises(TypeError, match="mi_bad_ret.*short"):
+        read_header(good + "MI_API short mi_bad_ret(int n);\n")
+    with pytest.raises(TypeError, match="3 MI_API declarations, 2 of them read"):
+        read_header(good + "MI_API int mi_callback(void (*fn)(int), int n);\n")
+    with pytest.raises(TypeError, match="MI_B"):
+        read_header("enum { MI_A = 0, MI_B };\n")
+    assert read_header("/* #define MI_NOT 1 */\n#define MI_X 7\n#define MI_Y 1e-3f\n#define MI_Z 0.5\nenum { MI_N = -1 };")[3] == {
+        "MI_X": 7, "MI_Y": 1e-3, "MI_Z": 0.5, "MI_N": -1}
+
+
+_OPS_ALIASES = {
+    "TILE_COUNTER_BYTES": "MI_TILE_COUNTER_BYTES", "DOTS_MIN_EPSILON": "MI_DOTS_MIN_EPSILON",
+    "AKAZE_KAPPA_MIN": "MI_AKAZE_KAPPA_MIN", "AKAZE_KAPPA_MAX": "MI_AKAZE_KAPPA_MAX",
+    "THRESHOLD_MAX_BINS": "MI_THRESHOLD_MAX_BINS", "THRESHOLD_MAX_CLASSES": "MI_THRESHOLD_MAX_CLASSES",
+    "POSE_MAX_N": "MI_POSE_MAX_N", "POSE_MAX_REFINE_ROUNDS": "MI_POSE_MAX_REFINE_ROUNDS", "RIGID_MAX_N": "MI_RIGID_MAX_N",
+    "PNP_MAX_N": "MI_PNP_MAX_N", "BA_MAX_FRAMES": "MI_BA_MAX_FRAMES", "BA_MAX_LANDMARKS": "MI_BA_MAX_LANDMARKS",
+    "BA_MAX_ITERATIONS": "MI_BA_MAX_ITERATIONS", "PLACE_MAX_DESCRIPTORS": "MI_PLACE_MAX_DESCRIPTORS",
+    "PLACE_MAX_KEYFRAMES": "MI_PLACE_MAX_KEYFRAMES", "PLACE_MAX_CANDIDATES": "MI_PLACE_MAX_CANDIDATES",
+    "ICP_MAX_STAGES": "MI_ICP_MAX_STAGES", "ICP_MAX_ITERATIONS": "MI_ICP_MAX_ITERATIONS", "INGEST_MAX_DIM": "MI_INGEST_MAX_DIM",
+    "MI_SOLVER_DEFAULT": "MI_SOLVER_DEFAULT", "MI_SOLVER_MULTI_LAUNCH": "MI_SOLVER_MULTI_LAUNCH",
+    "MI_SOLVER_NO_FORK": "MI_SOLVER_NO_FORK", "MI_SOLVER_DOTS_BELOW_1024": "MI_SOLVER_DOTS_BELOW_1024",
+    "MI_SCHEDULE_UNDECIDED": "MI_SCHEDULE_UNDECIDED", "MI_SCHEDULE_CALLER_HELPER": "MI_SCHEDULE_CALLER_HELPER",
+    "MI_SCHEDULE_TWO_HELPERS": "MI_SCHEDULE_TWO_HELPERS", "MI_SCHEDULE_UNSPLIT": "MI_SCHEDULE_UNSPLIT"}
+
+
+def test_struct_layout_and_constants_against_the_compiler(tmp_path):
+    """What the binding reads out of the header is what a C compiler makes of it: sizeof / offsetof of mi_match_params
+    against ctypes' layout of MatchParams, and the value of every MI_* constant (a macro with an f suffix is a float in C:
+    the attribute holds the literal, the compiler its float32 rounding).  The ops aliases equal their sources."""
+    import shutil
+    import struct
+    import subprocess
+    from onnx_image_processing_amd import _native, ops
+    if shutil.which("gcc") is None:
+        pytest.skip("gcc not available")
+    constants = {k: v for k, v in vars(_native).items() if k.startswith("MI_") and isinstance(v, (int, float))}
+    assert len(constants) == 25 + 20                  # enum members + numeric macros of the header
+    assert constants["MI_SCHEDULE_UNDECIDED"] == -1 and constants["MI_POSE_MAX_N"] == 2048
+    fields = [name for name, _ in _native.MatchParams._fields_]
+    assert fields == ["block_size", "nms_radius", "max_keypoints", "score_threshold", "border_margin", "num_pairs", "pair_geom",
+                      "pair_thr", "bad_plan", "normalize_descriptors", "epsilon", "unused_score", "sinkhorn_iterations",
+                      "max_matches", "match_threshold", "flags"]
+    lines = ['#include <stdio.h>', '#include "mi355x_match.h"', '#include "mi355x_match_debug.h"', 'int main(void) {',
+             '  printf("sizeof %zu\\n", sizeof(mi_match_params));']
+    lines += [f'  printf("offsetof {f} %zu\\n", offsetof(mi_match_params, {f}));' for f in fields]
+    lines += [f'  printf("{k} %.17g\\n", (double){k});' for k in constants]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines + ["  return 0;", "}", ""]))
+    exe = str(tmp_path / "layout")
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", f"-I{os.path.join(ROOT, 'include')}", str(src), "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split("\n")
+    assert out[0] == f"sizeof {ctypes.sizeof(_native.MatchParams)}"
+    assert out[1:1 + len(fields)] == [f"offsetof {f} {getattr(_native.MatchParams, f).offset}" for f in fields]
+    header = open(HEADER).read()
+    for line, (k, v) in zip(out[1 + len(fields):], constants.items()):
+        name, value = line.split()
+        if re.search(rf"#define {k}\s+\S+f\s", header):
+            v = struct.unpack("f", struct.pack("f", v))[0]
+        assert name == k and float(value) == v, (line, v)
+    for alias, source in _OPS_ALIASES.items():
+        assert getattr(ops, alias) == constants[source] and type(getattr(ops, alias)) is type(constants[source]), alias
+    assert ops._PIX == {torch.uint8: _native.MI_PIX_U8, torch.uint16: _native.MI_PIX_U16, torch.int32: _native.MI_PIX_I32,
+                        torch.float32: _native.MI_PIX_F32}
+    assert ops._CHANNEL_ORDERS == {"bgr": _native.MI_INGEST_BGR, "rgb": _native.MI_INGEST_RGB}
+    assert (_native.MI_BAD_RAW, _native.MI_BAD_SOFT, _native.MI_BAD_HARD, _native.MI_DIST_L2, _native.MI_DIST_L1) == (0, 1, 2, 0, 1)
+    assert (ops.POSE_MAX_N, ops.THRESHOLD_MAX_BINS, ops.DOTS_MIN_EPSILON, ops.AKAZE_KAPPA_MIN, ops.AKAZE_KAPPA_MAX) == (
+        2048, 65536, 0.005, 1e-3, 1e6)
+
+
+@pytest.mark.parametrize("nbytes", [0, 1, 8, 15, 16, 17, 255])
+def test_workspace_helper_rounds_up_and_reports_the_queried_size(monkeypatch, nbytes):
+    """ops._workspace: a tensor of at least the queried bytes whose size is a multiple of 16, the unrounded count for the
+    library, and the op's own refusal when the query answers 0.  A stand-in answers the size query; the tensor is made
+    on the CPU."""
+    from types import SimpleNamespace
+    from onnx_image_processing_amd import _native, ops
+    seen = []
+    monkeypatch.setattr(_native, "load", lambda: SimpleNamespace(mi_fake_workspace_bytes=lambda *a: seen.append(a) or nbytes))
+    work, wbytes = ops._workspace("mi_fake_workspace_bytes", 2, 3, 5, device="cpu")
+    assert seen == [(2, 3, 5)] and wbytes == nbytes
+    assert work.dtype == torch.int64 and work.dim() == 1 and work.device.type == "cpu"
+    size = work.numel() * 8
+    assert size % 16 == 0 and nbytes <= size < nbytes + 16
+    if nbytes == 0:
+        with pytest.raises(RuntimeError, match=r"^some_op: unsupported request \(batch 2\)$"):
+            ops._workspace("mi_fake_workspace_bytes", 2, device="cpu", refusal="some_op: unsupported request (batch 2)")
+    else:
+        assert ops._workspace("mi_fake_workspace_bytes", 2, device="cpu", refusal="never raised")[1] == nbytes
 
 
 def _exported(path):
