@@ -3,10 +3,16 @@ from __future__ import annotations
 
 import ast
 import os
+import subprocess
 
 import numpy as np
+import pytest
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+NATIVE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native")
+
+# the host's address and undefined-behaviour sanitizers, for a stand-alone program built by build_host(..., hip=True)
+SANITIZE = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-g"]
 
 
 def load_golden(name: str):
@@ -120,3 +126,58 @@ def check_match_sets(got: dict, want: dict, max_matches: int, tol: float = 1e-4,
         for k in set(got) - set(want):
             assert k in mutual and abs(mutual[k] - got[k]) <= tol, f"{k} (score {got[k]}) is not a mutual match of the reference"
     return "cut"
+
+
+# ---- stand-alone host programs (tests/native/*.cpp) and the built library --------------------------------------------------------
+def build_host(tmp_dir, source_name, *, hip, extra=()):
+    """Compile tests/native/<source_name> into a program under `tmp_dir` and return its path.  hip=True: the library's own
+    flags at -O1, without those of a shared object (the source includes device headers); hip=False: plain C++17 with
+    contraction off, so that float32 arithmetic is numpy's operation by operation.  `extra` (hip only) goes after -O1."""
+    from onnx_image_processing_amd.build import FLAGS, _hipcc
+    stem = os.path.splitext(source_name)[0]
+    exe = str(tmp_dir / (stem + "_san" if extra else stem))
+    src = os.path.join(NATIVE, source_name)
+    if hip:
+        flags = [f for f in FLAGS if f not in ("-fPIC", "-fvisibility=hidden", "-O3")]
+        argv = [_hipcc(), *flags, "-O1", *extra, "-x", "hip", src, "-o", exe]
+    else:
+        assert not extra, extra
+        argv = [_hipcc(), "-x", "c++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", src, "-o", exe, "-lm"]
+    r = subprocess.run(argv, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return exe
+
+
+def host_program(source_name, *, hip):
+    """A module-scoped fixture that builds tests/native/<source_name> once for the test file that assigns it to a name."""
+    @pytest.fixture(scope="module")
+    def program(tmp_path_factory):
+        return build_host(tmp_path_factory.mktemp(os.path.splitext(source_name)[0]), source_name, hip=hip)
+    return program
+
+
+def run_host(exe, args, text="", *, binary=False):
+    """Run a host program over `text` on its standard input; `args` is one mode string or an argument list.  Its exit status
+    must be 0 and its stderr free of sanitizer reports.  Returns the non-empty output lines split into fields, or with
+    binary=True (bytes in, bytes out) the raw standard output."""
+    args = [args] if isinstance(args, str) else list(args)
+    r = subprocess.run([exe, *args], input=text, capture_output=True, text=not binary)
+    err = r.stderr.decode(errors="replace") if binary else r.stderr
+    assert r.returncode == 0 and "runtime error" not in err and "AddressSanitizer" not in err, (args, r.returncode, err[-2000:])
+    return r.stdout if binary else [ln.split() for ln in r.stdout.split("\n") if ln]
+
+
+def run_records(exe, args, records, fmt="%.17g"):
+    """One record of numbers per input line, one float64 array per output line, as many out as in."""
+    text = "\n".join(" ".join(fmt % float(x) for x in rec) for rec in records)
+    out = [np.array(ln, np.float64) for ln in run_host(exe, args, text)]
+    assert len(out) == len(records)
+    return out
+
+
+def native_lib():
+    """The library, built if need be, for the argument checks that return before any launch."""
+    from onnx_image_processing_amd import _native
+    from onnx_image_processing_amd.build import build
+    build(verbose=False)
+    return _native.load()

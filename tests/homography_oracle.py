@@ -16,15 +16,7 @@ MIN_POSE_ROWS = 4
 
 def sample_ranks(seed, b, h, nv):
     """the 4 distinct ranks (among the valid rows, index order) of hypothesis h of pair b: K15's draws for slots 0 .. 3"""
-    taken, out = [], []
-    for s in range(4):
-        r = PO.draw(seed, b, h, s) % (nv - s)
-        for q in sorted(taken):
-            if r >= q:
-                r += 1
-        taken.append(r)
-        out.append(r)
-    return out
+    return PO.sample_ranks(seed, b, h, nv, 4)
 
 
 def planted_h(R, t, normal, distance):

@@ -31,15 +31,7 @@ SMALL_ANGLE = 1e-8               # ICP_SMALL_ANGLE
 
 def sample_ranks(seed, b, h, nv):
     """the 4 distinct ranks (among the valid rows, index order) of hypothesis h of pair b: slots 0 .. 2 solve, slot 3 picks"""
-    taken, out = [], []
-    for s in range(4):
-        r = PO.draw(seed, b, h, s) % (nv - s)
-        for q in sorted(taken):
-            if r >= q:
-                r += 1
-        taken.append(r)
-        out.append(r)
-    return out
+    return PO.sample_ranks(seed, b, h, nv, 4)
 
 
 # ---- the restatement of csrc/rigid_math.h and csrc/pnp_math.h on float32 scalars ---------------------------------------------

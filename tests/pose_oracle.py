@@ -24,10 +24,10 @@ def draw(seed, b, h, s):
     return mix((mix((mix((seed + 0x9E3779B9) & M32) + b) & M32) + (8 * h + s)) & M32)
 
 
-def sample_ranks(seed, b, h, nv):
-    """the 8 distinct ranks (among the valid rows, index order) of hypothesis h of pair b"""
+def sample_ranks(seed, b, h, nv, k=8):
+    """the k distinct ranks (among the valid rows, index order) of hypothesis h of pair b; draw index 8 * h + s for every k"""
     taken, out = [], []
-    for s in range(8):
+    for s in range(k):
         r = draw(seed, b, h, s) % (nv - s)
         for q in sorted(taken):
             if r >= q:
@@ -37,8 +37,8 @@ def sample_ranks(seed, b, h, nv):
     return out
 
 
-def sample_ranks_batch(seed, batch, num_hyp, nv):
-    """sample_ranks for every (b, h) at once: (batch, num_hyp, 8) int64"""
+def sample_ranks_batch(seed, batch, num_hyp, nv, k=8):
+    """sample_ranks for every (b, h) at once: (batch, num_hyp, k) int64"""
     def mixv(x):
         x = x & M32
         x ^= x >> 16
@@ -50,8 +50,8 @@ def sample_ranks_batch(seed, batch, num_hyp, nv):
     b = np.arange(batch, dtype=np.uint64)[:, None]
     h = np.arange(num_hyp, dtype=np.uint64)[None, :]
     base = mixv(np.uint64(mix((seed + 0x9E3779B9) & M32)) + b)
-    out = np.zeros((batch, num_hyp, 8), np.int64)
-    for s in range(8):
+    out = np.zeros((batch, num_hyp, k), np.int64)
+    for s in range(k):
         r = (mixv(base + (np.uint64(8) * h + np.uint64(s))) % np.uint64(nv - s)).astype(np.int64)
         taken = np.sort(out[..., :s], axis=-1)
         for j in range(s):

@@ -13,15 +13,7 @@ DEGENERATE = 1e-6
 
 def sample_ranks(seed, b, h, nv):
     """the 3 distinct ranks (among the valid rows, index order) of hypothesis h of pair b"""
-    taken, out = [], []
-    for s in range(3):
-        r = PO.draw(seed, b, h, s) % (nv - s)
-        for q in sorted(taken):
-            if r >= q:
-                r += 1
-        taken.append(r)
-        out.append(r)
-    return out
+    return PO.sample_ranks(seed, b, h, nv, 3)
 
 
 def lift_f32(kp_yx, depth, k_inv, z_scale, min_depth, max_depth, valid_in=None):
@@ -222,10 +214,5 @@ def lifted(k1, k2, d1, d2, K):
 
 
 def sample_ranks_batch(seed, batch, num_hyp, nv):
-    """sample_ranks for every (b, h) at once: (batch, num_hyp, 3) int64 (the first 3 slots of K15's batch sampler differ from
-    it only in the modulus, so this restates them)"""
-    out = np.zeros((batch, num_hyp, 3), np.int64)
-    for b in range(batch):
-        for h in range(num_hyp):
-            out[b, h] = sample_ranks(seed, b, h, nv)
-    return out
+    """sample_ranks for every (b, h) at once: (batch, num_hyp, 3) int64"""
+    return PO.sample_ranks_batch(seed, batch, num_hyp, nv, 3)

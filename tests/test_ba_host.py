@@ -6,8 +6,6 @@ compiled for the host in tests/native/ba_host.cpp -- once more under the host sa
 window of tests/test_gpu_ba.py must meet (the oracle has converged) and the MEASUREMENTS behind every tolerance of that file,
 asserted against its constants so that neither can drift from the other."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,6 +13,7 @@ import torch
 
 import ba_oracle as BO
 import test_gpu_ba as G
+from helpers import SANITIZE, build_host, host_program, run_host
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd.synth import rgbd_camera, synth_ba_window
 
@@ -272,26 +271,8 @@ def test_module_scheme_on_the_oracle_clears_exactly_the_planted_outliers():
 
 
 # ---- the kernels' arithmetic on the host ---------------------------------------------------------------------------------------
-def _build(tmp, name, extra):
-    from onnx_image_processing_amd.build import FLAGS, _hipcc
-    exe = str(tmp / name)
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "ba_host.cpp")
-    flags = [f for f in FLAGS if f not in ("-fPIC", "-fvisibility=hidden", "-O3")]
-    r = subprocess.run([_hipcc(), *flags, "-O1", *extra, "-x", "hip", src, "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
-
-
-@pytest.fixture(scope="module")
-def ba_host(tmp_path_factory):
-    """tests/native/ba_host.cpp: the kernels' own lines, 3x3 inverse and LDL^T, compiled for the host"""
-    return _build(tmp_path_factory.mktemp("ba_host"), "ba_host", [])
-
-
-def _run(exe, mode, text):
-    r = subprocess.run([exe, mode], input=text, capture_output=True, text=True)
-    assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, (mode, r.stderr[-2000:])
-    return [ln.split() for ln in r.stdout.split("\n") if ln]
+# tests/native/ba_host.cpp: the kernels' own lines, 3x3 inverse and LDL^T, compiled for the host
+ba_host = host_program("ba_host.cpp", hip=True)
 
 
 def _bits(x):
@@ -320,7 +301,7 @@ def _lines_text(hub, rt, X, uv):
 def test_native_lines_return_the_restatements_bits(ba_host):
     w, X, rt, uv = _lines_input()
     for hub in (0.0, F32(0.02)):
-        out = np.array([[float(v) for v in ln] for ln in _run(ba_host, "lines", _lines_text(hub, rt, X, uv))], F64)
+        out = np.array([[float(v) for v in ln] for ln in run_host(ba_host, "lines", _lines_text(hub, rt, X, uv))], F64)
         ln = BO.frame_lines(rt[:9].reshape(3, 3), rt[9:], X, uv, hub, F32)
         assert not ln["ok"][3] and ln["ok"].sum() >= 62 and np.array_equal(out[:, 0] != 0, ln["ok"])
         want = np.concatenate([ln["ju"], ln["jv"], ln["xu"], ln["xv"], ln["ru"][:, None], ln["rv"][:, None], ln["e2"][:, None],
@@ -348,7 +329,7 @@ def _inv3_input():
 
 def test_native_inverse_returns_the_restatements_bits(ba_host):
     rows = _inv3_input()
-    out = np.array([[float(v) for v in ln] for ln in _run(ba_host, "inv3", "\n".join(_fmt(r) for r in rows))], F64)
+    out = np.array([[float(v) for v in ln] for ln in run_host(ba_host, "inv3", "\n".join(_fmt(r) for r in rows))], F64)
     ok = np.zeros(len(rows), bool)
     vi = np.zeros((len(rows), 6), F32)
     for lam in np.unique(rows[:, 0]):
@@ -385,7 +366,7 @@ def _ldlt_text(systems):
 
 def test_native_ldlt_returns_the_restatements_bits(ba_host):
     systems = _ldlt_input()
-    out = _run(ba_host, "ldlt", _ldlt_text(systems))
+    out = run_host(ba_host, "ldlt", _ldlt_text(systems))
     assert len(out) == len(systems)
     for (S, b), ln in zip(systems, out):
         x, ok = BO.ldlt_solve(S, b)
@@ -399,11 +380,11 @@ def test_native_ldlt_returns_the_restatements_bits(ba_host):
 
 def test_native_harness_under_the_host_sanitizers(tmp_path):
     """the same stand-alone program built with the host's address and undefined-behaviour sanitizers, run once over every mode"""
-    exe = _build(tmp_path, "ba_host_san", ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-g"])
+    exe = build_host(tmp_path, "ba_host.cpp", hip=True, extra=SANITIZE)
     w, X, rt, uv = _lines_input()
-    assert len(_run(exe, "lines", _lines_text(F32(0.02), rt, X, uv))) == 64
-    assert len(_run(exe, "inv3", "\n".join(_fmt(r) for r in _inv3_input()))) == 200
-    assert len(_run(exe, "ldlt", _ldlt_text(_ldlt_input()))) == 8
+    assert len(run_host(exe, "lines", _lines_text(F32(0.02), rt, X, uv))) == 64
+    assert len(run_host(exe, "inv3", "\n".join(_fmt(r) for r in _inv3_input()))) == 200
+    assert len(run_host(exe, "ldlt", _ldlt_text(_ldlt_input()))) == 8
 
 
 # ---- the condition on the parity windows, and the measurements behind the GPU tolerances ---------------------------------------

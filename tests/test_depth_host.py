@@ -22,6 +22,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import native_lib
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "depth_frontend.npz")
 F32 = np.float32
@@ -220,16 +222,9 @@ def test_constructor_contract_and_no_cpu_path():
     assert np.array_equal(uu[0, :, 0].numpy(), u)
 
 
-def _lib():
-    from onnx_image_processing_amd.build import build
-    from onnx_image_processing_amd import _native
-    build(verbose=False)
-    return _native.load()
-
-
 def test_argument_errors_before_any_launch():
     """MI_E_* from the host checks (no GPU is touched: these return before the first launch)."""
-    lib = _lib()
+    lib = native_lib()
     buf = ctypes.create_string_buffer(1 << 12)
     p = ctypes.c_void_p((ctypes.addressof(buf) + 255) // 256 * 256)
     odd = ctypes.c_void_p(p.value + 2)

@@ -25,13 +25,13 @@ import pytest
 import torch
 
 import ba_oracle as BO
+from gpu_common import DEV, GPU, gpu
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.pytorch_model.geometry import BundleAdjuster
 from onnx_image_processing_amd.synth import rgbd_camera, synth_ba_window
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda"
+pytestmark = GPU
 K = rgbd_camera()
 FOCAL = 500.0
 ITERATIONS = 10
@@ -86,11 +86,8 @@ def refine_deviation(w, i, res, ref):
     return rot, np.abs(t - ref["t"]).max(), np.abs(X - ref["X"]).max(), abs(res["cost"] - ref["cost"]) / ref["cost"]
 
 
-def gpu(*arrays):
-    return [torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for a in arrays]
-
-
-def bits(t):
+def flat_bits(t):
+    """the bytes of a tensor of any rank, a scalar included"""
     return t.contiguous().reshape(-1).view(torch.uint8)
 
 
@@ -148,9 +145,9 @@ def test_refine_matches_the_oracle_and_its_info_is_the_linearisation_at_the_resu
         assert np.array_equal(point_ok[i].cpu().numpy(), BO.active(w["vis"][i]))
         assert abs(float(cost0[i]) - refs[i]["cost0"]) <= COST_RTOL * refs[i]["cost0"]
     nf = w["nf"]
-    assert torch.equal(bits(ro[:, :nf]), bits(r[:, :nf])) and torch.equal(bits(to[:, :nf]), bits(t[:, :nf]))    # held frames: the inputs' bits
+    assert torch.equal(flat_bits(ro[:, :nf]), flat_bits(r[:, :nf])) and torch.equal(flat_bits(to[:, :nf]), flat_bits(t[:, :nf]))    # held frames: the inputs' bits
     s, _, c = ops.ba_linearise(ro, to, xo, o, v, nf, w["huber"])
-    assert torch.equal(bits(s), bits(info)) and torch.equal(bits(c), bits(cost))
+    assert torch.equal(flat_bits(s), flat_bits(info)) and torch.equal(flat_bits(c), flat_bits(cost))
 
 
 def test_inactive_landmarks_take_no_part():
@@ -166,7 +163,7 @@ def test_inactive_landmarks_take_no_part():
     assert not e2[:, :, :2].any() and torch.isfinite(cost).all()
     out = ops.ba_refine(r, t, x, o, v, w["nf"], ITERATIONS, 0.0)
     assert out[8].all() and not out[3][:, :2].any()
-    assert torch.equal(bits(out[2][:, :2]), bits(x[:, :2]))
+    assert torch.equal(flat_bits(out[2][:, :2]), flat_bits(x[:, :2]))
     assert torch.equal(out[3], active)
     for i in range(3):
         ref = BO.refine(w["R0"][i], w["t0"][i], x[i].cpu().numpy(), w["obs"][i], v[i].cpu().numpy(), w["nf"], ITERATIONS, 0.0)
@@ -183,9 +180,9 @@ def test_refused_windows_return_their_inputs_and_leave_their_neighbours_alone():
     v2[2, 0] = True                                      # window 2: every landmark seen once: none active
     out = ops.ba_refine(r, t, x2, o, v2, 1, ITERATIONS, 0.0)
     assert out[8].tolist() == [True, False, False]
-    assert all(torch.equal(bits(a[0]), bits(b[0])) for a, b in zip(out, base))
+    assert all(torch.equal(flat_bits(a[0]), flat_bits(b[0])) for a, b in zip(out, base))
     for i in (1, 2):
-        assert torch.equal(bits(out[0][i]), bits(r[i])) and torch.equal(bits(out[1][i]), bits(t[i])) and torch.equal(bits(out[2][i]), bits(x2[i]))
+        assert torch.equal(flat_bits(out[0][i]), flat_bits(r[i])) and torch.equal(flat_bits(out[1][i]), flat_bits(t[i])) and torch.equal(flat_bits(out[2][i]), flat_bits(x2[i]))
         assert not out[3][i].any() and int(out[6][i]) == 0 and not out[7][i].any()
     assert torch.isinf(out[4][1]) and torch.isinf(out[5][1]) and float(out[4][2]) == 0.0 and float(out[5][2]) == 0.0
     e2, cost, active = ops.ba_cost(r, t, x2, o, v2, 0.0)
@@ -235,17 +232,17 @@ def test_outputs_are_fully_written_reproducible_and_blind_to_unseen_observations
         v[:, 1, 5::7] = False
     a = _raw(name, r, t, x, o, v, 0xFF)                  # 0xFF bytes: NaN floats, -1 integers
     b = _raw(name, r, t, x, o, v, 0x00)
-    assert all(torch.equal(bits(p), bits(q)) for p, q in zip(a, b))          # every output byte written; two runs agree
+    assert all(torch.equal(flat_bits(p), flat_bits(q)) for p, q in zip(a, b))          # every output byte written; two runs agree
     assert not any(torch.isnan(p).any() for p in a if p.dtype == torch.float32) and a[14].bool().all()
     o2 = o.clone()
     o2[~v] = float("nan")                                # unseen entries may hold anything
     o2[:, 0][~v[:, 0]] = 1e30
     c = _raw(name, r, t, x, o2, v, 0xFF)
-    assert all(torch.equal(bits(p), bits(q)) for p, q in zip(a, c))
+    assert all(torch.equal(flat_bits(p), flat_bits(q)) for p, q in zip(a, c))
     perm = [2, 0, 1]                                     # a window's result does not depend on its place in the batch
     d = ops.ba_refine(r[perm].contiguous(), t[perm].contiguous(), x[perm].contiguous(), o[perm].contiguous(), v[perm].contiguous(),
                       w["nf"], ITERATIONS, w["huber"])
-    assert torch.equal(bits(d[0]), bits(a[6][perm])) and torch.equal(bits(d[2]), bits(a[8][perm])) and torch.equal(bits(d[7]), bits(a[13][perm]))
+    assert torch.equal(flat_bits(d[0]), flat_bits(a[6][perm])) and torch.equal(flat_bits(d[2]), flat_bits(a[8][perm])) and torch.equal(flat_bits(d[7]), flat_bits(a[13][perm]))
 
 
 def test_the_three_entries_replay_from_one_graph():
@@ -272,7 +269,7 @@ def test_the_three_entries_replay_from_one_graph():
             dst.copy_(src)
         g.replay()
         torch.cuda.synchronize()
-        assert all(torch.equal(bits(a), bits(b)) for a, b in zip(out, eager[i])), i
+        assert all(torch.equal(flat_bits(a), flat_bits(b)) for a, b in zip(out, eager[i])), i
 
 
 def test_bundle_adjuster_clears_the_outliers_and_ends_below_the_truth():
@@ -294,7 +291,7 @@ def test_bundle_adjuster_clears_the_outliers_and_ends_below_the_truth():
         print(f"window {i}: cost {float(cost[i]):.3f} px^2, at the truth's inliers {truth * FOCAL ** 2:.3f} px^2")
         assert float(cost[i]) < truth * FOCAL ** 2
     single = m(R0[1], t0[1], X0[1], kp[1], vis[1])
-    assert single[0].shape == (8, 3, 3) and torch.equal(bits(single[2]), bits(X[1])) and single[8].dim() == 0
+    assert single[0].shape == (8, 3, 3) and torch.equal(flat_bits(single[2]), flat_bits(X[1])) and single[8].dim() == 0
 
 
 def test_bundle_adjuster_returns_a_refused_window_as_it_came():
@@ -309,15 +306,15 @@ def test_bundle_adjuster_returns_a_refused_window_as_it_came():
     X1[1, bad] = torch.tensor([0.1, 0.1, -2.0])          # ... now behind the cameras
     R, t, X, vis_out, point_ok, cost0, cost, info, ok = out = m(R0, t0, X1, kp, vis)
     assert ok.tolist() == [True, False, True]
-    assert torch.equal(bits(R[1]), bits(R0[1])) and torch.equal(bits(t[1]), bits(t0[1])) and torch.equal(bits(X[1]), bits(X1[1]))
+    assert torch.equal(flat_bits(R[1]), flat_bits(R0[1])) and torch.equal(flat_bits(t[1]), flat_bits(t0[1])) and torch.equal(flat_bits(X[1]), flat_bits(X1[1]))
     assert torch.equal(vis_out[1], vis[1]) and not point_ok[1].any() and not info[1].any()
     assert torch.isinf(cost0[1]) and torch.isinf(cost[1])
     for i in (0, 2):
-        assert all(torch.equal(bits(a[i]), bits(b[i])) for a, b in zip(out, base)), i
+        assert all(torch.equal(flat_bits(a[i]), flat_bits(b[i])) for a, b in zip(out, base)), i
         assert (vis_out[i] != vis[i]).any()              # the neighbours did go through the round
     # a window whose cleared observations leave nothing active keeps its first pass whole, mask included
     tight = BundleAdjuster(torch.from_numpy(K), iterations=ITERATIONS, huber_px=2.0, num_fixed=1, outlier_rounds=1, outlier_px=1e-4).to(DEV)
     first = ops.ba_refine(R0, t0, X0, ops.normalise_keypoints(kp, tight.K_inv), vis, 1, ITERATIONS, 2.0 / FOCAL)
     R, t, X, vis_out, point_ok, cost0, cost, info, ok = tight(R0, t0, X0, kp, vis)
-    assert ok.all() and torch.equal(vis_out, vis) and torch.equal(bits(X), bits(first[2])) and torch.equal(bits(R), bits(first[0]))
-    assert torch.equal(bits(cost), bits(first[5] * FOCAL ** 2)) and torch.equal(bits(info), bits(first[7])) and torch.equal(point_ok, first[3])
+    assert ok.all() and torch.equal(vis_out, vis) and torch.equal(flat_bits(X), flat_bits(first[2])) and torch.equal(flat_bits(R), flat_bits(first[0]))
+    assert torch.equal(flat_bits(cost), flat_bits(first[5] * FOCAL ** 2)) and torch.equal(flat_bits(info), flat_bits(first[7])) and torch.equal(point_ok, first[3])

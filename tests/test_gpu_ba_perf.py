@@ -4,15 +4,14 @@ the landmark blocks) followed by torch.linalg.solve of the reduced system, which
 That the formulation computes mi_ba_linearise's S and b is shown on a small ragged batch and on the timed tensors themselves.  The whole mi_ba_refine (10 iterations) on
 the same batch is timed and printed.  Measured on an MI355X: see DESIGN.md, "K25"."""
 import numpy as np
-import pytest
 import torch
 
 import test_gpu_ba as G
+from gpu_common import DEV, GPU, time_ms
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.synth import synth_ba_window
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU
 WINDOWS, FRAMES, LANDMARKS, ITERATIONS, NUM_FIXED = 256, 8, 512, 10, 1
 HUBER = 2.0 / G.FOCAL
 
@@ -60,21 +59,6 @@ def torch_linearise(R, t, X, obs, vis, nf, huber):
     return S, b, torch.linalg.solve(S, -b)
 
 
-def _time_ms(fn, iters=10, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        times.append(s.elapsed_time(e))
-    return float(np.median(times))
-
-
 def test_torch_formulation_computes_the_same_system():
     """the yardstick's S and b are mi_ba_linearise's within the linearise tolerance of tests/test_gpu_ba.py (float32 both,
     another summation order and another 3x3 inverse)"""
@@ -94,10 +78,10 @@ def test_torch_formulation_computes_the_same_system():
 
 def test_hip_linearise_beats_torch_on_gpu_for_256_windows():
     R, t, X, obs, vis = workload()
-    hip = _time_ms(lambda: ops.ba_linearise(R, t, X, obs, vis, NUM_FIXED, HUBER))
-    ref = _time_ms(lambda: torch_linearise(R, t, X, obs, vis, NUM_FIXED, HUBER))
-    cost = _time_ms(lambda: ops.ba_cost(R, t, X, obs, vis, HUBER))
-    refine = _time_ms(lambda: ops.ba_refine(R, t, X, obs, vis, NUM_FIXED, ITERATIONS, HUBER))
+    hip = time_ms(lambda: ops.ba_linearise(R, t, X, obs, vis, NUM_FIXED, HUBER))
+    ref = time_ms(lambda: torch_linearise(R, t, X, obs, vis, NUM_FIXED, HUBER))
+    cost = time_ms(lambda: ops.ba_cost(R, t, X, obs, vis, HUBER))
+    refine = time_ms(lambda: ops.ba_refine(R, t, X, obs, vis, NUM_FIXED, ITERATIONS, HUBER))
     out = ops.ba_refine(R, t, X, obs, vis, NUM_FIXED, ITERATIONS, HUBER)
     print(f"{WINDOWS} windows x {FRAMES} frames x {LANDMARKS} landmarks: HIP mi_ba_linearise {hip:.3f} ms, torch-on-GPU einsum + "
           f"linalg linearisation, Schur complement and solve {ref:.3f} ms ({ref / hip:.1f}x); mi_ba_cost {cost:.3f} ms; mi_ba_refine, "

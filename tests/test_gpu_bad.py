@@ -15,7 +15,7 @@ import pytest
 import torch
 
 import bad_oracle as B
-from gpu_common import DEV, mods  # noqa: F401  (mods: the module fixture)
+from gpu_common import DEV, mods, twice  # noqa: F401  (mods: the module fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -69,15 +69,6 @@ def _dev(a):
     return torch.from_numpy(np.array(a)).to(DEV)              # a copy: the cases' arrays are read-only
 
 
-def _twice(what, run):
-    first, second = run(), run()
-    for x, y in zip(first, second):
-        if x is not None:
-            same = np.array_equal(x.view(np.uint8), y.view(np.uint8))
-            assert same, f"{what}: the call does not repeat bit for bit"
-    return first
-
-
 _plans = {}
 
 
@@ -120,7 +111,7 @@ def _plain(N, case, mode, normalize, want_desc, want_bits, plan=False, u8=False,
         else:
             N.call("mi_sparse_bad_u8" if u8 else "mi_sparse_bad", parts[0].data_ptr(), b, h, w, kp.data_ptr(), k, *tail)
         return (desc.read(what) if desc else None, bits.read(what) if bits else None, status.read(what) if status else None)
-    desc, bits, status = _twice(what, run)
+    desc, bits, status = twice(what, run)
     if desc is not None:
         desc = desc.reshape(b, k, pairs)
     if bits is not None:
@@ -156,7 +147,7 @@ def _oriented(N, case, mode, normalize, want_desc, want_bits, status=True, misal
         if st:
             assert np.isin(st.read(what), (0, 1)).all(), f"{what}: a status byte is neither 0 nor 1"
         return out
-    desc, bits = _twice(what, run)
+    desc, bits = twice(what, run)
     if desc is not None:
         desc = desc.reshape(b, k, pairs)
     if bits is not None:

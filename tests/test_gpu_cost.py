@@ -14,7 +14,7 @@ import pytest
 import torch
 
 import cost_oracle as C
-from gpu_common import DEV, gpu, mods  # noqa: F401  (mods: the module fixture)
+from gpu_common import DEV, gpu, mods, twice, up  # noqa: F401  (mods: the module fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,10 +25,6 @@ MI_E_NULL, MI_E_SHAPE, MI_E_PARAM, MI_E_ALIGN = -1, -2, -3, -5
 def _report(group, what, ratio):
     if os.environ.get("MI_REPORT"):
         print(f"[cost {group}] {what}: worst error / bound {ratio:.3g}")
-
-
-def _up(x, k):
-    return (x + k - 1) // k * k
 
 
 # ------------------------------------------------------------------ guarded outputs
@@ -57,14 +53,6 @@ class _Out:
         return body.cpu().numpy()
 
 
-def _twice(what, run):
-    """run() -> tuple of numpy arrays from fresh sentinel-filled outputs; twice, equal bits."""
-    first, second = run(), run()
-    for x, y in zip(first, second):
-        assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), f"{what}: the call does not repeat bit for bit"
-    return first
-
-
 def _input(a, offset_elems=0):
     """A GPU copy of `a` (float32 or uint32) whose base sits `offset_elems` elements past an allocation's start:
     (keep-alive tensor, device pointer)."""
@@ -85,7 +73,7 @@ def _f32_vs_fp64(N, group, n, m, d, distance, kind, offset=0):
     batch = _batch_for(n, m)
     a, b = C.float_inputs(kind, batch, n, m, d, distance)
     (keep_a, pa), (keep_b, pb) = _input(a, offset), _input(b)
-    pitch = _up(m + 1, 4)
+    pitch = up(m + 1, 4)
     z1, bound1 = C.float_reference(a, b, distance, 1.0)
     for epsilon in EPSILONS:
         what = f"{C.DIST_NAME[distance]} {kind} {(n, m, d)} eps {epsilon}" + (" offset base" if offset else "")
@@ -94,7 +82,7 @@ def _f32_vs_fp64(N, group, n, m, d, distance, kind, offset=0):
             out = _Out(batch * n, pitch, torch.float32)
             N.call("mi_cost_logscores_f32", pa, pb, batch, n, m, d, distance, float(epsilon), out.ptr, pitch, N.stream_ptr())
             return (out.read(what, cols=m),)
-        (z,) = _twice(what, run)
+        (z,) = twice(what, run)
         z = z.reshape(batch, n, pitch)[:, :, :m]
         e = C.eps32(epsilon)
         ratio = C.worst_ratio(z, z1 / e, bound1 / e)
@@ -149,7 +137,7 @@ def _bits_vs_fp64(N, num_bits, n, m, offset=0, tag=""):
     (keep_a, pa), (keep_b, pb) = _input(b1, offset), _input(b2)
     want = C.bit_dots(b1, b2)
     assert want.max() <= num_bits and (want[0, 0, 0] == num_bits)          # all-ones against all-ones: the largest dot
-    zp, dp = _up(m + 1, 4), _up(m, 8)
+    zp, dp = up(m + 1, 4), up(m, 8)
     for normalized in (True, False):
         what = f"{num_bits} bits {(n, m)} normalized {int(normalized)}{tag}"
 
@@ -159,7 +147,7 @@ def _bits_vs_fp64(N, num_bits, n, m, offset=0, tag=""):
             N.call("mi_cost_dots_bits", pa, pb, batch, n, m, num_bits, int(normalized), dots.ptr, dp, ri.ptr, ci.ptr,
                    N.stream_ptr())
             return dots.read(what + " dots"), ri.read(what + " row_info"), ci.read(what + " col_info")
-        dots, ri, ci = _twice(what + " dots", run_dots)
+        dots, ri, ci = twice(what + " dots", run_dots)
         got = dots.view(np.uint16).reshape(batch, n, dp)[:, :, :m].astype(np.int64)
         bad = np.argwhere(got != want)
         assert bad.size == 0, f"{what}: {len(bad)} dot products differ, first at {bad[0].tolist()}: {got[tuple(bad[0])]} vs {want[tuple(bad[0])]}"
@@ -177,7 +165,7 @@ def _bits_vs_fp64(N, num_bits, n, m, offset=0, tag=""):
                 N.call("mi_cost_logscores_bits", pa, pb, batch, n, m, num_bits, int(normalized), float(epsilon), out.ptr, zp,
                        N.stream_ptr())
                 return (out.read(what + " z", cols=m),)
-            (z,) = _twice(what + " z", run_z)
+            (z,) = twice(what + " z", run_z)
             z = z.reshape(batch, n, zp)[:, :, :m]
             e = C.eps32(epsilon)
             ratio = C.worst_ratio(z, z1 / e, bound1 / e)

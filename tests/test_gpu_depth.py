@@ -10,16 +10,12 @@ import torch
 from test_depth_host import (F32, align_cases, align_oracle, camera_args, check_align_against_reference, check_normals,
                              check_points, fixture_depth, golden, points_cases, points_oracle,
                              tables_oracle)
+from gpu_common import DEV, GPU, gpu
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.synth import synth_depth_frame
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
-
-
-def _gpu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+pytestmark = GPU
 
 
 def _frames(h, w, count, seed, counts=False):
@@ -50,8 +46,8 @@ def test_points_are_the_oracle_s_bits_and_normals_are_within_the_bound(h, w, cou
     batch = 5 if h * w < 100_000 else 3
     frames = _frames(h, w, batch, 50 + h + w, counts)
     want = points_oracle(frames, u, v, zs)
-    tu, tv = _gpu(u), _gpu(v)
-    d = _gpu(frames)
+    tu, tv = gpu(u), gpu(v)
+    d = gpu(frames)
     pts = ops.depth_to_points(d, tu, tv, float(zs))
     pts2, nrm = ops.depth_to_points(d, tu, tv, float(zs), normals=True)
     assert pts.shape == (batch, h, w, 3) and nrm.shape == (batch, h, w, 3) and nrm.dtype == torch.float32
@@ -68,7 +64,7 @@ def test_points_are_the_oracle_s_bits_and_normals_are_within_the_bound(h, w, cou
 
 def test_point_output_shapes():
     u, v, zs = tables_oracle(1.0, 8, 6, 4.0, 3.0, 7.0, 7.5)
-    tu, tv = _gpu(u), _gpu(v)
+    tu, tv = gpu(u), gpu(v)
     for shape, out in (((6, 8), (6, 8, 3)), ((6, 8, 1), (6, 8, 3)), ((3, 6, 8), (3, 6, 8, 3)), ((3, 6, 8, 1), (3, 6, 8, 3))):
         assert ops.depth_to_points(torch.ones(shape, device=DEV), tu, tv, float(zs)).shape == out
         al = ops.depth_align(torch.ones(shape, device=DEV), tu, tv, float(zs), 4.0, 3.0, 7.0, 7.5,
@@ -89,8 +85,8 @@ def _rot(rx, ry, rz):
 
 
 def _align_gpu(frames, u, v, zs, rgb, rot, tr):
-    return ops.depth_align(_gpu(frames), _gpu(u), _gpu(v), float(zs), *[float(x) for x in rgb], _gpu(np.asarray(rot, F32)),
-                           _gpu(np.asarray(tr, F32)))
+    return ops.depth_align(gpu(frames), gpu(u), gpu(v), float(zs), *[float(x) for x in rgb], gpu(np.asarray(rot, F32)),
+                           gpu(np.asarray(tr, F32)))
 
 
 def _check_align_everywhere(frames, u, v, zs, rgb, rot, tr, what):
@@ -165,7 +161,7 @@ def test_dirty_output_buffers_do_not_show():
     args = _camera(1.0, h, w)
     u, v, zs = tables_oracle(*args)
     rgb, rot, tr = (27.0, 18.0, 38.0, 38.5), _rot(0.004, -0.006, 0.003), np.float32([0.025, 0.0, 0.0])
-    d, tu, tv, trot, ttr = _gpu(frames), _gpu(u), _gpu(v), _gpu(rot), _gpu(tr)
+    d, tu, tv, trot, ttr = gpu(frames), gpu(u), gpu(v), gpu(rot), gpu(tr)
     want_p, want_n = ops.depth_to_points(d, tu, tv, float(zs), normals=True)
     want_a = ops.depth_align(d, tu, tv, float(zs), *rgb, trot, ttr)
     assert np.array_equal(want_a[1].cpu().numpy(), align_oracle(frames[1], u, v, zs, rgb, rot, tr))
@@ -194,7 +190,7 @@ def test_modules_reproduce_the_reference_fixture():
         d = fixture_depth(g, name)
         h, w = d.shape
         args = camera_args(g, name)
-        x = _gpu(d).reshape(h, w, 1)                                   # what the reference's forward takes
+        x = gpu(d).reshape(h, w, 1)                                   # what the reference's forward takes
         pts = DepthToPointCloud(*args).to(DEV)(x)
         pts2, nrm = DepthToPointCloudWithNormal(*args).to(DEV)(x)
         assert pts.shape == (h, w, 3) and nrm.shape == (h, w, 3)
@@ -202,7 +198,7 @@ def test_modules_reproduce_the_reference_fixture():
         check_points(pts2.cpu().numpy(), g[f"{name}__points"], name)
         check_normals(nrm.cpu().numpy(), g[f"{name}__points"], name)
         if int(g[f"{name}__millimetres"]):                              # the same frame as uint16 sensor counts
-            p16, n16 = DepthToPointCloudWithNormal(*args).to(DEV)(_gpu(d.astype(np.uint16)))
+            p16, n16 = DepthToPointCloudWithNormal(*args).to(DEV)(gpu(d.astype(np.uint16)))
             assert torch.equal(p16, pts2) and torch.equal(n16, nrm)
     for name in align_cases(g):
         d = fixture_depth(g, name)
@@ -210,13 +206,13 @@ def test_modules_reproduce_the_reference_fixture():
         args = camera_args(g, name)
         rgb, rot, tr = g[f"{name}__rgb"], g[f"{name}__rotation"], g[f"{name}__translation"]
         model = DepthAlignment(*args, *[float(x) for x in rgb], torch.from_numpy(rot), torch.from_numpy(tr)).to(DEV)
-        out = model(_gpu(d).reshape(h, w, 1))
+        out = model(gpu(d).reshape(h, w, 1))
         assert out.shape == (h, w, 1)
         u, v, zs = tables_oracle(*args)
         _, clean = align_oracle(d, u, v, zs, rgb, rot, tr, with_clean=True)
         check_align_against_reference(out.reshape(h, w).cpu().numpy(), g[f"{name}__aligned"], clean, name)
         if int(g[f"{name}__millimetres"]):
-            assert torch.equal(model(_gpu(d.astype(np.uint16))), out.reshape(h, w))
+            assert torch.equal(model(gpu(d.astype(np.uint16))), out.reshape(h, w))
 
 
 def test_depth_to_voxels_composition_captured_in_one_graph():
@@ -237,8 +233,8 @@ def test_depth_to_voxels_composition_captured_in_one_graph():
         vox, mask, counts, _ = ops.voxel_downsample_batch(pts.reshape(-1, 3), leaf, offsets=offs)
         return pts, nrm, al, vox, mask, counts
 
-    first = _gpu(np.stack([synth_depth_frame(130 + i, h, w, hole_share=0.02 * i) for i in range(batch)]))
-    second = _gpu(np.stack([synth_depth_frame(140 + i, h, w, hole_share=0.03 * i) for i in range(batch)]))
+    first = gpu(np.stack([synth_depth_frame(130 + i, h, w, hole_share=0.02 * i) for i in range(batch)]))
+    second = gpu(np.stack([synth_depth_frame(140 + i, h, w, hole_share=0.03 * i) for i in range(batch)]))
     static = first.clone()
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())

@@ -4,16 +4,15 @@ multiply (points); F.conv2d + normalise on top of it (points + normals); back-pr
 index_put_ + minimum (the reference's form) or one scatter_reduce_('amin') over the four splats (alignment: both are
 timed, the faster one is the yardstick and the test prints which)."""
 import numpy as np
-import pytest
 import torch
 import torch.nn.functional as F
 
 from test_depth_host import align_oracle, tables_oracle
+from gpu_common import DEV, GPU_PERF, time_ms
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.synth import synth_depth_frame
 
-pytestmark = [pytest.mark.gpu_perf, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU_PERF
 H, W, FRAMES = 480, 640, 16
 DEPTH_CAM = (1.0, W, H, 319.5, 239.5, 525.0, 525.0)
 # a colour camera with the wider field of view: the torch formulation indexes out of range otherwise, as the reference does
@@ -73,21 +72,6 @@ def torch_align_scatter(depth, uv, rot, trans, rgb):
     return torch.where(out == 10000.0, 0.0, out).reshape(h, w)
 
 
-def _time_ms(fn, iters=10, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        times.append(s.elapsed_time(e))
-    return float(np.median(times))
-
-
 def workload(frames=FRAMES, seed=500):
     """(depth (frames, H, W) on the GPU, tables, torch-side constants); checks on the host that no source indexes out
     of range in the torch formulation (a device-side fault otherwise)."""
@@ -138,8 +122,8 @@ def test_hip_depth_operations_beat_torch_on_gpu_for_sixteen_frames():
     t = workload()
     failed = []
     for name, (hip_fn, torch_fns) in operations(t).items():
-        hip = _time_ms(hip_fn)
-        refs = {k: _time_ms(fn) for k, fn in torch_fns.items()}
+        hip = time_ms(hip_fn)
+        refs = {k: time_ms(fn) for k, fn in torch_fns.items()}
         best = min(refs, key=refs.get)
         print(f"{name}: 16 frames HIP {hip:.3f} ms; torch-on-GPU " + ", ".join(f"{k} {v:.3f} ms" for k, v in refs.items())
               + f"; yardstick: {best} ({refs[best] / hip:.1f}x)")

@@ -40,13 +40,13 @@ import torch
 
 import icp_oracle as IO
 import photo_oracle as PO
+from gpu_common import DEV, GPU, bits
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.pytorch_model.geometry import DirectRgbdRefiner
 from onnx_image_processing_amd.synth import rgbd_camera
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU
 F32, F64 = np.float32, np.float64
 ANGLE = float(np.deg2rad(IO.ANGLE_DEG))
 SEEDS = (0, 1, 2)
@@ -63,10 +63,6 @@ PLANE_TOL = {(48, 64): (2 * 3.017e-6, 4 * 1.071e-7), (120, 160): (2 * 4.428e-6, 
 # (truth deg, truth m, oracle deg, oracle m, information relative, rmse relative, rmse_photo relative)
 ROOM_TOL = (4.429e-2 + 2 * 1.851e-6, 1.199e-3 + 4 * 1.153e-7, 2 * 1.851e-6, 4 * 1.153e-7, 4 * 2.32e-7, 4 * 3.80e-6, 4 * 1.96e-6)
 ARGS = (IO.SCHEDULE, IO.DIST, ANGLE, PO.PHOTO_WEIGHT, PO.INTENSITY_THRESHOLD, IO.MIN_CORR)
-
-
-def bits(x):
-    return x.contiguous().view(torch.uint8) if isinstance(x, torch.Tensor) else np.ascontiguousarray(x).view(np.uint8)
 
 
 def same(a, b):

@@ -11,17 +11,16 @@ beside `ops.icp_refine` on the same maps in the same process 1.006 ms: 2.29x, fo
 with all four maps 2.464 ms, 6.5 k pairs/s, beside DenseRgbdRefiner 1.108 ms; the kernel has the float64 formulation's counts
 and is within 1.5e-7 (A), 1.7e-6 (b) and 2.7e-6 (sum r^2) of its sums."""
 import numpy as np
-import pytest
 import torch
 
 import icp_oracle as IO
 import photo_oracle as PO
+from gpu_common import DEV, GPU_PERF, time_ms
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.pytorch_model.geometry import DenseRgbdRefiner, DirectRgbdRefiner
 from onnx_image_processing_amd.synth import rgbd_camera, synth_depth_room
 
-pytestmark = [pytest.mark.gpu_perf, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU_PERF
 HEIGHT, WIDTH, PAIRS = 480, 640, 16
 ANGLE = float(np.deg2rad(IO.ANGLE_DEG))
 SUMS_A_TOL, SUMS_B_TOL, SUMS_RR_TOL, COUNT_ALLOWANCE = 6.94e-6, 4.28e-5, 6.53e-5, 0       # tests/test_gpu_direct_rgbd.py, SUMS_TOL
@@ -81,21 +80,6 @@ def torch_photo_linearise(v1, g1, v2, g2, r, t, cam, dist, thr, dtype=torch.floa
                       keep.sum(1, keepdim=True).to(dtype)], dim=1)
 
 
-def _time_ms(fn, iters=10, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        times.append(s.elapsed_time(e))
-    return float(np.median(times))
-
-
 def test_torch_formulation_computes_the_same_thing():
     """Run in float64 on the kernels' own maps the stock formulation is an accurate statement of the operation; the kernel
     agrees with it as the GPU suite asks of the kernel against the oracle: equal counts and the sums within that suite's
@@ -127,16 +111,16 @@ def test_hip_photo_linearise_beats_torch_on_gpu_for_16_pairs():
     wl = workload(PAIRS, HEIGHT, WIDTH)
     m1, m2 = wl["m1"], wl["m2"]
     args = (m1[0], m1[2], m2[0], m2[2], wl["r"], wl["t"], wl["cam"])
-    hip = _time_ms(lambda: ops.photo_linearise(*args, 1, IO.DIST, PO.INTENSITY_THRESHOLD))
-    ref = _time_ms(lambda: torch_photo_linearise(*args, IO.DIST, PO.INTENSITY_THRESHOLD))
+    hip = time_ms(lambda: ops.photo_linearise(*args, 1, IO.DIST, PO.INTENSITY_THRESHOLD))
+    ref = time_ms(lambda: torch_photo_linearise(*args, IO.DIST, PO.INTENSITY_THRESHOLD))
     eye, zero = torch.eye(3, device=DEV).repeat(PAIRS, 1, 1), torch.zeros(PAIRS, 3, device=DEV)
-    icp = _time_ms(lambda: ops.icp_refine(m1[:2], m2[:2], eye, zero, wl["cam"], IO.SCHEDULE, IO.DIST, ANGLE, IO.MIN_CORR))
+    icp = time_ms(lambda: ops.icp_refine(m1[:2], m2[:2], eye, zero, wl["cam"], IO.SCHEDULE, IO.DIST, ANGLE, IO.MIN_CORR))
     joint_args = (m1, m2, eye, zero, wl["cam"], IO.SCHEDULE, IO.DIST, ANGLE, PO.PHOTO_WEIGHT, PO.INTENSITY_THRESHOLD, IO.MIN_CORR)
-    joint = _time_ms(lambda: ops.rgbd_refine(*joint_args))
+    joint = time_ms(lambda: ops.rgbd_refine(*joint_args))
     K = torch.from_numpy(wl["K"])
     direct, dense = DirectRgbdRefiner(K).to(DEV), DenseRgbdRefiner(K).to(DEV)
-    whole = _time_ms(lambda: direct(wl["d1"], wl["g1"], wl["d2"], wl["g2"]))
-    whole_icp = _time_ms(lambda: dense(wl["d1"], wl["d2"]))
+    whole = time_ms(lambda: direct(wl["d1"], wl["g1"], wl["d2"], wl["g2"]))
+    whole_icp = time_ms(lambda: dense(wl["d1"], wl["d2"]))
     assert bool(ops.rgbd_refine(*joint_args)[8].all())
     mbytes = PAIRS * HEIGHT * WIDTH * BYTES_PER_SOURCE_PIXEL / 1e6
     print(f"{PAIRS} pairs of {HEIGHT} x {WIDTH}: HIP stride-1 photometric linearisation {hip:.3f} ms ({hip / PAIRS * 1e3:.1f} us per "

@@ -28,7 +28,7 @@ import pytest
 import torch
 
 import essential_oracle as EO
-from gpu_common import DEV, mods  # noqa: F401  (mods: the module fixture)
+from gpu_common import DEV, gpu, mods, twice  # noqa: F401  (mods: the module fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -72,10 +72,6 @@ class _Work:
         return self.full[self.GUARD: self.GUARD + self.nbytes].cpu().numpy()
 
 
-def gpu(a):
-    return torch.from_numpy(np.array(a, copy=True)).to(DEV)          # (the oracle's arrays are read-only: upload a copy)
-
-
 def _ptr(t):
     return None if t is None else t.data_ptr()
 
@@ -103,11 +99,7 @@ def _call(src, dims, pts, masks, top_k, n_iter, banded):
 
 
 def _twice(*args):
-    first, second = _call(*args), _call(*args)
-    assert np.array_equal(first[0].view(np.uint32), second[0].view(np.uint32)), "E does not repeat bit for bit"
-    if first[1] is not None:
-        assert np.array_equal(first[1], second[1]), "the workspace does not repeat byte for byte"
-    return first
+    return twice("E and the workspace", lambda: _call(*args))
 
 
 def _check_e(e, refs, form):

@@ -37,12 +37,12 @@ import torch
 
 import homography_oracle as HO
 import pose_oracle as PO
+from gpu_common import DEV, GPU, bits, gpu
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.pytorch_model.geometry import RelativePoseEstimator, TwoViewPoseEstimator
 from onnx_image_processing_amd.synth import synth_planar_two_view, synth_two_view, two_view_camera
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU
 K = two_view_camera()
 FOCAL = 500.0
 THR = 3.0 / FOCAL                      # HomographyEstimator's default
@@ -94,14 +94,6 @@ def parity_valid(n):
 def cost_deviation(cost, ref):
     """relative deviation of MSAC costs, against ref + COST_FLOOR: the cost of an exact fit (n = 4) is rounding noise"""
     return np.abs(np.asarray(cost, D) - np.asarray(ref, D)) / (np.asarray(ref, D) + COST_FLOOR)
-
-
-def gpu(*arrays):
-    return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for a in arrays)
-
-
-def bits(x):
-    return x.contiguous().view(torch.uint8)
 
 
 def model_of(h):

@@ -5,14 +5,13 @@ every one of them, both ways, in one batch of stock ops, forms the MSAC cost and
 mi_homography_hypotheses'.  mi_essential_ransac (K15) and mi_rigid_ransac (K17) on the same shape are timed for
 comparison.  Measured on an MI355X: see DESIGN.md, "K24"."""
 import numpy as np
-import pytest
 import torch
 
+from gpu_common import DEV, GPU_PERF, time_ms
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.synth import synth_planar_two_view, two_view_camera
 
-pytestmark = [pytest.mark.gpu_perf, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU_PERF
 K = two_view_camera()
 THR = 3.0 / 500.0
 PAIRS, N_ROWS, HYP = 256, 512, 128
@@ -41,21 +40,6 @@ def torch_score(h_h, p1, p2, thr):
     d2 = torch.where((a[..., 2] > 0) & (b[..., 2] > 0) & torch.isfinite(d2), d2, torch.full_like(d2, float("inf")))
     cost = torch.clamp(d2, max=thr * thr).sum(-1)
     return cost, torch.argmin(cost, dim=1)
-
-
-def _time_ms(fn, iters=10, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        times.append(s.elapsed_time(e))
-    return float(np.median(times))
 
 
 def hip_pose(w, rounds=3):
@@ -91,11 +75,11 @@ def test_hip_planar_pose_beats_torch_on_gpu_for_256_pairs():
     safe = torch.where(torch.isfinite(cost)[..., None, None], h_h, torch.eye(3, device=DEV).expand_as(h_h)).contiguous()
     one = torch.ones_like(p1[..., :1])
     x1, x2 = torch.cat([p1, one], -1), torch.cat([p2, one], -1)              # the same rows as 3-D points for K17
-    hip = _time_ms(lambda: hip_pose(w))
-    hip_hyp = _time_ms(lambda: ops.homography_hypotheses(p1, p2, None, HYP, THR, w["seed"]))
-    ess = _time_ms(lambda: ops.essential_ransac(p1, p2, None, HYP, 1.0 / 500.0, 3, w["seed"]))
-    rigid = _time_ms(lambda: ops.rigid_ransac(x1, x2, None, HYP, 0.05, 3, w["seed"]))
-    ref = _time_ms(lambda: torch_score(safe, p1, p2, THR))
+    hip = time_ms(lambda: hip_pose(w))
+    hip_hyp = time_ms(lambda: ops.homography_hypotheses(p1, p2, None, HYP, THR, w["seed"]))
+    ess = time_ms(lambda: ops.essential_ransac(p1, p2, None, HYP, 1.0 / 500.0, 3, w["seed"]))
+    rigid = time_ms(lambda: ops.rigid_ransac(x1, x2, None, HYP, 0.05, 3, w["seed"]))
+    ref = time_ms(lambda: torch_score(safe, p1, p2, THR))
     print(f"{PAIRS} pairs x {N_ROWS} rows x {HYP} hypotheses: HIP normalise + homography_ransac (3 rounds) + homography_pose "
           f"{hip:.3f} ms ({PAIRS / hip * 1e3:.0f} pairs/s), hypotheses alone {hip_hyp:.3f} ms; torch-on-GPU transfer error + "
           f"cost + argmin of given homographies {ref:.3f} ms ({ref / hip:.1f}x); mi_essential_ransac on the same shape "

@@ -8,16 +8,15 @@ against 2.772 ms, 25x; the default refinement (15 linearisations from identity) 
 surfel maps 1.118 ms, 14.3 k pairs/s; the kernel has the float64 formulation's counts and is within 2.8e-8 (A), 4.9e-6 (b) and
 6.9e-6 (sum r^2) of its sums."""
 import numpy as np
-import pytest
 import torch
 
 import icp_oracle as IO
+from gpu_common import DEV, GPU_PERF, time_ms
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.pytorch_model.geometry import DenseRgbdRefiner
 from onnx_image_processing_amd.synth import rgbd_camera, synth_depth_room
 
-pytestmark = [pytest.mark.gpu_perf, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU_PERF
 HEIGHT, WIDTH, PAIRS = 480, 640, 16
 ANGLE = float(np.deg2rad(IO.ANGLE_DEG))
 SUMS_A_TOL, SUMS_B_TOL, SUMS_RR_TOL, COUNT_ALLOWANCE = 4.08e-6, 1.90e-3, 1.53e-4, 0      # tests/test_gpu_icp.py
@@ -68,21 +67,6 @@ def torch_linearise(m1, m2, r, t, cam, dist, angle, dtype=torch.float32):
                       keep.sum(1, keepdim=True).to(dtype)], dim=1)
 
 
-def _time_ms(fn, iters=10, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        times.append(s.elapsed_time(e))
-    return float(np.median(times))
-
-
 def test_torch_formulation_computes_the_same_thing():
     """Run in float64 on the kernels' own maps the stock formulation is an accurate statement of the operation; the kernel
     agrees with it as the GPU suite asks of the kernel against the oracle: equal counts and the sums within that suite's
@@ -110,12 +94,12 @@ def test_torch_formulation_computes_the_same_thing():
 def test_hip_linearise_beats_torch_on_gpu_for_16_pairs():
     wl = workload(PAIRS, HEIGHT, WIDTH)
     args = (wl["m1"], wl["m2"], wl["r"], wl["t"], wl["cam"])
-    hip = _time_ms(lambda: ops.icp_linearise(*args, 1, IO.DIST, ANGLE))
-    ref = _time_ms(lambda: torch_linearise(*args, IO.DIST, ANGLE))
+    hip = time_ms(lambda: ops.icp_linearise(*args, 1, IO.DIST, ANGLE))
+    ref = time_ms(lambda: torch_linearise(*args, IO.DIST, ANGLE))
     eye, zero = torch.eye(3, device=DEV).repeat(PAIRS, 1, 1), torch.zeros(PAIRS, 3, device=DEV)
-    refine = _time_ms(lambda: ops.icp_refine(wl["m1"], wl["m2"], eye, zero, wl["cam"], IO.SCHEDULE, IO.DIST, ANGLE, IO.MIN_CORR))
+    refine = time_ms(lambda: ops.icp_refine(wl["m1"], wl["m2"], eye, zero, wl["cam"], IO.SCHEDULE, IO.DIST, ANGLE, IO.MIN_CORR))
     module = DenseRgbdRefiner(torch.from_numpy(wl["K"])).to(DEV)
-    whole = _time_ms(lambda: module(wl["d1"], wl["d2"]))
+    whole = time_ms(lambda: module(wl["d1"], wl["d2"]))
     ok = ops.icp_refine(wl["m1"], wl["m2"], eye, zero, wl["cam"], IO.SCHEDULE, IO.DIST, ANGLE, IO.MIN_CORR)[6]
     assert bool(ok.all())
     mbytes = PAIRS * HEIGHT * WIDTH * BYTES_PER_SOURCE_PIXEL / 1e6

@@ -4,15 +4,14 @@ in device memory has to do without it: (a) the frame to float32, the integer-wei
 (bilinear, align_corners=False), round and clamp; (b) the gray image in integers first, so that only one channel goes to
 float32.  Both are first checked to compute the same thing (within 1 gray level on >= 99 % of the pixels)."""
 import numpy as np
-import pytest
 import torch
 import torch.nn.functional as F
 
+from gpu_common import DEV, GPU_PERF, time_ms
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.synth import synth_colour_frame
 
-pytestmark = [pytest.mark.gpu_perf, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU_PERF
 FRAMES = 16
 WORKLOADS = {"1080x1920x3 -> 480x640": ((1080, 1920), (480, 640)), "480x640x3 -> 480x640": ((480, 640), (480, 640))}
 WEIGHTS = (3735.0, 19235.0, 9798.0)
@@ -34,21 +33,6 @@ def torch_gray_first(frames, h, w, weights):
 
 
 FORMULATIONS = {"float first": torch_float_first, "gray first": torch_gray_first}
-
-
-def _time_ms(fn, iters=10, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        times.append(s.elapsed_time(e))
-    return float(np.median(times))
 
 
 def workload(src_size, frames=FRAMES, seed=700):
@@ -77,8 +61,8 @@ def test_hip_ingest_beats_torch_on_gpu_for_sixteen_frames():
     failed = []
     for name, (src, (h, w)) in WORKLOADS.items():
         frames = workload(src)
-        hip = _time_ms(lambda: ops.ingest_frames(frames, h, w))
-        refs = {k: _time_ms(lambda: fn(frames, h, w, weights)) for k, fn in FORMULATIONS.items()}
+        hip = time_ms(lambda: ops.ingest_frames(frames, h, w))
+        refs = {k: time_ms(lambda: fn(frames, h, w, weights)) for k, fn in FORMULATIONS.items()}
         best = min(refs, key=refs.get)
         print(f"{name}: 16 frames HIP {hip:.4f} ms ({traffic_bytes(frames, h, w) / hip / 1e6:.0f} GB/s of source + destination); "
               + "torch-on-GPU " + ", ".join(f"{k} {v:.3f} ms" for k, v in refs.items())

@@ -1,12 +1,10 @@
 """Rate comparisons on a real MI355X: `-m gpu_perf`, on a box nothing else is using.  Not part of `-m gpu` -- a noisy
 neighbour must not fail the correctness suite."""
-import pytest
-import torch
-
+from gpu_common import GPU_PERF
 from test_gpu_runtime import _run_bench
 
 # selected by `-m gpu_perf`; a `-m "not gpu"` run on a machine without a GPU (the CPU suite) skips it
-pytestmark = [pytest.mark.gpu_perf, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
+pytestmark = GPU_PERF
 
 
 def test_forced_rccl_group_costs_less_than_seven_percent():

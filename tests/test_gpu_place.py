@@ -12,9 +12,9 @@ import pytest
 import torch
 
 import place_oracle as PO
+from gpu_common import DEV, GPU, gpu
 from onnx_image_processing_amd.synth import synth_batch, synth_place_descriptors
 
-DEV = "cuda:0"
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 F32 = np.float32
 
@@ -174,12 +174,7 @@ def scene_camera():
 
 
 # ---- the device ------------------------------------------------------------------------------------------------------------------
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-
-
-def gpu(*arrays):
-    out = [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for a in arrays]
-    return out[0] if len(out) == 1 else out
+pytestmark = GPU
 
 
 def host(*tensors):

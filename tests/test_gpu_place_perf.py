@@ -7,11 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_common import DEV, GPU_PERF, time_ms
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.synth import synth_place_descriptors
 
-pytestmark = [pytest.mark.gpu_perf, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU_PERF
 KEYFRAMES, DESCRIPTORS, BITS, MAX_DISTANCE, RATIO = 1024, 512, 256, 64, 0.8
 
 
@@ -48,21 +48,6 @@ def torch_votes(db_u, q_u, max_distance, ratio):
     return torch.stack(out).to(torch.int32)
 
 
-def _time_ms(fn, iters=10, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        times.append(s.elapsed_time(e))
-    return float(np.median(times))
-
-
 def test_torch_formulation_returns_the_kernels_votes():
     db, q = workload(2, 40, 96)
     want = ops.place_votes(db, None, q, None, MAX_DISTANCE, RATIO)
@@ -73,12 +58,12 @@ def test_torch_formulation_returns_the_kernels_votes():
 def test_hip_votes_beat_torch_on_gpu(queries):
     db, q = workload(queries)
     db_u, q_u = unpack(db), unpack(q)
-    hip = _time_ms(lambda: ops.place_votes(db, None, q, None, MAX_DISTANCE, RATIO))
-    ref = _time_ms(lambda: torch_votes(db_u, q_u, MAX_DISTANCE, RATIO))
+    hip = time_ms(lambda: ops.place_votes(db, None, q, None, MAX_DISTANCE, RATIO))
+    ref = time_ms(lambda: torch_votes(db_u, q_u, MAX_DISTANCE, RATIO))
     votes = ops.place_votes(db, None, q, None, MAX_DISTANCE, RATIO)
-    both = _time_ms(lambda: ops.place_select(ops.place_votes(db, None, q, None, MAX_DISTANCE, RATIO), 4, 20))
-    select = _time_ms(lambda: ops.place_select(votes, 4, 20))
-    matches = _time_ms(lambda: ops.place_votes(db, None, q, None, MAX_DISTANCE, RATIO, want_matches=True))
+    both = time_ms(lambda: ops.place_select(ops.place_votes(db, None, q, None, MAX_DISTANCE, RATIO), 4, 20))
+    select = time_ms(lambda: ops.place_select(votes, 4, 20))
+    matches = time_ms(lambda: ops.place_votes(db, None, q, None, MAX_DISTANCE, RATIO, want_matches=True))
     pairs = queries * KEYFRAMES * DESCRIPTORS * DESCRIPTORS
     print(f"{queries} x {DESCRIPTORS} descriptors against {KEYFRAMES} keyframes x {DESCRIPTORS}, {BITS} bits: HIP mi_place_votes {hip:.3f} ms "
           f"({queries * KEYFRAMES / hip * 1e3:.0f} keyframes/s, {pairs / hip / 1e9:.2f} T descriptor pairs/s), torch-on-GPU matmul + topk "
@@ -87,7 +72,7 @@ def test_hip_votes_beat_torch_on_gpu(queries):
     assert torch.equal(torch_votes(db_u, q_u, MAX_DISTANCE, RATIO), votes)       # the two timed calls compute the same votes
     # the same shape at 512 bits: twice the MFMA work under the same epilogue, which tells the two apart
     db2, q2 = torch.cat([db, db.flip(2)], 2).contiguous(), torch.cat([q, q.flip(2)], 2).contiguous()
-    wide = _time_ms(lambda: ops.place_votes(db2, None, q2, None, 2 * MAX_DISTANCE, RATIO))
+    wide = time_ms(lambda: ops.place_votes(db2, None, q2, None, 2 * MAX_DISTANCE, RATIO))
     print(f"512-bit descriptors, same shape: {wide:.3f} ms ({wide / hip:.2f}x the 256-bit time)")
     assert torch.equal(ops.place_votes(db2, None, q2, None, 2 * MAX_DISTANCE, RATIO), votes)   # every distance doubles: the same votes
     assert hip < ref

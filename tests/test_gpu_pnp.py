@@ -29,13 +29,13 @@ import torch
 import pnp_oracle as QO
 import pose_oracle as PO
 import rigid_oracle as RO
+from gpu_common import DEV, GPU, bits, gpu, k_inv, same_bits
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.pytorch_model.geometry import AbsolutePoseEstimator, RgbdPoseEstimator
 from onnx_image_processing_amd.synth import rgbd_camera, synth_rgbd_pair
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU
 K = rgbd_camera()
 FOCAL = 500.0
 THR = QO.THR_PX / FOCAL
@@ -59,18 +59,6 @@ def raw_scenes(seeds, n, outliers, noise_px):
     return tuple(np.stack([x[j] for x in s]) for j in range(4)) + ([x[4] for x in s], [x[5] for x in s], np.stack([x[6] for x in s]))
 
 
-def gpu(*arrays):
-    return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for a in arrays)
-
-
-def k_inv():
-    return torch.from_numpy(np.linalg.inv(K)).float().to(DEV)
-
-
-def bits(x):
-    return x.contiguous().view(torch.uint8)
-
-
 def perturbed(R, t):
     w = np.deg2rad(2.0) * np.array([1.0, 2.0, 3.0]) / np.sqrt(14.0)
     return (QO._exp(w) @ R).astype(np.float32), (t + [0.03, -0.02, 0.05]).astype(np.float32)
@@ -81,7 +69,7 @@ def perturbed(R, t):
 def test_normalised_points_are_the_oracles_bits():
     """what the tests feed the oracle is what mi_normalise_keypoints gives the kernels"""
     k1, k2, d1, d2, _, _, _ = raw_scenes((100, 101, 102), 97, 0.25, 0.5)
-    got = ops.normalise_keypoints(gpu(k2)[0], k_inv()).cpu().numpy()
+    got = ops.normalise_keypoints(gpu(k2), k_inv(K)).cpu().numpy()
     assert np.array_equal(got.view(np.uint32), QO.normalise_f32(k2, np.linalg.inv(K).astype(np.float32)).view(np.uint32))
 
 
@@ -203,7 +191,7 @@ def test_refit_matches_the_oracle(n, noise):
     y = x.clone()
     y[1, :8] = torch.from_numpy((np.outer(np.ones(8), [0.3, -0.2, 4.0])).astype(np.float32)).to(DEV)   # one point eight times
     y[2, :8] = -x[2, :8]                                                       # behind the camera under the start
-    r, t, info, ok = ops.pnp_refit(y, u, gpu(few)[0], gr0, gt0)
+    r, t, info, ok = ops.pnp_refit(y, u, gpu(few), gr0, gt0)
     assert not ok.any() and torch.equal(bits(r), bits(gr0)) and torch.equal(bits(t), bits(gt0)) and not info.any()
 
 
@@ -284,7 +272,7 @@ def test_degenerate_pairs_and_small_shapes(batch):
         assert torch.isinf(cost).all() and (cost > 0).all() and not count.any() and not rt_h.any()
         out = ops.pnp_ransac(x, u, None, 65, thr, 3, 0)
         assert all(_failed(*out, b) for b in range(batch)) and not out[3].any()
-        r, t, info, ok = ops.pnp_refit(x, u, gpu(np.ones((batch, n), bool))[0], *gpu(np.stack([np.eye(3, dtype=np.float32)] * batch),
+        r, t, info, ok = ops.pnp_refit(x, u, gpu(np.ones((batch, n), bool)), *gpu(np.stack([np.eye(3, dtype=np.float32)] * batch),
                                                                                       np.zeros((batch, 3), np.float32)))
         assert not ok.any() and torch.equal(r, torch.eye(3, device=DEV).expand(batch, 3, 3)) and not t.any() and not info.any()
     # n = 4: every sample is the four rows in some order
@@ -301,9 +289,9 @@ def test_degenerate_pairs_and_small_shapes(batch):
     for keep in (3, 0):
         valid = np.zeros((batch, 64), bool)
         valid[:, :keep] = True
-        rt_h, cost, count = ops.pnp_hypotheses(x, u, gpu(valid)[0], 64, thr, 3)
+        rt_h, cost, count = ops.pnp_hypotheses(x, u, gpu(valid), 64, thr, 3)
         assert torch.isinf(cost).all() and not count.any() and not rt_h.any()
-        out = ops.pnp_ransac(x, u, gpu(valid)[0], 64, thr, 3, 3)
+        out = ops.pnp_ransac(x, u, gpu(valid), 64, thr, 3, 3)
         assert all(_failed(*out, b) for b in range(batch))
     # all model points on one line: every sample is degenerate
     line = np.stack([(np.outer(np.arange(16.0), [0.1, 0.2, 0.05]) + [0.3, -0.2, 4.0]).astype(np.float32)] * batch)
@@ -320,15 +308,15 @@ def test_degenerate_pairs_and_small_shapes(batch):
     p4, u4, R, t, _, _ = scenes(seeds, 4, 0.0, 0.0)
     assert all(_failed(*ops.pnp_ransac(*gpu(mirror(p4), u4), None, 64, thr, 3, 3), b) for b in range(batch))
     p3, p2, R, t, inl, thr = scenes(seeds, 64, 0.25, 0.0)
-    xm = gpu(mirror(p3))[0]
+    xm = gpu(mirror(p3))
     out = ops.pnp_ransac(xm, u, None, 64, thr, 3, 3)
     for b in range(batch):
         got = out[2][b].cpu().numpy()
         z = (mirror(p3)[b].astype(D) @ out[0][b].cpu().numpy().astype(D).T + out[1][b].cpu().numpy().astype(D))[:, 2]
         print(f"mirrored scene, pair {b}: ok {bool(out[7][b])}, {int(out[4][b])} inliers of {int(inl[b].sum())} planted")
         assert (z[got] > 0).all() and int(out[4][b]) == got.sum() < inl[b].sum() // 2
-    true_rt = gpu(np.stack([np.concatenate([R[b].ravel(), t[b]]).astype(np.float32) for b in range(batch)]))[0]
-    r, tt, info, ok = ops.pnp_refit(xm, u, gpu(inl[:batch])[0], true_rt[:, :9].reshape(batch, 3, 3).contiguous(), true_rt[:, 9:].contiguous())
+    true_rt = gpu(np.stack([np.concatenate([R[b].ravel(), t[b]]).astype(np.float32) for b in range(batch)]))
+    r, tt, info, ok = ops.pnp_refit(xm, u, gpu(inl[:batch]), true_rt[:, :9].reshape(batch, 3, 3).contiguous(), true_rt[:, 9:].contiguous())
     assert not ok.any() and not info.any()
 
 
@@ -359,10 +347,6 @@ def _raw_pnp(x, u, v, H, rounds, seed, fill, thr):
     return [rt_h, cost, count, r, t, inl, bh, cnt, rmse, info, ok, r2, t2, info2, ok2]
 
 
-def _same_bits(a, b):
-    return all(torch.equal(bits(x), bits(y)) for x, y in zip(a, b))
-
-
 def test_outputs_are_fully_written_reproducible_and_blind_to_invalid_rows():
     n, H = 97, 200
     p3, p2, _, _, _, thr = scenes((100, 101, 102), n, 0.25, 0.5)
@@ -372,7 +356,7 @@ def test_outputs_are_fully_written_reproducible_and_blind_to_invalid_rows():
     x, u, v = gpu(p3, p2, vin)
     a = _raw_pnp(x, u, v, H, 3, 21, 0xFF, thr)                                  # 0xFF bytes: NaN floats, -1 integers
     b = _raw_pnp(x, u, v, H, 3, 21, 0x00, thr)
-    assert _same_bits(a, b)                                                    # every output byte written; two runs agree
+    assert same_bits(a, b)                                                    # every output byte written; two runs agree
     assert not any(torch.isnan(t).any() for t in (a[0], a[1], a[3], a[4], a[8], a[9], a[11], a[12], a[13]))
     assert set(torch.unique(a[5]).tolist()) <= {0, 1} and not (a[5].bool() & ~v.bool()).any()      # inlier <= valid
     assert a[10].bool().all() and a[14].bool().all()
@@ -380,7 +364,7 @@ def test_outputs_are_fully_written_reproducible_and_blind_to_invalid_rows():
     y, w = x.clone(), u.clone()
     y[~v.bool()] = float("nan")
     w[~v.bool()] = 1e30
-    assert _same_bits(a, _raw_pnp(y, w, v, H, 3, 21, 0xFF, thr))
+    assert same_bits(a, _raw_pnp(y, w, v, H, 3, 21, 0xFF, thr))
     # the entry without a sampler does not depend on the batch position
     perm = [2, 0, 1]
     r_p, t_p, info_p, ok_p = ops.pnp_refit(x[perm].contiguous(), u[perm].contiguous(), a[5][perm].contiguous(), a[3][perm].contiguous(),
@@ -396,7 +380,7 @@ def test_normalise_ransac_and_the_module_replay_from_one_graph():
         k1, k2, d1, _, _, _, _ = raw_scenes(s, n, 0.25, 0.5)
         sets.append(list(gpu(scenes(s, n, 0.25, 0.5)[0], k1, k2, d1)))
     m = AbsolutePoseEstimator(torch.from_numpy(K), num_hypotheses=H, seed=4).to(DEV)
-    ki = k_inv()
+    ki = k_inv(K)
 
     def run(x, k1, k2, d1):
         u = ops.normalise_keypoints(k2, ki)

@@ -4,16 +4,15 @@ one batch of stock ops, forms the MSAC cost and takes the argmin -- no sampling,
 mask.  A separate test shows that its cost is mi_pnp_hypotheses'.  mi_rigid_ransac (K17) on the same shape is timed for
 comparison.  Measured on an MI355X: see DESIGN.md, "K23"."""
 import numpy as np
-import pytest
 import torch
 
 import pnp_oracle as QO
 import rigid_oracle as RO
+from gpu_common import DEV, GPU_PERF, time_ms
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.synth import rgbd_camera, synth_rgbd_pair
 
-pytestmark = [pytest.mark.gpu_perf, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU_PERF
 HEIGHT, WIDTH = 240, 320
 K = rgbd_camera(HEIGHT, WIDTH)
 THR = QO.THR_PX / float((K[0, 0] + K[1, 1]) / 2)
@@ -45,21 +44,6 @@ def torch_score(rt_h, x, u, thr):
     return cost, torch.argmin(cost, dim=1)
 
 
-def _time_ms(fn, iters=10, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        times.append(s.elapsed_time(e))
-    return float(np.median(times))
-
-
 def hip_pose(w, rounds=3):
     u = ops.normalise_keypoints(w["k2"], w["k_inv"])
     return ops.pnp_ransac(w["x1"], u, None, w["hyp"], THR, rounds, w["seed"])
@@ -87,10 +71,10 @@ def test_hip_absolute_pose_beats_torch_on_gpu_for_256_pairs():
     w = workload()
     u = ops.normalise_keypoints(w["k2"], w["k_inv"])
     rt_h = ops.pnp_hypotheses(w["x1"], u, None, HYP, THR, w["seed"])[0]
-    hip = _time_ms(lambda: hip_pose(w))
-    hip_hyp = _time_ms(lambda: ops.pnp_hypotheses(w["x1"], u, None, HYP, THR, w["seed"]))
-    rigid = _time_ms(lambda: ops.rigid_ransac(w["x1"], w["x2"], None, HYP, RO.THR, 3, w["seed"]))
-    ref = _time_ms(lambda: torch_score(rt_h, w["x1"], u, THR))
+    hip = time_ms(lambda: hip_pose(w))
+    hip_hyp = time_ms(lambda: ops.pnp_hypotheses(w["x1"], u, None, HYP, THR, w["seed"]))
+    rigid = time_ms(lambda: ops.rigid_ransac(w["x1"], w["x2"], None, HYP, RO.THR, 3, w["seed"]))
+    ref = time_ms(lambda: torch_score(rt_h, w["x1"], u, THR))
     print(f"{PAIRS} pairs x {N_ROWS} rows x {HYP} hypotheses: HIP normalise + pnp_ransac (3 rounds) {hip:.3f} ms "
           f"({PAIRS / hip * 1e3:.0f} pairs/s), hypotheses alone {hip_hyp:.3f} ms; torch-on-GPU projection + cost + argmin of given "
           f"poses {ref:.3f} ms ({ref / hip:.1f}x); mi_rigid_ransac on the same shape {rigid:.3f} ms")

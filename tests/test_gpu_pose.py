@@ -18,13 +18,13 @@ import pytest
 import torch
 
 import pose_oracle as PO
+from gpu_common import DEV, GPU, same_bits
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.pytorch_model.geometry import RelativePoseEstimator, triangulate_points
 from onnx_image_processing_amd.synth import synth_two_view, two_view_camera
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU
 K = two_view_camera()
 F = 500.0
 THR = 1.0 / F
@@ -330,10 +330,6 @@ def _raw_calls(p1, p2, v, H, rounds, seed, fill):
     return [e_h, cost, count, e, inl, bh, cnt, r, t, pm, pc, ok]
 
 
-def _same_bits(a, b):
-    return all(torch.equal(x.contiguous().view(torch.uint8), y.contiguous().view(torch.uint8)) for x, y in zip(a, b))
-
-
 def test_outputs_are_fully_written_reproducible_and_blind_to_invalid_rows():
     n, H = 97, 200
     k1, k2, _, _, _ = scenes((100, 101, 102), n, 0.25, 0.5)
@@ -344,14 +340,14 @@ def test_outputs_are_fully_written_reproducible_and_blind_to_invalid_rows():
     v = torch.from_numpy(valid).to(DEV)
     a = _raw_calls(p1, p2, v, H, 3, 21, 0xFF)                                   # 0xFF bytes: NaN floats, -1 integers
     b = _raw_calls(p1, p2, v, H, 3, 21, 0x00)
-    assert _same_bits(a, b)                                                    # every output byte written; two runs agree
+    assert same_bits(a, b)                                                    # every output byte written; two runs agree
     assert not any(torch.isnan(x).any() for x in (a[0], a[1], a[3], a[7], a[8]))
     assert set(torch.unique(a[4]).tolist()) <= {0, 1} and set(torch.unique(a[9]).tolist()) <= {0, 1}
     assert not (a[4].bool() & ~v.bool()).any() and not (a[9].bool() & ~a[4].bool()).any()     # pose_mask <= inlier <= valid
     q1, q2 = p1.clone(), p2.clone()
     q1[~v.bool()] = float("nan")                                               # invalid rows: any coordinates at all
     q2[~v.bool()] = 1e30
-    assert _same_bits(a, _raw_calls(q1, q2, v, H, 3, 21, 0xFF))
+    assert same_bits(a, _raw_calls(q1, q2, v, H, 3, 21, 0xFF))
     # the entries without a sampler do not depend on the batch position
     perm = [2, 0, 1]
     pv = v[perm].contiguous()

@@ -4,15 +4,14 @@ samples, Hartley normalisation, torch.linalg.eigh on A^T A, denormalisation, the
 batched Sampson evaluation with the MSAC cost, argmin.  The yardstick does LESS than the timed HIP calls (no refinement, no
 pose recovery).  A separate test shows that it computes the same thing as mi_essential_hypotheses."""
 import numpy as np
-import pytest
 import torch
 
 import pose_oracle as PO
+from gpu_common import DEV, GPU_PERF, time_ms
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.synth import synth_two_view, two_view_camera
 
-pytestmark = [pytest.mark.gpu_perf, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU_PERF
 K = two_view_camera()
 THR = 1.0 / 500.0
 PAIRS, N_CORR, HYP = 256, 512, 256
@@ -74,21 +73,6 @@ def torch_hypotheses(p1, p2, idx, thr):
     return e, cost, count, torch.argmin(cost, dim=1)
 
 
-def _time_ms(fn, iters=10, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        times.append(s.elapsed_time(e))
-    return float(np.median(times))
-
-
 def hip_pose(w, rounds=3):
     e, inl, _, _ = ops.essential_ransac(w["p1"], w["p2"], None, w["hyp"], THR, rounds, w["seed"])
     return ops.recover_pose(e, w["p1"], w["p2"], inl)
@@ -126,9 +110,9 @@ def test_torch_formulation_computes_the_same_thing():
 
 def test_hip_pose_beats_torch_on_gpu_for_256_pairs():
     w = workload()
-    hip = _time_ms(lambda: hip_pose(w))
-    hip_hyp = _time_ms(lambda: ops.essential_hypotheses(w["p1"], w["p2"], None, HYP, THR, w["seed"]))
-    ref = _time_ms(lambda: torch_hypotheses(w["p1"], w["p2"], w["idx"], THR))
+    hip = time_ms(lambda: hip_pose(w))
+    hip_hyp = time_ms(lambda: ops.essential_hypotheses(w["p1"], w["p2"], None, HYP, THR, w["seed"]))
+    ref = time_ms(lambda: torch_hypotheses(w["p1"], w["p2"], w["idx"], THR))
     print(f"{PAIRS} pairs x {N_CORR} correspondences x {HYP} hypotheses: HIP ransac (3 rounds) + recover_pose {hip:.3f} ms "
           f"({PAIRS / hip * 1e3:.0f} pairs/s), hypotheses alone {hip_hyp:.3f} ms; torch-on-GPU hypotheses + argmin {ref:.3f} ms "
           f"({ref / hip:.1f}x)")

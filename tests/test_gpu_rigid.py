@@ -28,13 +28,13 @@ import torch
 
 import pose_oracle as PO
 import rigid_oracle as RO
+from gpu_common import DEV, GPU, bits, k_inv, same_bits
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.pytorch_model.geometry import RelativePoseEstimator, RgbdPoseEstimator
 from onnx_image_processing_amd.synth import rgbd_camera
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU
 K = rgbd_camera()
 THR = RO.THR
 COST_RTOL, REFIT_ROT_DEG, REFIT_T_M, GT_ROT_DEG, GT_T_M = 3.9e-5, 1.6e-5, 9.4e-6, 1.5e-4, 2.2e-5
@@ -48,19 +48,11 @@ def scenes(seeds, n, outliers, noise_px, depth_noise):
     return RO.scenes(seeds, n, outliers, noise_px, depth_noise)
 
 
-def k_inv():
-    return torch.from_numpy(np.linalg.inv(K)).float().to(DEV)
-
-
 def lifted(k1, k2, d1, d2):
     """the kernels' own lifted points and joint validity, on the GPU and as numpy arrays"""
-    x1, v1 = ops.lift_keypoints(torch.from_numpy(k1).to(DEV), torch.from_numpy(d1).to(DEV), k_inv(), 1.0, RO.MIN_DEPTH, RO.MAX_DEPTH)
-    x2, v2 = ops.lift_keypoints(torch.from_numpy(k2).to(DEV), torch.from_numpy(d2).to(DEV), k_inv(), 1.0, RO.MIN_DEPTH, RO.MAX_DEPTH, v1)
+    x1, v1 = ops.lift_keypoints(torch.from_numpy(k1).to(DEV), torch.from_numpy(d1).to(DEV), k_inv(K), 1.0, RO.MIN_DEPTH, RO.MAX_DEPTH)
+    x2, v2 = ops.lift_keypoints(torch.from_numpy(k2).to(DEV), torch.from_numpy(d2).to(DEV), k_inv(K), 1.0, RO.MIN_DEPTH, RO.MAX_DEPTH, v1)
     return x1, x2, v2, x1.cpu().numpy(), x2.cpu().numpy(), v2.cpu().numpy()
-
-
-def bits(x):
-    return x.contiguous().view(torch.uint8) if isinstance(x, torch.Tensor) else np.ascontiguousarray(x).view(np.uint8)
 
 
 # ---- lift ---------------------------------------------------------------------------------------------------------------------
@@ -324,7 +316,7 @@ def _raw_calls(kp1, kp2, dep1, dep2, vin, H, rounds, seed, fill):
         t = torch.empty(shape, dtype=dtype, device=DEV)
         t.view(torch.uint8).fill_(fill)
         return t
-    ki = k_inv()
+    ki = k_inv(K)
     x1, v1, x2, v2 = dirty((b, n, 3), torch.float32), dirty((b, n), torch.uint8), dirty((b, n, 3), torch.float32), dirty((b, n), torch.uint8)
     N.call("mi_lift_keypoints", kp1.data_ptr(), dep1.data_ptr(), 0, b, n, h, w, ki.data_ptr(), 1.0, 0.1, 10.0, vin.data_ptr(),
            x1.data_ptr(), v1.data_ptr(), N.stream_ptr())
@@ -355,10 +347,6 @@ def _raw_rigid(x1, x2, v, H, rounds, seed, fill):
     return [rt_h, cost, count, r, t, inl, bh, cnt, rmse, ok, r2, t2, ok2]
 
 
-def _same_bits(a, b):
-    return all(torch.equal(bits(x), bits(y)) for x, y in zip(a, b))
-
-
 def test_outputs_are_fully_written_reproducible_and_blind_to_invalid_rows():
     n, H = 97, 200
     k1, k2, d1, d2, _, _, _ = scenes((100, 101, 102), n, 0.25, 0.5, 0.001)
@@ -368,7 +356,7 @@ def test_outputs_are_fully_written_reproducible_and_blind_to_invalid_rows():
     args = [torch.from_numpy(x).to(DEV) for x in (k1, k2, d1, d2, vin)]
     a = _raw_calls(*args, H, 3, 21, 0xFF)                                       # 0xFF bytes: NaN floats, -1 integers
     b = _raw_calls(*args, H, 3, 21, 0x00)
-    assert _same_bits(a, b)                                                    # every output byte written; two runs agree
+    assert same_bits(a, b)                                                    # every output byte written; two runs agree
     assert not any(torch.isnan(x).any() for x in (a[0], a[2], a[4], a[5], a[7], a[8], a[12], a[14], a[15]))
     v = a[3]
     assert set(torch.unique(v).tolist()) <= {0, 1} and set(torch.unique(a[9]).tolist()) <= {0, 1}
@@ -378,15 +366,15 @@ def test_outputs_are_fully_written_reproducible_and_blind_to_invalid_rows():
     x1, x2 = a[0].clone(), a[2].clone()
     x1[~v.bool()] = float("nan")
     x2[~v.bool()] = 1e30
-    assert _same_bits(a[4:], _raw_rigid(x1, x2, v, H, 3, 21, 0xFF))
+    assert same_bits(a[4:], _raw_rigid(x1, x2, v, H, 3, 21, 0xFF))
     kk1 = args[0].clone()
     kk1[~args[4].bool()] = float("nan")
-    assert _same_bits(a, _raw_calls(kk1, *args[1:], H, 3, 21, 0xFF))
+    assert same_bits(a, _raw_calls(kk1, *args[1:], H, 3, 21, 0xFF))
     # the entries without a sampler do not depend on the batch position
     perm = [2, 0, 1]
     r_p, t_p, ok_p = ops.rigid_refit(a[0][perm].contiguous(), a[2][perm].contiguous(), a[9][perm].contiguous())
     assert torch.equal(bits(r_p), bits(a[14][perm])) and torch.equal(bits(t_p), bits(a[15][perm])) and torch.equal(ok_p, a[16][perm].bool())
-    p_p, v_p = ops.lift_keypoints(args[0][perm].contiguous(), args[2][perm].contiguous(), k_inv(), 1.0, 0.1, 10.0, args[4][perm].contiguous())
+    p_p, v_p = ops.lift_keypoints(args[0][perm].contiguous(), args[2][perm].contiguous(), k_inv(K), 1.0, 0.1, 10.0, args[4][perm].contiguous())
     assert torch.equal(bits(p_p), bits(a[0][perm])) and torch.equal(v_p, a[1][perm].bool())
 
 
@@ -395,7 +383,7 @@ def test_lift_ransac_and_the_module_replay_from_one_graph():
     sets = [scenes(s, n, 0.25, 0.5, 0.001)[:4] for s in ((100, 101, 102), (103, 104, 105), (106, 107, 108))]
     sets = [[torch.from_numpy(x).to(DEV) for x in s] for s in sets]
     m = RgbdPoseEstimator(torch.from_numpy(K), num_hypotheses=H, seed=4).to(DEV)
-    ki = k_inv()
+    ki = k_inv(K)
 
     def run(k1, k2, d1, d2):
         x1, v1 = ops.lift_keypoints(k1, d1, ki, 1.0, 0.1, 10.0)

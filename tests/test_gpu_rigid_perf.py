@@ -4,15 +4,14 @@ a batched 3x3 torch.linalg.svd, a batched point-to-point evaluation with the MSA
 the timed HIP calls (no lift, no refinement, no inlier mask).  A separate test shows that it computes the same thing as
 mi_rigid_hypotheses.  Measured on an MI355X: 0.174 ms (1.47 M pairs/s) against 12.56 ms, 72x."""
 import numpy as np
-import pytest
 import torch
 
 import rigid_oracle as RO
+from gpu_common import DEV, GPU_PERF, time_ms
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.synth import rgbd_camera, synth_rgbd_pair
 
-pytestmark = [pytest.mark.gpu_perf, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU_PERF
 HEIGHT, WIDTH = 240, 320
 K = rgbd_camera(HEIGHT, WIDTH)
 THR = RO.THR
@@ -62,21 +61,6 @@ def torch_hypotheses(x1, x2, idx, thr):
     return r, t, cost, count, torch.argmin(cost, dim=1)
 
 
-def _time_ms(fn, iters=10, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        times.append(s.elapsed_time(e))
-    return float(np.median(times))
-
-
 def hip_pose(w, rounds=3):
     x1, x2, v = lift_both(w)
     return ops.rigid_ransac(x1, x2, v, w["hyp"], THR, rounds, w["seed"])
@@ -108,10 +92,10 @@ def test_torch_formulation_computes_the_same_thing():
 
 def test_hip_rgbd_pose_beats_torch_on_gpu_for_256_pairs():
     w = workload()
-    hip = _time_ms(lambda: hip_pose(w))
-    hip_hyp = _time_ms(lambda: ops.rigid_hypotheses(w["x1"], w["x2"], None, HYP, THR, w["seed"]))
-    hip_lift = _time_ms(lambda: lift_both(w))
-    ref = _time_ms(lambda: torch_hypotheses(w["x1"], w["x2"], w["idx"], THR))
+    hip = time_ms(lambda: hip_pose(w))
+    hip_hyp = time_ms(lambda: ops.rigid_hypotheses(w["x1"], w["x2"], None, HYP, THR, w["seed"]))
+    hip_lift = time_ms(lambda: lift_both(w))
+    ref = time_ms(lambda: torch_hypotheses(w["x1"], w["x2"], w["idx"], THR))
     print(f"{PAIRS} pairs x {N_ROWS} rows x {HYP} hypotheses: HIP lifts + ransac (3 rounds) {hip:.3f} ms ({PAIRS / hip * 1e3:.0f} pairs/s), "
           f"lifts alone {hip_lift:.3f} ms, hypotheses alone {hip_hyp:.3f} ms; torch-on-GPU hypotheses + argmin {ref:.3f} ms "
           f"({ref / hip:.1f}x)")

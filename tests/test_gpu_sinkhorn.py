@@ -23,7 +23,7 @@ import pytest
 import torch
 
 import sinkhorn_oracle as S
-from gpu_common import DEV, mods  # noqa: F401  (mods: the module fixture)
+from gpu_common import DEV, mods, twice, up  # noqa: F401  (mods: the module fixture)
 from helpers import p_close
 
 pytestmark = pytest.mark.gpu
@@ -36,10 +36,6 @@ ITERATIONS = (1, 2, 7)
 def _report(group, what, **ratios):
     if os.environ.get("MI_REPORT"):
         print(f"[sinkhorn {group}] {what}: worst error / bound " + ", ".join(f"{k} {v:.3g}" for k, v in ratios.items()))
-
-
-def _up(x, k):
-    return (x + k - 1) // k * k
 
 
 # ------------------------------------------------------------------ guarded, poisoned outputs
@@ -74,13 +70,6 @@ class _Work:
         assert bool((self.full[self.GUARD + self.nbytes:] == 0xFF).all()), f"{what}: bytes behind the workspace were written"
 
 
-def _twice(what, run):
-    first, second = run(), run()
-    for x, y in zip(first, second):
-        assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), f"{what}: the call does not repeat bit for bit"
-    return first
-
-
 # ------------------------------------------------------------------ problems, references and device inputs (cached)
 @functools.lru_cache(maxsize=None)
 def _problem(form, batch, n, m, regime):
@@ -97,7 +86,7 @@ def _dots_on_device(batch, n, m, normalized):
     b1, b2 = S.bit_inputs(batch, n, m)
     words = b1.shape[-1]
     t1, t2 = [torch.from_numpy(np.ascontiguousarray(x).view(np.int32)).to(DEV) for x in (b1, b2)]
-    pitch = _up(m, 8) + 8
+    pitch = up(m, 8) + 8
     dots = torch.zeros((batch * n, pitch), dtype=torch.int16, device=DEV)
     ri, ci = torch.zeros((batch * n, 2), device=DEV), torch.zeros((batch * m, 2), device=DEV)
     N.call("mi_cost_dots_bits", t1.data_ptr(), t2.data_ptr(), batch, n, m, 32 * words, int(normalized), dots.data_ptr(), pitch,
@@ -169,7 +158,7 @@ def _check_form(group, what, prob, run, bounded, prob_form, regime, iterations=I
     e2e = [t for t in S.E2E_ITERATIONS[regime]]
     need = sorted(set(iterations) | {t - 1 for t in iterations if t > 1} | set(e2e))
     last = max(iterations)
-    got = {t: _twice(f"{what} T {t}", lambda: run(t, t == last)) for t in need}
+    got = {t: twice(f"{what} T {t}", lambda: run(t, t == last)) for t in need}
     Z = prob["Z"]
     for t in iterations:
         u, v = got[t][:2]
@@ -325,7 +314,7 @@ def test_p_writers_vs_fp64(mods, form, shape, key18):
                 run = lambda: _run_dots(N, prob, 7, prob["sqnorm_bound"], MULTI_LAUNCH, True)
             else:
                 run = lambda: _run_f32(N, prob, 7, True, True)
-            _check_p("H", what, prob, *_twice(what, run), 7)
+            _check_p("H", what, prob, *twice(what, run), 7)
 
 
 # ------------------------------------------------------------------ I. argument checks

@@ -19,13 +19,13 @@ import torch
 
 import surface_oracle as SO
 import tsdf_oracle as TO
+from gpu_common import DEV, GPU, bits
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.pytorch_model.geometry import TsdfVolume
 from onnx_image_processing_amd.synth import rgbd_camera
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU
 F32, F64 = np.float32, np.float64
 H, W = 37, 53
 SPECS = {"room": TO.ROOM, "odd": TO.ODD, "tiny": TO.TINY}
@@ -33,10 +33,6 @@ COUNTS = {"room": (9232, 17732), "odd": (6659, 12744), "tiny": (9, 8), "plane": 
 TOL = {"room": (2.4424e-5, 2.0062e-5), "odd": (1.1482e-5, 1.7495e-5), "tiny": (7.8848e-7, 0.0), "plane": (2.7866e-6, 0.0),
        "sphere": (3.6154e-6, 1.0840e-6)}
 SPHERE = ((9.3, 9.7, 10.1), 6.2)
-
-
-def bits(x):
-    return x.contiguous().view(torch.uint8) if isinstance(x, torch.Tensor) else np.ascontiguousarray(x).view(np.uint8)
 
 
 @functools.lru_cache(maxsize=None)

@@ -7,17 +7,16 @@ Measured on an MI355X (8.9 % of the volume observed, 142,609 vertices, 281,910 t
 against the 134 MB, 7.7x the 0.03 ms floor derived from K19's 4.3 TB/s) against 0.789 ms, 3.4x; full extraction 0.473 ms;
 points only 0.377 ms."""
 import numpy as np
-import pytest
 import torch
 
 import surface_oracle as SO
 import tsdf_oracle as TO
+from gpu_common import DEV, GPU_PERF, time_ms
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.pytorch_model.geometry import TsdfVolume
 from onnx_image_processing_amd.synth import rgbd_camera, synth_depth_room
 
-pytestmark = [pytest.mark.gpu_perf, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU_PERF
 HEIGHT, WIDTH, FRAMES, SIDE = 480, 640, 4, 256
 BIG = ((SIDE, SIDE, SIDE), (-2.0, -2.6, 0.4), 0.015625, 0.0625)           # tests/test_gpu_tsdf_perf.py's volume
 BYTES_PER_VOXEL = 8                                                       # DESIGN.md, K20: the volume is read once
@@ -37,21 +36,6 @@ def torch_vertex_count(volume, min_weight=1.0, dtype=torch.float32):
         q = (slice(dz, nz), slice(dy, ny), slice(dx, nx))
         total = total + (obs[p] & obs[q] & (ins[p] ^ ins[q])).sum()
     return total
-
-
-def _time_ms(fn, iters=10, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        times.append(s.elapsed_time(e))
-    return float(np.median(times))
 
 
 def test_torch_formulation_counts_the_same_thing():
@@ -80,10 +64,10 @@ def test_hip_sizing_pass_beats_torch_on_gpu_for_256_cubed():
     assert int(torch_vertex_count(m.volume[0])) == nv and nv > 100000 and nt > 100000
     observed = float((m.volume[..., 1] > 0).float().mean())
 
-    sizing = _time_ms(lambda: ops.tsdf_surface_counts(m.volume))
-    ref = _time_ms(lambda: torch_vertex_count(m.volume[0]), iters=5, warmup=2)
-    full = _time_ms(lambda: m.extract_surface(nv, nt))
-    points = _time_ms(lambda: m.extract_points(nv))
+    sizing = time_ms(lambda: ops.tsdf_surface_counts(m.volume))
+    ref = time_ms(lambda: torch_vertex_count(m.volume[0]), iters=5, warmup=2)
+    full = time_ms(lambda: m.extract_surface(nv, nt))
+    points = time_ms(lambda: m.extract_points(nv))
     vertex, normal, tris, c = m.extract_surface(nv, nt)
     assert torch.equal(c, counts) and int(tris.min()) >= 0 and int(tris.max()) < nv and bool((vertex[..., 3] == 1).all())
     mbytes = SIDE ** 3 * BYTES_PER_VOXEL / 1e6

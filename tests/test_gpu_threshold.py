@@ -10,17 +10,13 @@ import torch
 
 from test_threshold_host import (F32, apply_oracle, binary_oracle, golden, hist_oracle, multi_cases, multi_otsu_oracle,
                                  otsu_cases, otsu_oracle)
+from gpu_common import DEV, GPU, gpu
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.synth import THRESHOLD_FAMILIES, synth_threshold_frame
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU
 NP_DTYPES = {"uint8": np.uint8, "uint16": np.uint16, "int32": np.int32, "float32": np.float32}
-
-
-def _gpu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _values(seed, h, w, lo, hi):
@@ -47,7 +43,7 @@ def _frame(seed, h, w, dtype, min_val, bins):
 
 
 def _check_hist(frames, min_val, bins, what):
-    got = ops.histogram(_gpu(frames), min_val, bins)
+    got = ops.histogram(gpu(frames), min_val, bins)
     assert got.dtype == torch.int64
     got = got.cpu().numpy()
     if frames.ndim < 3:
@@ -85,37 +81,37 @@ def test_histogram_of_a_constant_frame(dtype):
     """every pixel in one bin: the highest contention, on the LDS path and on the global path"""
     frame = np.full((480, 640), 77, NP_DTYPES[dtype])
     for bins in (256, 65536 if dtype != "uint8" else 200):
-        got = ops.histogram(_gpu(frame), 0, bins).cpu().numpy()
+        got = ops.histogram(gpu(frame), 0, bins).cpu().numpy()
         assert got[77] == 480 * 640 and got.sum() == 480 * 640, (dtype, bins)
-    assert int(ops.histogram(_gpu(frame), 78, 100).sum()) == 0            # nothing in range: all zeros, not stale memory
+    assert int(ops.histogram(gpu(frame), 78, 100).sum()) == 0            # nothing in range: all zeros, not stale memory
 
 
 def test_histogram_batch_equals_each_frame_alone():
     """5 frames of differing content whose starts are not 16-byte aligned (37 * 53 bytes each), and 3 full frames"""
     frames = np.stack([synth_threshold_frame(20 + k, 37, 53, THRESHOLD_FAMILIES[k]) for k in range(5)])
-    batch = ops.histogram(_gpu(frames), 0, 256)
+    batch = ops.histogram(gpu(frames), 0, 256)
     for b in range(5):
-        alone = ops.histogram(_gpu(frames[b]), 0, 256)
+        alone = ops.histogram(gpu(frames[b]), 0, 256)
         assert torch.equal(alone, batch[b]) and np.array_equal(alone.cpu().numpy(), hist_oracle(frames[b], 0, 256)), b
     full = np.stack([synth_threshold_frame(30 + k, 480, 640, f) for k, f in enumerate(("trimodal", "uniform", "spikes"))])
     _check_hist(full, 0, 256, "480x640 batch")
     _check_hist(full.astype(np.uint16) * 257, 0, 65536, "480x640 uint16 batch, global path")
     # a sliced (non-contiguous) batch and an unaligned view
-    sliced = ops.histogram(_gpu(full)[:, 1:, 3:], 0, 256).cpu().numpy()
+    sliced = ops.histogram(gpu(full)[:, 1:, 3:], 0, 256).cpu().numpy()
     assert np.array_equal(sliced, np.stack([hist_oracle(f[1:, 3:], 0, 256) for f in full]))
-    flat = _gpu(full.reshape(-1))
+    flat = gpu(full.reshape(-1))
     assert np.array_equal(ops.histogram(flat[5:5 + 4001], 0, 256).cpu().numpy(), hist_oracle(full.reshape(-1)[5:4006], 0, 256))
 
 
 def _otsu_gpu(hist, min_val):
-    return ops.otsu_threshold(_gpu(np.asarray(hist, np.int64)), min_val).cpu().numpy()
+    return ops.otsu_threshold(gpu(np.asarray(hist, np.int64)), min_val).cpu().numpy()
 
 
 def test_otsu_equals_the_fixture_and_the_oracle():
     g = golden()
     for name in otsu_cases(g):
         frame, max_val = g[f"{name}__frame"], int(g[f"{name}__max_val"])
-        hist = ops.histogram(_gpu(frame), 0, max_val + 1)
+        hist = ops.histogram(gpu(frame), 0, max_val + 1)
         got = ops.otsu_threshold(hist, 0)
         assert got.dtype == torch.int32 and got.shape == ()
         assert int(got) == int(g[f"{name}__thresh"]) == otsu_oracle(hist.cpu().numpy(), 0)[0], name
@@ -159,11 +155,11 @@ def test_otsu_at_65536_bins():
     for f in frames:
         hists.append(hist_oracle(f, 0, 65536))
         want.append(otsu_oracle(hists[-1], 0)[0])
-    got_hist = ops.histogram(_gpu(frames[0]), 0, 65536)
+    got_hist = ops.histogram(gpu(frames[0]), 0, 65536)
     assert np.array_equal(got_hist.cpu().numpy(), hists[0])
     assert _otsu_gpu(np.stack(hists), 0).tolist() == want
     assert 10000 < want[0] < 55000 and want[2] == 0
-    thresh, bin_img = ops.otsu(_gpu(frames[0]), 0, 65535, torch.int32)
+    thresh, bin_img = ops.otsu(gpu(frames[0]), 0, 65535, torch.int32)
     assert int(thresh) == want[0]
     assert np.array_equal(bin_img.cpu().numpy(), binary_oracle(frames[0], want[0], 0, 65535, np.int32))
 
@@ -187,10 +183,10 @@ def test_multi_otsu_equals_the_fp64_oracle(n_class, bins):
     hists = np.stack(hists).astype(np.int64)
     for min_val in (0, 11):
         want = [multi_otsu_oracle(h, min_val, n_class) for h in hists]
-        got = ops.multi_otsu_threshold(_gpu(hists), min_val, n_class)
+        got = ops.multi_otsu_threshold(gpu(hists), min_val, n_class)
         assert got.dtype == torch.int32 and got.shape == (len(hists), n_class - 1)
         assert got.cpu().numpy().tolist() == want, (n_class, bins, min_val)
-        alone = ops.multi_otsu_threshold(_gpu(hists[1]), min_val, n_class)
+        alone = ops.multi_otsu_threshold(gpu(hists[1]), min_val, n_class)
         assert alone.shape == (n_class - 1,) and alone.cpu().numpy().tolist() == want[1]
     assert want[4] == [11 + k for k in range(n_class - 1)]                                  # all ties: the first combination
 
@@ -201,7 +197,7 @@ def test_multi_otsu_four_classes_at_255_bins():
     frame = synth_threshold_frame(51, 480, 640, "trimodal", levels=255)
     hists = np.stack([hist_oracle(frame, 0, 255), _gapped_hist(rng, 255, 0.3)])
     want = [multi_otsu_oracle(h, 0, 4) for h in hists]
-    got = ops.multi_otsu_threshold(_gpu(hists), 0, 4)
+    got = ops.multi_otsu_threshold(gpu(hists), 0, 4)
     assert got.cpu().numpy().tolist() == want
 
 
@@ -210,19 +206,19 @@ def test_multi_otsu_large_ranges_without_lds_prefix():
     rng = np.random.default_rng(10)
     for n_class, bins in ((2, 4096), (2, 65536), (3, 2047), (3, 2048)):
         h = _gapped_hist(rng, bins, 0.4)
-        assert ops.multi_otsu_threshold(_gpu(h), 0, n_class).cpu().numpy().tolist() == multi_otsu_oracle(h, 0, n_class), (n_class, bins)
+        assert ops.multi_otsu_threshold(gpu(h), 0, n_class).cpu().numpy().tolist() == multi_otsu_oracle(h, 0, n_class), (n_class, bins)
 
 
 def test_multi_otsu_on_the_fixture():
     g = golden()
     for name in multi_cases(g):
         hist, n_class = g[f"{name}__hist"], int(g[f"{name}__n_class"])
-        got = ops.multi_otsu_threshold(_gpu(hist), 0, n_class).cpu().numpy().tolist()
+        got = ops.multi_otsu_threshold(gpu(hist), 0, n_class).cpu().numpy().tolist()
         assert got == multi_otsu_oracle(hist, 0, n_class), name
         if not int(g[f"{name}__differs"]):
             assert got == [int(t) for t in g[f"{name}__thresholds"]], name
         if f"{name}__frame" in g:
-            assert np.array_equal(ops.histogram(_gpu(g[f"{name}__frame"]), 0, hist.size).cpu().numpy(), hist), name
+            assert np.array_equal(ops.histogram(gpu(g[f"{name}__frame"]), 0, hist.size).cpu().numpy(), hist), name
 
 
 def test_apply_and_bin_img_equal_the_fixture_in_every_dtype():
@@ -234,7 +230,7 @@ def test_apply_and_bin_img_equal_the_fixture_in_every_dtype():
         for in_dtype in ("uint8", "uint16", "int32", "float32"):
             if in_dtype == "uint8" and max_val > 255:
                 continue
-            x = _gpu(frame.astype(NP_DTYPES[in_dtype]))
+            x = gpu(frame.astype(NP_DTYPES[in_dtype]))
             for dtype, npdt in outs.items():
                 if dtype == torch.uint8 and max_val > 255:
                     continue
@@ -250,23 +246,23 @@ def test_labels_equal_the_oracle():
             frames = np.stack([_frame(7 * k + h, h, w, dtype, 0, 256) for k in range(3)])
             for n_thresh in (1, 2, 3, 4):
                 th = np.sort(rng.integers(-3, 260, (3, n_thresh))).astype(np.int32)
-                got = ops.threshold_apply(_gpu(frames), _gpu(th))
+                got = ops.threshold_apply(gpu(frames), gpu(th))
                 assert got.dtype == torch.uint8 and got.shape == frames.shape
                 for b in range(3):
                     assert np.array_equal(got[b].cpu().numpy(), apply_oracle(frames[b], th[b])), (dtype, h, w, n_thresh, b)
-                one = ops.threshold_apply(_gpu(frames[1]), _gpu(th[1]))
+                one = ops.threshold_apply(gpu(frames[1]), gpu(th[1]))
                 assert torch.equal(one, got[1])
             th1 = rng.integers(0, 256, 3).astype(np.int32)
             for out_dtype, npdt in ((torch.uint8, np.uint8), (torch.int32, np.int32), (torch.float32, np.float32)):
-                got = ops.threshold_apply(_gpu(frames), _gpu(th1), binary=(3, 250, out_dtype)).cpu().numpy()
+                got = ops.threshold_apply(gpu(frames), gpu(th1), binary=(3, 250, out_dtype)).cpu().numpy()
                 for b in range(3):
                     assert np.array_equal(got[b], binary_oracle(frames[b], th1[b], 3, 250, npdt)), (dtype, h, w, out_dtype, b)
-    nan = ops.threshold_apply(torch.full((4, 4), float("nan"), device=DEV), _gpu(np.int32([5])), binary=(0, 255, torch.int32))
+    nan = ops.threshold_apply(torch.full((4, 4), float("nan"), device=DEV), gpu(np.int32([5])), binary=(0, 255, torch.int32))
     assert bool((nan == 255).all())                                                         # torch.where(img <= thresh, ...)
     with pytest.raises(RuntimeError, match="uint8, uint16, int32 or float32"):
-        ops.threshold_apply(torch.zeros(4, 4, device=DEV, dtype=torch.float64), _gpu(np.int32([5])))
+        ops.threshold_apply(torch.zeros(4, 4, device=DEV, dtype=torch.float64), gpu(np.int32([5])))
     with pytest.raises(RuntimeError, match="thresholds"):
-        ops.threshold_apply(torch.zeros(2, 4, 4, device=DEV), _gpu(np.int32([5, 6, 7])))
+        ops.threshold_apply(torch.zeros(2, 4, 4, device=DEV), gpu(np.int32([5, 6, 7])))
 
 
 def test_modules_reproduce_the_reference_fixture():
@@ -278,16 +274,16 @@ def test_modules_reproduce_the_reference_fixture():
         frame, max_val = g[f"{name}__frame"], int(g[f"{name}__max_val"])
         for dtype in (torch.int32, torch.float32) + ((torch.uint8,) if max_val <= 255 else ()):
             model = OtsuThreshold(0, max_val, dtype=dtype, device=DEV)
-            thresh, bin_img = model(_gpu(frame))
+            thresh, bin_img = model(gpu(frame))
             assert thresh.dtype == torch.int64 and thresh.shape == () and int(thresh) == int(g[f"{name}__thresh"]), name
             assert bin_img.dtype == dtype and torch.equal(bin_img.to(torch.int32).cpu(), torch.from_numpy(g[f"{name}__bin_img"]))
-            t2, b2 = model(_gpu(frame.astype(np.float32)))                  # the reference's hosts also hand in float32
+            t2, b2 = model(gpu(frame.astype(np.float32)))                  # the reference's hosts also hand in float32
             assert int(t2) == int(thresh) and torch.equal(b2, bin_img)
         if max_val == 255:
             by_size.setdefault(frame.shape, []).append(name)
     for shape, names in by_size.items():                                    # a leading batch dimension
         frames = np.stack([g[f"{n}__frame"] for n in names])
-        thresh, bin_img = OtsuThreshold(0, 255, device=DEV)(_gpu(frames))
+        thresh, bin_img = OtsuThreshold(0, 255, device=DEV)(gpu(frames))
         assert thresh.shape == (len(names),) and thresh.cpu().tolist() == [int(g[f"{n}__thresh"]) for n in names]
         assert np.array_equal(bin_img.cpu().numpy(), np.stack([g[f"{n}__bin_img"] for n in names]))
     groups = {}
@@ -296,19 +292,19 @@ def test_modules_reproduce_the_reference_fixture():
             continue
         hist, n_class = g[f"{name}__hist"], int(g[f"{name}__n_class"])
         ref = [int(t) for t in g[f"{name}__thresholds"]]
-        from_hist = MultiOtsuThreshold(0, hist.size, device=DEV, n_class=n_class)(_gpu(hist))
+        from_hist = MultiOtsuThreshold(0, hist.size, device=DEV, n_class=n_class)(gpu(hist))
         assert isinstance(from_hist, list) and len(from_hist) == n_class - 1
         assert all(t.dtype == torch.int64 and t.shape == () for t in from_hist) and [int(t) for t in from_hist] == ref, name
-        as_float = MultiOtsuThreshold(0, hist.size, device=DEV, n_class=n_class)(_gpu(hist.astype(np.float32)))
+        as_float = MultiOtsuThreshold(0, hist.size, device=DEV, n_class=n_class)(gpu(hist.astype(np.float32)))
         assert [int(t) for t in as_float] == ref                             # float32 counts, as the reference takes them
         if f"{name}__frame" in g:
             frame = g[f"{name}__frame"]
-            from_img = MultiOtsuThreshold(0, hist.size, device=DEV, n_class=n_class, calc_hist=True)(_gpu(frame))
+            from_img = MultiOtsuThreshold(0, hist.size, device=DEV, n_class=n_class, calc_hist=True)(gpu(frame))
             assert [int(t) for t in from_img] == ref, name
             groups.setdefault((n_class, hist.size, frame.shape), []).append(name)
     for (n_class, bins, _), names in groups.items():
         frames = np.stack([g[f"{n}__frame"] for n in names])
-        out = MultiOtsuThreshold(0, bins, device=DEV, n_class=n_class, calc_hist=True)(_gpu(frames))
+        out = MultiOtsuThreshold(0, bins, device=DEV, n_class=n_class, calc_hist=True)(gpu(frames))
         assert len(out) == n_class - 1 and all(t.shape == (len(names),) for t in out)
         assert torch.stack(out, 1).cpu().tolist() == [[int(t) for t in g[f"{n}__thresholds"]] for n in names]
 
@@ -316,7 +312,7 @@ def test_modules_reproduce_the_reference_fixture():
 def test_two_runs_are_bit_identical_and_dirty_buffers_do_not_show():
     """The C entries take outputs and workspaces of any content."""
     frames = np.stack([synth_threshold_frame(80 + k, 37, 53, THRESHOLD_FAMILIES[k % 6], levels=200) for k in range(4)])
-    x = _gpu(frames)
+    x = gpu(frames)
     batch, pixels, s = 4, 37 * 53, N.stream_ptr
     runs = []
     for junk in (None, 0x00, 0xFF, 0x5A, 0x7F):
@@ -362,8 +358,8 @@ def test_fused_otsu_captured_in_one_graph():
     """ops.otsu on 4 frames as one straight-line graph (nothing is read back between histogram, search and apply):
     replayed on new frame content it equals the eager result on that content."""
     h, w, batch = 120, 160, 4
-    first = _gpu(np.stack([synth_threshold_frame(90 + k, h, w, THRESHOLD_FAMILIES[k]) for k in range(batch)]))
-    second = _gpu(np.stack([synth_threshold_frame(95 + k, h, w, THRESHOLD_FAMILIES[5 - k]) for k in range(batch)]))
+    first = gpu(np.stack([synth_threshold_frame(90 + k, h, w, THRESHOLD_FAMILIES[k]) for k in range(batch)]))
+    second = gpu(np.stack([synth_threshold_frame(95 + k, h, w, THRESHOLD_FAMILIES[5 - k]) for k in range(batch)]))
     static = first.clone()
 
     def run(x):

@@ -7,15 +7,14 @@ Reported without a condition (no stock formulation exists): Otsu over the 16-bit
 import itertools
 
 import numpy as np
-import pytest
 import torch
 
 from test_threshold_host import combinations_lex
+from gpu_common import DEV, GPU_PERF, time_ms
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.synth import synth_threshold_frame
 
-pytestmark = [pytest.mark.gpu_perf, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU_PERF
 H, W, FRAMES = 480, 640, 16
 MULTI_BINS, MULTI_CLASSES = 255, 3
 
@@ -82,21 +81,6 @@ def torch_multi_cumsum(img, c):
     return c["combos"][torch.argmax(var)] - 1
 
 
-def _time_ms(fn, iters=10, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        times.append(s.elapsed_time(e))
-    return float(np.median(times))
-
-
 def workload(frames=FRAMES, seed=700):
     """frames (frames, H, W) uint8 with values below 255 on the GPU, and the constants of the torch formulations"""
     host = np.stack([synth_threshold_frame(seed + i, H, W, "trimodal", levels=MULTI_BINS) for i in range(frames)])
@@ -156,13 +140,13 @@ def test_hip_thresholds_beat_torch_on_gpu_for_sixteen_frames():
     t = workload()
     failed = []
     for name, (hip_fn, torch_fns) in operations(t).items():
-        hip = _time_ms(hip_fn)
-        refs = {k: _time_ms(fn) for k, fn in torch_fns.items()}
+        hip = time_ms(hip_fn)
+        refs = {k: time_ms(fn) for k, fn in torch_fns.items()}
         best = min(refs, key=refs.get)
         print(f"{name}: 16 frames HIP {hip:.3f} ms; torch-on-GPU " + ", ".join(f"{k} {v:.3f} ms" for k, v in refs.items())
               + f"; yardstick: {best} ({refs[best] / hip:.1f}x)")
         if not hip < refs[best]:
             failed.append(name)
     for name, hip_fn in unmeasured_operations(t).items():
-        print(f"{name}: 16 frames HIP {_time_ms(hip_fn):.3f} ms (no torch formulation can run it)")
+        print(f"{name}: 16 frames HIP {time_ms(hip_fn):.3f} ms (no torch formulation can run it)")
     assert not failed, failed

@@ -24,12 +24,12 @@ import torch
 
 import icp_oracle as IO
 import tsdf_oracle as TO
+from gpu_common import DEV, GPU, bits
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.pytorch_model.geometry import TsdfVolume
 from onnx_image_processing_amd.synth import rgbd_camera, synth_depth_room
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU
 F32, F64 = np.float32, np.float64
 SHAPES = [(37, 53), (48, 64)]
 SPECS = {"room": TO.ROOM, "odd": TO.ODD, "tiny": TO.TINY}
@@ -39,10 +39,6 @@ RAYCAST_TOL = {((37, 53), "room"): (9.31e-6, 2.11e-5), ((37, 53), "odd"): (5.41e
 # (truth deg, truth m, oracle deg, oracle m, information relative, rmse relative)
 TRACK_TOL = (5.5823e-2, 1.2180e-3, 1.108e-5, 7.50e-7, 3.54e-7, 1.61e-5)
 BEHIND = (np.eye(3), np.array([0.0, 0.0, -1.75]))    # a camera at world z = 1.75: the nearer part of every volume is behind it
-
-
-def bits(x):
-    return x.contiguous().view(torch.uint8) if isinstance(x, torch.Tensor) else np.ascontiguousarray(x).view(np.uint8)
 
 
 def t32(a):

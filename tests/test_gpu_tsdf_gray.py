@@ -27,13 +27,13 @@ import icp_oracle as IO
 import photo_oracle as PO
 import tsdf_gray_oracle as GO
 import tsdf_oracle as TO
+from gpu_common import DEV, GPU, bits
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.pytorch_model.geometry import DirectTsdfVolume, TsdfVolume
 from onnx_image_processing_amd.synth import rgbd_camera, synth_depth_room
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU
 F32, F64 = np.float32, np.float64
 SPECS = {"room": TO.ROOM, "odd": TO.ODD, "tiny": TO.TINY}
 SEEDS = (0, 1, 2)
@@ -41,10 +41,6 @@ PLANE_TOL = {(48, 64): (2 * 3.1529e-6, 4 * 1.0139e-7), (120, 160): (2 * 3.7049e-
 PLANE_TRUTH = {(48, 64): ((1.8643e-2, 6.8776e-4), (1.2932e-2, 7.4820e-4), (1.5486e-2, 9.1242e-4)),
                (120, 160): ((2.4718e-2, 8.5116e-4), (2.9137e-2, 9.4596e-4), (2.6599e-2, 8.8594e-4))}
 ALIGN, NULL, SHAPE = -5, -1, -2
-
-
-def bits(x):
-    return x.contiguous().view(torch.uint8) if isinstance(x, torch.Tensor) else np.ascontiguousarray(x).view(np.uint8)
 
 
 def t32(a):

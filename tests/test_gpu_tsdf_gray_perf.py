@@ -11,18 +11,17 @@ formulation 6.048 ms (38x); the sampler at 480 x 640 0.020 ms beside the raycast
 (777 frames/s) against TsdfVolume.forward's 0.725 ms.  The same kernel with the intensity record loaded for every voxel
 (DESIGN.md, K22): 0.158 ms against 0.155 for the 4 frames, 0.098 against 0.065 for one."""
 import numpy as np
-import pytest
 import torch
 
 import photo_oracle as PO
 import tsdf_gray_oracle as GO
 import tsdf_oracle as TO
+from gpu_common import DEV, GPU_PERF, time_ms
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.pytorch_model.geometry import DirectTsdfVolume, TsdfVolume
 from onnx_image_processing_amd.synth import rgbd_camera, synth_depth_room
 
-pytestmark = [pytest.mark.gpu_perf, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU_PERF
 HEIGHT, WIDTH, FRAMES, SIDE = 480, 640, 4, 256
 BIG = ((SIDE, SIDE, SIDE), (-2.0, -2.6, 0.4), 0.015625, 0.0625)           # 4 m of room in 1.5625 cm voxels
 
@@ -58,21 +57,6 @@ def torch_integrate_gray(volume, intensity, depth, gray, r, t, cam, origin, voxe
         gry = torch.where(gkeep, (gry * gwt + g) / (gwt + 1), gry)
         gwt = torch.where(gkeep, torch.clamp(gwt + 1, max=max_weight), gwt)
     return tsdf, weight, gry, gwt
-
-
-def _time_ms(fn, iters=10, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        times.append(s.elapsed_time(e))
-    return float(np.median(times))
 
 
 def test_torch_formulation_computes_the_same_thing():
@@ -121,8 +105,8 @@ def test_hip_integrate_gray_beats_torch_on_gpu_for_4_frames_into_256_cubed():
         ops.tsdf_integrate(k19.volume, depth[None], r[None], t[None], cam, origin, vs, trunc, 64.0)
 
     state = (m.volume[0].clone(), m.intensity[0].clone())
-    hip, plain, one = _time_ms(hip_all), _time_ms(k19_all), _time_ms(hip_one)
-    ref = _time_ms(lambda: torch_integrate_gray(*state, depth, gray, r, t, cam, origin, vs, trunc, 64.0, 0.1, 10.0), iters=5, warmup=2)
+    hip, plain, one = time_ms(hip_all), time_ms(k19_all), time_ms(hip_one)
+    ref = time_ms(lambda: torch_integrate_gray(*state, depth, gray, r, t, cam, origin, vs, trunc, 64.0, 0.1, 10.0), iters=5, warmup=2)
     m.reset()
     k19.reset()
     hip_all()
@@ -131,16 +115,16 @@ def test_hip_integrate_gray_beats_torch_on_gpu_for_4_frames_into_256_cubed():
     band = float((m.intensity[..., 1] > 0).float().mean())
     assert band > 0.01 and float((m.volume[..., 1] > 0).float().mean()) > band          # the frames do land; the band is a part of it
     vertex = k19.raycast(r[:1], t[:1])[0]
-    sample = _time_ms(lambda: ops.tsdf_sample_gray(m.intensity, vertex, origin, vs, r[:1], t[:1]))
-    ray = _time_ms(lambda: k19.raycast(r[:1], t[:1]))
+    sample = time_ms(lambda: ops.tsdf_sample_gray(m.intensity, vertex, origin, vs, r[:1], t[:1]))
+    ray = time_ms(lambda: k19.raycast(r[:1], t[:1]))
     inten = ops.tsdf_sample_gray(m.intensity, vertex, origin, vs, r[:1], t[:1])
     hits = float((vertex[..., 3] != 0).float().mean())
     assert hits > 0.5 and torch.equal(inten[..., 3] != 0, vertex[..., 3] != 0)           # every hit has an intensity
     live = synth_depth_room(900, HEIGHT, WIDTH)
     live_d, live_g = torch.from_numpy(live[1])[None].to(DEV), torch.from_numpy(PO.render(*live)[1])[None].to(DEV)
     # the prediction is the truth of frame 1, not of the live frame: both trackers have a motion to find
-    whole = _time_ms(lambda: m(live_d, live_g, r[:1], t[:1]))
-    parent = _time_ms(lambda: k19(live_d, r[:1], t[:1]))
+    whole = time_ms(lambda: m(live_d, live_g, r[:1], t[:1]))
+    parent = time_ms(lambda: k19(live_d, r[:1], t[:1]))
     assert bool(m.track(live_d, live_g, r[:1], t[:1])[7].all())
     mb16, mb32 = SIDE ** 3 * 16 / 1e6, SIDE ** 3 * 32 / 1e6
     print(f"{FRAMES} frames of {HEIGHT} x {WIDTH} into {SIDE}^3: HIP integrate_gray {hip:.3f} ms ({mb16 / hip:.0f} GB/s against 16 bytes "

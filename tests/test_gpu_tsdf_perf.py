@@ -6,16 +6,15 @@ Measured on an MI355X: integrate 0.141 ms (1909 GB/s against the 268 MB) against
 (4255 GB/s); raycast at 480 x 640 0.170 ms, 1.81 G rays/s with 98 % of the rays hitting; forward (raycast, surfel maps, 15
 linearisations, compose, integrate) 0.709 ms, 1411 frames/s."""
 import numpy as np
-import pytest
 import torch
 
 import tsdf_oracle as TO
+from gpu_common import DEV, GPU_PERF, time_ms
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.pytorch_model.geometry import TsdfVolume
 from onnx_image_processing_amd.synth import rgbd_camera, synth_depth_room
 
-pytestmark = [pytest.mark.gpu_perf, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU_PERF
 HEIGHT, WIDTH, FRAMES, SIDE = 480, 640, 4, 256
 BIG = ((SIDE, SIDE, SIDE), (-2.0, -2.6, 0.4), 0.015625, 0.0625)           # 4 m of room in 1.5625 cm voxels
 BYTES_PER_VOXEL = 16                                                      # DESIGN.md, K19: 8 read, 8 written, per call
@@ -46,21 +45,6 @@ def torch_integrate(volume, depth, r, t, cam, origin, voxel_size, truncation, ma
         tsdf = torch.where(keep, (tsdf * weight + fv) / (weight + 1), tsdf)
         weight = torch.where(keep, torch.clamp(weight + 1, max=max_weight), weight)
     return tsdf, weight
-
-
-def _time_ms(fn, iters=10, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        times.append(s.elapsed_time(e))
-    return float(np.median(times))
 
 
 def test_torch_formulation_computes_the_same_thing():
@@ -96,16 +80,16 @@ def test_hip_integrate_beats_torch_on_gpu_for_4_frames_into_256_cubed():
         ops.tsdf_integrate(m.volume, depth[None, :1], r[None, :1], t[None, :1], cam, origin, vs, trunc, 64.0)
 
     state = m.volume[0].clone()
-    hip = _time_ms(hip_all)
-    one = _time_ms(hip_one)
-    ref = _time_ms(lambda: torch_integrate(state, depth, r, t, cam, origin, vs, trunc, 64.0, 0.1, 10.0), iters=5, warmup=2)
+    hip = time_ms(hip_all)
+    one = time_ms(hip_one)
+    ref = time_ms(lambda: torch_integrate(state, depth, r, t, cam, origin, vs, trunc, 64.0, 0.1, 10.0), iters=5, warmup=2)
     m.reset()
     hip_all()
     assert float((m.volume[..., 1] > 0).float().mean()) > 0.02                      # the frames do land in the volume
-    ray = _time_ms(lambda: m.raycast(r[:1], t[:1]))
+    ray = time_ms(lambda: m.raycast(r[:1], t[:1]))
     hits = float((m.raycast(r[:1], t[:1])[0][..., 3] != 0).float().mean())
     live = torch.from_numpy(synth_depth_room(900, HEIGHT, WIDTH)[1])[None].to(DEV)
-    whole = _time_ms(lambda: m(live, r[:1], t[:1]))
+    whole = time_ms(lambda: m(live, r[:1], t[:1]))
     assert bool(m.track(live, r[:1], t[:1])[5].all()) and hits > 0.5
     mbytes = SIDE ** 3 * BYTES_PER_VOXEL / 1e6
     print(f"{FRAMES} frames of {HEIGHT} x {WIDTH} into {SIDE}^3: HIP integrate {hip:.3f} ms ({mbytes / hip:.0f} GB/s of {mbytes:.0f} MB per "

@@ -1,14 +1,12 @@
 """K12 rate: the HIP voxel downsampling beats a torch-on-GPU formulation of the same operation (torch.unique with
 return_inverse + index_add_, one cloud at a time) on a batch of 16 depth-frame clouds (4 915 200 points, leaf 0.02)."""
-import numpy as np
-import pytest
 import torch
 
+from gpu_common import DEV, GPU_PERF, time_ms
 from onnx_image_processing_amd import ops
 from onnx_image_processing_amd.synth import synth_depth_cloud
 
-pytestmark = [pytest.mark.gpu_perf, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")]
-DEV = "cuda:0"
+pytestmark = GPU_PERF
 
 
 def torch_voxel(points: torch.Tensor, leaf: float):
@@ -27,27 +25,12 @@ def torch_voxel(points: torch.Tensor, leaf: float):
     return out, torch.arange(n, device=points.device) < m
 
 
-def _time_ms(fn, iters=10, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        times.append(s.elapsed_time(e))
-    return float(np.median(times))
-
-
 def test_hip_path_beats_torch_on_gpu_for_sixteen_frames():
     clouds = [torch.from_numpy(synth_depth_cloud(300 + i)).to(DEV) for i in range(16)]
     packed = torch.cat(clouds)
     offs = torch.tensor([0] + [c.shape[0] for c in clouds], dtype=torch.int64).cumsum(0).to(DEV)
     leaf = torch.full((16,), 0.02, dtype=torch.float32, device=DEV)
-    hip = _time_ms(lambda: ops.voxel_downsample_batch(packed, leaf, offsets=offs))
-    ref = _time_ms(lambda: [torch_voxel(c, 0.02) for c in clouds])
+    hip = time_ms(lambda: ops.voxel_downsample_batch(packed, leaf, offsets=offs))
+    ref = time_ms(lambda: [torch_voxel(c, 0.02) for c in clouds])
     print(f"16 frames: HIP {hip:.3f} ms, torch-on-GPU {ref:.3f} ms ({ref / hip:.1f}x)")
     assert hip < ref

@@ -8,7 +8,6 @@ asserted against the constants so that neither can drift from the other."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,6 +16,7 @@ import torch
 import homography_oracle as HO
 import pose_oracle as PO
 import test_gpu_homography as G
+from helpers import SANITIZE, build_host, host_program, run_host
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd.synth import synth_planar_two_view, two_view_camera
 
@@ -271,25 +271,8 @@ def test_essential_matrix_is_confidently_wrong_on_planar_scenes_and_the_homograp
 
 
 # ---- the kernels' arithmetic on the host ---------------------------------------------------------------------------------------
-def _build(tmp, name, extra):
-    from onnx_image_processing_amd.build import FLAGS, _hipcc
-    exe = str(tmp / name)
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "homography_host.cpp")
-    flags = [f for f in FLAGS if f not in ("-fPIC", "-fvisibility=hidden", "-O3")]
-    r = subprocess.run([_hipcc(), *flags, "-O1", *extra, "-x", "hip", src, "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
-
-
-@pytest.fixture(scope="module")
-def hg_host(tmp_path_factory):
-    """tests/native/homography_host.cpp: the kernels' own sampler, solver, score and decomposition, compiled for the host"""
-    return _build(tmp_path_factory.mktemp("homography_host"), "homography_host", [])
-
-
-def _run(exe, mode, text=""):
-    out = subprocess.run([exe, mode], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
-    return [ln.split() for ln in out if ln]
+# tests/native/homography_host.cpp: the kernels' own sampler, solver, score and decomposition, compiled for the host
+hg_host = host_program("homography_host.cpp", hip=True)
 
 
 def _rows(a, b):
@@ -297,7 +280,7 @@ def _rows(a, b):
 
 
 def test_native_sampler_is_the_oracles(hg_host):
-    rows = [tuple(map(int, f)) for f in _run(hg_host, "ranks")]
+    rows = [tuple(map(int, f)) for f in run_host(hg_host, "ranks")]
     assert len(rows) == 4 * 50
     for seed, b, h, nv, r0, r1, r2, r3 in rows:
         assert HO.sample_ranks(seed, b, h, nv) == [r0, r1, r2, r3], (h, nv)
@@ -324,7 +307,7 @@ def test_native_solver_score_and_decomposition_match_the_oracle(hg_host):
     """the host build of csrc/homography_math.h next to the oracle's float32 run: the same refusals, and a deviation from the
     float64 oracle within 4 times the float32 run's own (values), 2 times (angles)"""
     samples = _solve_samples()
-    out = _run(hg_host, "solve", "\n".join(_rows(a, b) for a, b in samples))
+    out = run_host(hg_host, "solve", "\n".join(_rows(a, b) for a, b in samples))
     assert len(out) == len(samples)
     dev_native, dev_f32, solved = [], [], 0
     for i, (a, b) in enumerate(samples):
@@ -348,7 +331,7 @@ def test_native_solver_score_and_decomposition_match_the_oracle(hg_host):
     m32 = HO.solve_minimal(*first, F)
     a, b = p1[0].copy(), p2[0].copy()
     a[5] = -40 * a[5] + 3                                                   # far outside the image
-    got = np.array([float(x[0]) for x in _run(hg_host, "score", " ".join("%.9g" % x for x in m32) + "\n" + _rows(a, b))])
+    got = np.array([float(x[0]) for x in run_host(hg_host, "score", " ".join("%.9g" % x for x in m32) + "\n" + _rows(a, b))])
     w64, w32 = HO.dist2(m32.astype(D), a.astype(D), b.astype(D)), HO.dist2(m32, a, b)
     assert np.array_equal(np.isinf(got), np.isinf(w64)) and np.array_equal(np.isinf(w32), np.isinf(w64))
     fin = np.isfinite(w64)
@@ -363,7 +346,7 @@ def test_native_solver_score_and_decomposition_match_the_oracle(hg_host):
             Hn, mask, _, _, _ = HO.ransac(q1[i], q2[i], None, G.POSE_H, THR, 3, G.POSE_SEED, i, F)
             text.append(f"{mask.sum()}\n" + " ".join("%.9g" % x for x in Hn.ravel()) + "\n" + _rows(q1[i][mask], q2[i][mask]))
             cases.append((Hn, q1[i][mask], q2[i][mask], baseline))
-    out = _run(hg_host, "pose", "\n".join(text))
+    out = run_host(hg_host, "pose", "\n".join(text))
     assert len(out) == 5 * len(cases)
     rot_n = rot_o = t_n = t_o = 0.0
     for i, (Hn, a, b, baseline) in enumerate(cases):
@@ -391,13 +374,12 @@ G_ROT_DEV_BOUND = _rotation_tol() / 4         # the deviation of w1 - w3 the con
 
 def test_native_harness_under_the_host_sanitizers(tmp_path):
     """the same stand-alone program built with the host's address and undefined-behaviour sanitizers, run once over every mode"""
-    exe = _build(tmp_path, "homography_host_san", ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-g"])
+    exe = build_host(tmp_path, "homography_host.cpp", hip=True, extra=SANITIZE)
     samples = _solve_samples()
     for mode, text in (("ranks", ""), ("solve", "\n".join(_rows(a, b) for a, b in samples)),
                        ("score", " ".join(["0.25"] * 18) + "\n" + _rows(*samples[0])),
                        ("pose", "4\n1 0 0.01 0 1 0.02 0 0 1\n" + _rows(*samples[0]) + "\n0\n0 0 0 0 0 0 0 0 0")):
-        r = subprocess.run([exe, mode], input=text, capture_output=True, text=True)
-        assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, (mode, r.stderr[-2000:])
+        run_host(exe, mode, text)
 
 
 # ---- the measurements behind the constants -----------------------------------------------------------------------------------------

@@ -11,14 +11,13 @@ for bit.  The oracle's fixed point: refined from the truth at (48, 64), seeds 0 
 deg and 1.6994e-3 m of the truth (the bias of crease and sphere normals, tests/test_gpu_icp.py) and within 1e-9 of its own
 result from identity."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import icp_oracle as IO
+from helpers import host_program, run_records as run
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd.synth import rgbd_camera, synth_depth_room
 
@@ -216,24 +215,8 @@ def test_oracle_degenerate_scenes():
 
 # ---- the kernels' arithmetic on the host ----------------------------------------------------------------------------------------
 
-@pytest.fixture(scope="module")
-def icp_host(tmp_path_factory):
-    """tests/native/icp_host.cpp around csrc/icp_math.h, compiled as plain C++ (no HIP)"""
-    from onnx_image_processing_amd.build import _hipcc
-    exe = str(tmp_path_factory.mktemp("icp_host") / "icp_host")
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "icp_host.cpp")
-    r = subprocess.run([_hipcc(), "-x", "c++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", src, "-o", exe, "-lm"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
-
-
-def run(exe, mode, records):
-    text = "\n".join(" ".join("%.17g" % float(x) for x in rec) for rec in records)
-    out = subprocess.run([exe, mode], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
-    out = [np.array(ln.split(), F64) for ln in out if ln]
-    assert len(out) == len(records)
-    return out
+# tests/native/icp_host.cpp around csrc/icp_math.h, compiled as plain C++ (no HIP)
+icp_host = host_program("icp_host.cpp", hip=False)
 
 
 def test_native_solve_matches_the_oracle(icp_host):

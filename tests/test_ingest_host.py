@@ -4,13 +4,12 @@ layers' refusal of CPU tensors and bad arguments; the `pytorch_model.ingest` ali
 frame; and the oracle's own sanity (identity at equal sizes, constants stay constant, < 1 gray level from a float64
 bilinear resize)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import helpers
 import ingest_oracle as IO
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd import ops
@@ -20,22 +19,14 @@ NULL, SHAPE, PARAM = -1, -2, -3
 BGR, RGB = 0, 1
 
 
-@pytest.fixture(scope="module")
-def ingest_host(tmp_path_factory):
-    """tests/native/ingest_host.cpp: frames ingested on the host by the kernel's own per-pixel functions"""
-    from onnx_image_processing_amd.build import FLAGS, _hipcc
-    exe = str(tmp_path_factory.mktemp("ingest_host") / "ingest_host")
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "ingest_host.cpp")
-    flags = [f for f in FLAGS if f not in ("-fPIC", "-fvisibility=hidden", "-O3")]
-    r = subprocess.run([_hipcc(), *flags, "-O1", "-x", "hip", src, "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+# tests/native/ingest_host.cpp: frames ingested on the host by the kernel's own per-pixel functions
+ingest_host = helpers.host_program("ingest_host.cpp", hip=True)
 
 
 def run_host(exe, frames, height, width, channel_order):
     b, hs, ws, c = frames.shape
     head = f"{b} {hs} {ws} {c} {int(channel_order == 'rgb')} {height} {width}\n".encode()
-    out = subprocess.run([exe], input=head + np.ascontiguousarray(frames).tobytes(), capture_output=True, check=True).stdout
+    out = helpers.run_host(exe, [], head + np.ascontiguousarray(frames).tobytes(), binary=True)
     return np.frombuffer(out, np.uint8).reshape(b, 1, height, width)
 
 

@@ -14,8 +14,6 @@ icp_oracle.refine is frozen at step 0 on every seed; the joint oracle applies al
   (120, 160): 5.524e-4 / 2.389e-4 / 3.816e-4 deg and 2.474e-5 / 1.517e-5 / 5.606e-6 m
 with its smallest pivot ratio 1.2e-2.  tests/test_gpu_direct_rgbd.py builds on these."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -23,6 +21,7 @@ import torch
 
 import icp_oracle as IO
 import photo_oracle as PO
+from helpers import host_program, run_records as run
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd.synth import rgbd_camera
 
@@ -188,24 +187,8 @@ def test_module_constructor_and_cpu_refusal():
 
 # ---- the kernels' arithmetic on the host ----------------------------------------------------------------------------------------
 
-@pytest.fixture(scope="module")
-def photo_host(tmp_path_factory):
-    """tests/native/photo_host.cpp around csrc/photo_math.h, compiled as plain C++ (no HIP)"""
-    from onnx_image_processing_amd.build import _hipcc
-    exe = str(tmp_path_factory.mktemp("photo_host") / "photo_host")
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "photo_host.cpp")
-    r = subprocess.run([_hipcc(), "-x", "c++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", src, "-o", exe, "-lm"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
-
-
-def run(exe, mode, records):
-    text = "\n".join(" ".join("%.17g" % float(x) for x in rec) for rec in records)
-    out = subprocess.run([exe, mode], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
-    out = [np.array(ln.split(), F64) for ln in out if ln]
-    assert len(out) == len(records)
-    return out
+# tests/native/photo_host.cpp around csrc/photo_math.h, compiled as plain C++ (no HIP)
+photo_host = host_program("photo_host.cpp", hip=False)
 
 
 def bits(a):

@@ -6,8 +6,6 @@ conditions of the end-to-end GPU test of tests/test_gpu_place.py asserted on the
 oracle for the inlier bound."""
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,6 +13,7 @@ import torch
 
 import place_oracle as PO
 import test_gpu_place as G
+from helpers import SANITIZE, build_host, host_program, run_host
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd.synth import synth_place_descriptors
 
@@ -61,25 +60,7 @@ def test_select_oracle_on_a_worked_example():
 
 
 # ---- the kernels' arithmetic on the host -----------------------------------------------------------------------------------------
-def _build(tmp, name, extra):
-    from onnx_image_processing_amd.build import FLAGS, _hipcc
-    exe = str(tmp / name)
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "place_host.cpp")
-    flags = [f for f in FLAGS if f not in ("-fPIC", "-fvisibility=hidden", "-O3")]
-    r = subprocess.run([_hipcc(), *flags, "-O1", *extra, "-x", "hip", src, "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
-
-
-@pytest.fixture(scope="module")
-def place_host(tmp_path_factory):
-    return _build(tmp_path_factory.mktemp("place_host"), "place_host", [])
-
-
-def _run(exe, mode, text):
-    r = subprocess.run([exe, mode], input=text, capture_output=True, text=True)
-    assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, (mode, r.stderr[-2000:])
-    return [ln.split() for ln in r.stdout.split("\n") if ln]
+place_host = host_program("place_host.cpp", hip=True)
 
 
 def _merge_sets():
@@ -121,7 +102,7 @@ def _merge_expected(sets):
 
 def test_native_pair_merge_in_every_order_gives_the_scan(place_host):
     sets = _merge_sets()
-    out = _run(place_host, "merge", _merge_text(sets))
+    out = run_host(place_host, "merge", _merge_text(sets))
     assert len(out) == len(sets) == 20
     for got, want in zip(out, _merge_expected(sets)):
         assert [int(v) for v in got] == want
@@ -138,7 +119,7 @@ def _vote_rows():
 
 def test_native_vote_predicate(place_host):
     rows = _vote_rows()
-    out = _run(place_host, "vote", "\n".join("%d %d %d %.9g" % r for r in rows))
+    out = run_host(place_host, "vote", "\n".join("%d %d %d %.9g" % r for r in rows))
     want = [int(PO._vote(d1, d2, md, ratio)) for d1, d2, md, ratio in rows]
     assert [int(ln[0]) for ln in out] == want and want[:4] == [0, 1, 1, 0] and 20 < sum(want) < 200
 
@@ -152,7 +133,7 @@ def _key_rows():
 
 def test_native_selection_key_orders_like_the_oracle(place_host):
     votes, index = _key_rows()
-    out = _run(place_host, "key", "\n".join(f"{v} {i}" for v, i in zip(votes, index)))
+    out = run_host(place_host, "key", "\n".join(f"{v} {i}" for v, i in zip(votes, index)))
     keys = [int(ln[0]) for ln in out]
     assert [(int(ln[1]), int(ln[2])) for ln in out] == list(zip(votes.tolist(), index.tolist())) and min(keys) > 0
     order = sorted(range(len(keys)), key=lambda r: -keys[r])
@@ -161,11 +142,11 @@ def test_native_selection_key_orders_like_the_oracle(place_host):
 
 def test_native_harness_under_the_host_sanitizers(tmp_path):
     """the same stand-alone program built with the host's address and undefined-behaviour sanitizers, run once over every mode"""
-    exe = _build(tmp_path, "place_host_san", ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-g"])
-    assert len(_run(exe, "merge", _merge_text(_merge_sets()))) == 20
-    assert len(_run(exe, "vote", "\n".join("%d %d %d %.9g" % r for r in _vote_rows()))) == 214
+    exe = build_host(tmp_path, "place_host.cpp", hip=True, extra=SANITIZE)
+    assert len(run_host(exe, "merge", _merge_text(_merge_sets()))) == 20
+    assert len(run_host(exe, "vote", "\n".join("%d %d %d %.9g" % r for r in _vote_rows()))) == 214
     votes, index = _key_rows()
-    assert len(_run(exe, "key", "\n".join(f"{v} {i}" for v, i in zip(votes, index)))) == 65
+    assert len(run_host(exe, "key", "\n".join(f"{v} {i}" for v, i in zip(votes, index)))) == 65
 
 
 # ---- argument checks -------------------------------------------------------------------------------------------------------------

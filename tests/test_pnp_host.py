@@ -16,8 +16,6 @@ project's margins (2 for angles, 4 for values):
     TRUTH_T_M = 4.73e-5 + 4 * 4.15e-3 = 1.7e-2.
   The float64 oracle misses the truth (no candidate within 1e-2 deg) on 0 of the 192 samples: none excluded (cap: 2 %)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -26,6 +24,7 @@ import torch
 import pose_oracle as PO
 import pnp_oracle as QO
 import rigid_oracle as RO
+from helpers import host_program, run_host
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd.synth import rgbd_camera
 
@@ -278,16 +277,8 @@ def test_polish_steps_are_justified(planted):
 
 
 # ---- the kernels' arithmetic on the host ---------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def pnp_host(tmp_path_factory):
-    """tests/native/pnp_host.cpp: the kernels' own sampler and P3P solver, compiled for the host"""
-    from onnx_image_processing_amd.build import FLAGS, _hipcc
-    exe = str(tmp_path_factory.mktemp("pnp_host") / "pnp_host")
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "pnp_host.cpp")
-    flags = [f for f in FLAGS if f not in ("-fPIC", "-fvisibility=hidden", "-O3")]
-    r = subprocess.run([_hipcc(), *flags, "-O1", "-x", "hip", src, "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+# tests/native/pnp_host.cpp: the kernels' own sampler and P3P solver, compiled for the host
+pnp_host = host_program("pnp_host.cpp", hip=True)
 
 
 def _rows(X, uv):
@@ -298,13 +289,8 @@ def _bits(x):
     return np.asarray(x, F).view(np.uint32)
 
 
-def _run(exe, mode, text=""):
-    out = subprocess.run([exe, mode], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
-    return [ln.split() for ln in out if ln]
-
-
 def test_native_sampler_is_the_oracles(pnp_host):
-    rows = [tuple(map(int, f)) for f in _run(pnp_host, "ranks")]
+    rows = [tuple(map(int, f)) for f in run_host(pnp_host, "ranks")]
     assert len(rows) == 4 * 50
     for seed, b, h, nv, r0, r1, r2, r3 in rows:
         assert QO.sample_ranks(seed, b, h, nv) == [r0, r1, r2, r3], (h, nv)
@@ -324,7 +310,7 @@ def native_solve(pnp_host, planted):
     samples.append((line, samples[0][1]))                                   # collinear model points
     samples.append((samples[0][0], np.repeat(samples[0][1][:1], 4, axis=0)))  # one bearing four times
     samples.append((samples[0][0], -samples[0][1]))                         # mirrored pixels: whatever comes must agree
-    out = _run(pnp_host, "solve", "\n".join(_rows(X, uv) for X, uv in samples))
+    out = run_host(pnp_host, "solve", "\n".join(_rows(X, uv) for X, uv in samples))
     assert len(out) == 5 * len(samples)
     return samples, out
 
@@ -382,7 +368,7 @@ def test_native_score_and_jacobian_lines_return_the_restatements_bits(pnp_host):
     rt = np.concatenate([Rs[0].ravel(), ts[0]]).astype(F)
     X[5] = -X[5]                                                            # behind the camera
     text = " ".join("%.9g" % x for x in rt) + "\n" + _rows(X, uv)
-    score, lines = _run(pnp_host, "score", text), _run(pnp_host, "lines", text)
+    score, lines = run_host(pnp_host, "score", text), run_host(pnp_host, "lines", text)
     assert len(score) == len(lines) == 64
     with np.errstate(all="ignore"):
         for i in range(64):

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import pose_oracle as PO
+from helpers import host_program, run_host
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd.synth import synth_two_view, two_view_camera
 
@@ -217,24 +218,12 @@ def test_oracle_degenerate_cases():
     assert PO.recover_pose(np.zeros((3, 3)), p1, p2, None)[4] is False
 
 
-@pytest.fixture(scope="module")
-def pose_host(tmp_path_factory):
-    """tests/native/pose_host.cpp: the kernels' own sampler hash and minimal solver, compiled for the host"""
-    import os
-    import subprocess
-    from onnx_image_processing_amd.build import FLAGS, _hipcc
-    exe = str(tmp_path_factory.mktemp("pose_host") / "pose_host")
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "pose_host.cpp")
-    flags = [f for f in FLAGS if f not in ("-fPIC", "-fvisibility=hidden", "-O3")]
-    r = subprocess.run([_hipcc(), *flags, "-O1", "-x", "hip", src, "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+# tests/native/pose_host.cpp: the kernels' own sampler hash and minimal solver, compiled for the host
+pose_host = host_program("pose_host.cpp", hip=True)
 
 
 def test_native_sampler_hash_is_the_oracles(pose_host):
-    import subprocess
-    lines = subprocess.run([pose_host, "draws"], capture_output=True, text=True, check=True).stdout.split("\n")
-    rows = [tuple(map(int, ln.split())) for ln in lines if ln]
+    rows = [tuple(map(int, ln)) for ln in run_host(pose_host, "draws")]
     assert len(rows) == 3 * 3 * 4 * 8
     for seed, b, h, s, v in rows:
         assert PO.draw(seed, b, h, s) == v, (seed, b, h, s)
@@ -244,7 +233,6 @@ def test_native_minimal_solver_matches_the_oracle(pose_host):
     """the solver the hypothesis kernel runs per lane (Gauss-Jordan with complete pivoting on the strided work area,
     denormalisation, projection), on the host: on 3 noisy scenes x 64 samples its E has the fp64 oracle's inlier count to
     within 1 on >= 90 % of the samples (the GPU suite's cap), and degenerate samples are refused"""
-    import subprocess
     samples, meta = [], []
     for b, seed in enumerate((100, 101, 102)):
         k1, k2, _, _, _ = synth_two_view(seed, 64, 0.25, 0.5)
@@ -256,8 +244,7 @@ def test_native_minimal_solver_matches_the_oracle(pose_host):
     samples.append(np.concatenate([np.repeat(p1[:1], 8, 0), p2[:8]], axis=1))                        # zero spread
     samples.append(np.concatenate([np.tile(p1[:4], (2, 1)), np.tile(p2[:4], (2, 1))], axis=1))       # rank 4
     text = "\n".join(" ".join("%.9g" % x for x in row) for smp in samples for row in smp)
-    out = subprocess.run([pose_host, "solve"], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
-    out = [ln.split() for ln in out if ln]
+    out = run_host(pose_host, "solve", text)
     assert len(out) == len(samples)
     assert out[-1][0] == "0" and out[-2][0] == "0" and not any(float(x) for x in out[-1][1:] + out[-2][1:])
     thr = 1.0 / 500
@@ -279,7 +266,6 @@ def test_native_pose_decomposition_and_depth_test_match_the_oracle(pose_host):
     """po_decompose + po_in_front on the host: for the true E (and -E) of six scenes the candidate the oracle selects holds
     the true R, t (0.01 deg: ~100 float32 roundings) and every row passes under it; the four candidates all occur; a zero
     matrix is refused"""
-    import subprocess
     text, truth = [], []
     for seed in range(6):
         k1, k2, R, t, _ = synth_two_view(seed, 32, 0.0, 0.0)
@@ -290,8 +276,7 @@ def test_native_pose_decomposition_and_depth_test_match_the_oracle(pose_host):
             text += [" ".join("%.9g" % x for x in row) for row in np.concatenate([p1, p2], axis=1)]
             truth.append((E, p1, p2, R, t))
     text.append("0 0 0 0 0 0 0 0 0 50 0")
-    out = subprocess.run([pose_host, "pose"], input="\n".join(text), capture_output=True, text=True, check=True).stdout.split("\n")
-    out = [ln.split() for ln in out if ln]
+    out = run_host(pose_host, "pose", "\n".join(text))
     assert len(out) == 13 and out[-1][0] == "0" and out[-1][-4:] == ["0", "0", "0", "0"]
     cands = set()
     for (E, p1, p2, R, t), f in zip(truth, out):
@@ -307,7 +292,6 @@ def test_native_pose_decomposition_and_depth_test_match_the_oracle(pose_host):
 def test_native_triangulation_matches_the_oracle(pose_host):
     """po_triangulate_point on the host against the oracle's SVD DLT: 9e-6 relative on points with >= 1 deg of parallax (4 x
     the float32 oracle's own 2.2e-6, as in the GPU suite); identical rays under identical cameras are not finite"""
-    import subprocess
     k1, k2, R, t, _ = synth_two_view(300, 97, 0.0, 0.5)
     P1 = (K @ np.hstack([np.eye(3), np.zeros((3, 1))])).astype(np.float32)
     P2 = (K @ np.hstack([R, 0.4 * t[:, None]])).astype(np.float32)
@@ -316,8 +300,7 @@ def test_native_triangulation_matches_the_oracle(pose_host):
     def run(pa, pb, xa, xb):
         text = " ".join("%.9g" % v for v in np.concatenate([pa.ravel(), pb.ravel()])) + f" {len(xa)}\n"
         text += "\n".join(" ".join("%.9g" % v for v in row) for row in np.concatenate([xa, xb], axis=1))
-        out = subprocess.run([pose_host, "tri"], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
-        a = np.array([ln.split() for ln in out if ln], float)
+        a = np.array(run_host(pose_host, "tri", text), float)
         return a[:, 1:], a[:, 0] == 1
     got, fin = run(P1, P2, x1, x2)
     ref, rfin = PO.triangulate(P1, P2, x1, x2)

@@ -8,8 +8,6 @@ run in float32 deviates from its float64 run by at most 3.07e-4 deg in rotation 
 margins of the GPU suites (2 for angles, 4 for values) -> SOLVE_ROT_DEG = 6.2e-4, SOLVE_T_M = 1.6e-4.  The kernels'
 arithmetic measured 3.46e-4 deg and 4.4e-5 m."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,6 +15,7 @@ import torch
 
 import pose_oracle as PO
 import rigid_oracle as RO
+from helpers import host_program, run_host
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd.synth import rgbd_camera, synth_rgbd_pair, two_view_camera
 
@@ -228,16 +227,8 @@ def test_oracle_degenerate_cases():
     assert RO.refit(line8, line8 @ R.T + t, np.ones(8, bool))[2] is False
 
 
-@pytest.fixture(scope="module")
-def rigid_host(tmp_path_factory):
-    """tests/native/rigid_host.cpp: the kernels' own sampler and Horn solver, compiled for the host"""
-    from onnx_image_processing_amd.build import FLAGS, _hipcc
-    exe = str(tmp_path_factory.mktemp("rigid_host") / "rigid_host")
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "rigid_host.cpp")
-    flags = [f for f in FLAGS if f not in ("-fPIC", "-fvisibility=hidden", "-O3")]
-    r = subprocess.run([_hipcc(), *flags, "-O1", "-x", "hip", src, "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+# tests/native/rigid_host.cpp: the kernels' own sampler and Horn solver, compiled for the host
+rigid_host = host_program("rigid_host.cpp", hip=True)
 
 
 def _rows(a, b):
@@ -245,13 +236,11 @@ def _rows(a, b):
 
 
 def test_native_sampler_is_the_oracles(rigid_host):
-    lines = subprocess.run([rigid_host, "draws"], capture_output=True, text=True, check=True).stdout.split("\n")
-    rows = [tuple(map(int, ln.split())) for ln in lines if ln]
+    rows = [tuple(map(int, ln)) for ln in run_host(rigid_host, "draws")]
     assert len(rows) == 3 * 3 * 4 * 3
     for seed, b, h, s, v in rows:
         assert PO.draw(seed, b, h, s) == v, (seed, b, h, s)
-    lines = subprocess.run([rigid_host, "ranks"], capture_output=True, text=True, check=True).stdout.split("\n")
-    rows = [tuple(map(int, ln.split())) for ln in lines if ln]
+    rows = [tuple(map(int, ln)) for ln in run_host(rigid_host, "ranks")]
     assert len(rows) == 4 * 50
     for seed, b, h, nv, r0, r1, r2 in rows:
         assert RO.sample_ranks(seed, b, h, nv) == [r0, r1, r2], (h, nv)
@@ -273,8 +262,7 @@ def test_native_minimal_solver_matches_the_oracle(rigid_host):
     samples.append(_rows(line, meta[0][1]))                                 # collinear in frame 1
     samples.append(_rows(meta[0][0], line))                                 # collinear in frame 2
     samples.append(_rows(meta[0][0][[0, 0, 1]], meta[0][1][[0, 0, 1]]))     # a repeated point
-    out = subprocess.run([rigid_host, "solve"], input="\n".join(samples), capture_output=True, text=True, check=True).stdout.split("\n")
-    out = [ln.split() for ln in out if ln]
+    out = run_host(rigid_host, "solve", "\n".join(samples))
     assert len(out) == len(samples)
     for f in out[-3:]:
         assert f[0] == "0" and not any(float(x) for x in f[1:])
@@ -300,8 +288,7 @@ def test_native_fit_refuses_collinear_sets_and_matches_the_oracle(rigid_host):
     a, b = x1[0][inl[0]], x2[0][inl[0]]
     line = (np.outer(np.arange(8.0), [1.0, 2.0, 0.5]) + [0.3, -0.2, 4.0]).astype(np.float32)
     text = "\n".join([f"{len(a)}", _rows(a, b), "8", _rows(line, (line @ R[0].T + t[0]).astype(np.float32)), "2", _rows(a[:2], b[:2])])
-    out = subprocess.run([rigid_host, "fit"], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
-    out = [ln.split() for ln in out if ln]
+    out = run_host(rigid_host, "fit", text)
     assert len(out) == 3 and out[0][0] == "1" and out[1][0] == "0" and out[2][0] == "0"
     got = np.array(out[0][1:], np.float64)
     assert PO.rotation_angle_deg(got[:9].reshape(3, 3), R[0]) < 1e-3 and RO.translation_error(got[9:12], t[0]) < 1e-4

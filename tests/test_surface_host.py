@@ -11,8 +11,6 @@ uses every vertex, and its vertices lie within 6.0128e-2 voxel of the sphere (li
 area, still closed and of Euler characteristic 2.  On the fused rooms the float32 and float64 runs give the counts of COUNTS
 and identical triangles: a condition on the scenes, not a tolerance."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -20,6 +18,7 @@ import torch
 
 import surface_oracle as SO
 import tsdf_oracle as TO
+from helpers import host_program, run_host, run_records
 from onnx_image_processing_amd import _native as N
 
 NULL, SHAPE, PARAM, CAPACITY, ALIGN = -1, -2, -3, -4, -5
@@ -104,42 +103,25 @@ def test_oracle_float32_and_float64_agree_on_the_fused_rooms(name, h, w):
 
 # ---- the kernels' arithmetic on the host ----------------------------------------------------------------------------------------
 
-@pytest.fixture(scope="module")
-def surface_host(tmp_path_factory):
-    """tests/native/surface_host.cpp around csrc/surface_math.h, compiled as plain C++ (no HIP)"""
-    from onnx_image_processing_amd.build import _hipcc
-    exe = str(tmp_path_factory.mktemp("surface_host") / "surface_host")
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "surface_host.cpp")
-    r = subprocess.run([_hipcc(), "-x", "c++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", src, "-o", exe, "-lm"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
-
-
-def run(exe, args, records):
-    text = "\n".join(" ".join("%.17g" % float(x) for x in rec) for rec in records)
-    out = subprocess.run([exe, *args], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
-    out = [np.array(ln.split(), F64) for ln in out if ln]
-    assert len(out) == len(records)
-    return np.array(out)
+# tests/native/surface_host.cpp around csrc/surface_math.h, compiled as plain C++ (no HIP)
+surface_host = host_program("surface_host.cpp", hip=False)
 
 
 def test_native_table_is_the_oracles(surface_host):
-    out = subprocess.run([surface_host, "table"], capture_output=True, text=True, check=True).stdout.split("\n")
-    rows = np.array([ln.split() for ln in out if ln], np.int64)
+    rows = np.array(run_host(surface_host, "table"), np.int64)
     assert rows.shape == (96, 3) and np.array_equal(rows[:, 0], np.repeat(np.arange(6), 16)) and np.array_equal(rows[:, 1], np.tile(np.arange(16), 6))
     assert np.array_equal(rows[:, 2].reshape(6, 16), SO.packed_table().astype(np.int64))
 
 
 def test_native_bits_and_cells_are_the_oracles(surface_host):
     recs = [[t, w, mw] for t in (-1.0, -0.0, 0.0, 1e-30, 1.0, NAN) for w in (0.0, 0.5, 1.0, 2.0, NAN) for mw in (0.5, 1.0, 2.0)]
-    out = run(surface_host, ["bits"], recs)[:, 0]
+    out = np.array(run_records(surface_host, "bits", recs))[:, 0]
     for (t, w, mw), got in zip(recs, out):
         obs = w >= mw
         assert got == (1 if obs else 0) + (2 if obs and not t > 0 else 0), (t, w, mw)
     # every (observed, inside) pair of a cell's eight corners, inside implying observed
     pairs = [(o, n) for o in range(256) for n in range(256) if n & ~o == 0]
-    out = run(surface_host, ["cell"], pairs).astype(np.int64)
+    out = np.array(run_records(surface_host, "cell", pairs)).astype(np.int64)
     table = SO.triangle_table()
     for (o, n), got in zip(pairs, out):
         edges = sum(1 << e for e in range(1, 8) if (o & 1) and (o >> e) & 1 and ((n & 1) != ((n >> e) & 1)))
@@ -160,7 +142,7 @@ def test_native_vertex_and_normal_are_the_float32_oracles(surface_host, tmp_path
         np.stack(vol, axis=-1).astype(F32).tofile(path)
         mesh = SO.extract(vol, grid, dtype=F32)
         assert mesh["counts"][0] > 0
-        out = run(surface_host, ["vertex", path, str(nx), str(ny), str(nz)], [[*o, *grid[0], grid[1]] for o in mesh["owner"]])
+        out = np.array(run_records(surface_host, ["vertex", path, str(nx), str(ny), str(nz)], [[*o, *grid[0], grid[1]] for o in mesh["owner"]]))
         assert np.array_equal(out[:, 0].astype(F32).view(np.uint32), mesh["alpha"].view(np.uint32))
         assert np.array_equal(out[:, 1:4].astype(F32).view(np.uint32), mesh["vertices"].view(np.uint32))
         assert np.array_equal(out[:, 4].astype(bool), mesh["normal_ok"])

@@ -23,6 +23,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import native_lib
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "threshold.npz")
 F32 = np.float32
@@ -210,16 +212,9 @@ def test_value_errors():
     assert ops.multi_otsu_combinations(33, 5) == math.comb(32, 4)
 
 
-def _lib():
-    from onnx_image_processing_amd.build import build
-    from onnx_image_processing_amd import _native
-    build(verbose=False)
-    return _native.load()
-
-
 def test_argument_errors_before_any_launch():
     """MI_E_* from the host checks (no GPU is touched: these return before the first launch)."""
-    lib = _lib()
+    lib = native_lib()
     buf = ctypes.create_string_buffer(1 << 12)
     p = ctypes.c_void_p((ctypes.addressof(buf) + 255) // 256 * 256)
     odd1, odd2, odd4 = (ctypes.c_void_p(p.value + k) for k in (1, 2, 4))

@@ -18,8 +18,6 @@ from the float64 run (deg, m):
 Every raycast hit gets an intensity (0.902 of the pixels at (48, 64), 0.912 at (120, 160)); its median deviation from the frame
 that was fused is 1.689 and 1.104 gray levels."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -29,6 +27,7 @@ import icp_oracle as IO
 import photo_oracle as PO
 import tsdf_gray_oracle as GO
 import tsdf_oracle as TO
+from helpers import host_program, run_records as run
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd.synth import rgbd_camera
 
@@ -269,24 +268,8 @@ def test_oracle_direct_tracking_moves_where_k19_is_frozen(h, w, seed):
 
 # ---- the kernels' arithmetic on the host ----------------------------------------------------------------------------------------
 
-@pytest.fixture(scope="module")
-def gray_host(tmp_path_factory):
-    """tests/native/tsdf_gray_host.cpp around csrc/tsdf_gray_math.h, compiled as plain C++ (no HIP)"""
-    from onnx_image_processing_amd.build import _hipcc
-    exe = str(tmp_path_factory.mktemp("tsdf_gray_host") / "tsdf_gray_host")
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "tsdf_gray_host.cpp")
-    r = subprocess.run([_hipcc(), "-x", "c++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", src, "-o", exe, "-lm"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
-
-
-def run(exe, args, records):
-    text = "\n".join(" ".join("%.17g" % float(x) for x in rec) for rec in records)
-    out = subprocess.run([exe, *args], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
-    out = [np.array(ln.split(), F64) for ln in out if ln]
-    assert len(out) == len(records)
-    return out
+# tests/native/tsdf_gray_host.cpp around csrc/tsdf_gray_math.h, compiled as plain C++ (no HIP)
+gray_host = host_program("tsdf_gray_host.cpp", hip=False)
 
 
 def same(a, b):

@@ -12,8 +12,6 @@ rounds the corner); frame-to-model refinement of the unseen second views of seed
 is ok and ends within 5.5812e-2 deg / 1.2172e-3 m and 4.6397e-2 deg / 1.0879e-3 m of the truth (frame-to-frame K18 at this
 size: 5.2624e-2 deg, tests/test_icp_host.py)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -21,6 +19,7 @@ import torch
 
 import icp_oracle as IO
 import tsdf_oracle as TO
+from helpers import host_program, run_records as run
 from onnx_image_processing_amd import _native as N
 from onnx_image_processing_amd.synth import rgbd_camera, synth_depth_room
 
@@ -263,24 +262,8 @@ def test_oracle_compose():
 
 # ---- the kernels' arithmetic on the host ----------------------------------------------------------------------------------------
 
-@pytest.fixture(scope="module")
-def tsdf_host(tmp_path_factory):
-    """tests/native/tsdf_host.cpp around csrc/tsdf_math.h, compiled as plain C++ (no HIP)"""
-    from onnx_image_processing_amd.build import _hipcc
-    exe = str(tmp_path_factory.mktemp("tsdf_host") / "tsdf_host")
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "tsdf_host.cpp")
-    r = subprocess.run([_hipcc(), "-x", "c++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", src, "-o", exe, "-lm"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
-
-
-def run(exe, args, records):
-    text = "\n".join(" ".join("%.17g" % float(x) for x in rec) for rec in records)
-    out = subprocess.run([exe, *args], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
-    out = [np.array(ln.split(), F64) for ln in out if ln]
-    assert len(out) == len(records)
-    return out
+# tests/native/tsdf_host.cpp around csrc/tsdf_math.h, compiled as plain C++ (no HIP)
+tsdf_host = host_program("tsdf_host.cpp", hip=False)
 
 
 @pytest.fixture(scope="module")

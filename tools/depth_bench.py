@@ -22,9 +22,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from onnx_image_processing_amd import ops  # noqa: E402
-from test_gpu_depth_perf import H, W, RGB, _time_ms, operations, workload  # noqa: E402
-
-DEV = "cuda:0"
+from gpu_common import DEV, time_ms  # noqa: E402
+from test_gpu_depth_perf import H, W, RGB, operations, workload  # noqa: E402
 BYTES_PER_PIXEL = {"points": 16, "points+normals": 28, "alignment": 12}
 
 
@@ -38,8 +37,8 @@ def main():
         t = workload(frames)
         px = frames * H * W
         for name, (hip_fn, torch_fns) in operations(t).items():
-            hip = _time_ms(hip_fn, a.iters, a.warmup)
-            refs = {k: _time_ms(fn, max(5, a.iters // 4), 3) for k, fn in torch_fns.items()}
+            hip = time_ms(hip_fn, a.iters, a.warmup)
+            refs = {k: time_ms(fn, max(5, a.iters // 4), 3) for k, fn in torch_fns.items()}
             best = min(refs, key=refs.get)
             moved = BYTES_PER_PIXEL[name] * px
             row = {"workload": f"{name}_{frames}x{H}x{W}", "hip_ms": round(hip, 4), "hip_ms_per_frame": round(hip / frames, 4),
@@ -49,7 +48,7 @@ def main():
             if name == "points+normals":
                 src = torch.empty(moved // 2, dtype=torch.uint8, device=DEV)
                 dst = torch.empty_like(src)
-                cp = _time_ms(lambda: dst.copy_(src), a.iters, a.warmup)
+                cp = time_ms(lambda: dst.copy_(src), a.iters, a.warmup)
                 row.update({"copy_same_bytes_ms": round(cp, 4), "copy_GBps": round(moved / cp / 1e6, 1),
                             "share_of_copy_rate": round(cp / hip, 3)})
             print(json.dumps(row), flush=True)
@@ -57,10 +56,10 @@ def main():
             d16 = (t["depth"] * 1000.0).round().to(torch.int32).cpu().numpy().astype("uint16")
             d16 = torch.from_numpy(d16).to(DEV)
             u3 = t["u"] * 0.001
-            hip = _time_ms(lambda: ops.depth_to_points(d16, u3, t["v"], t["zs"], normals=True), a.iters, a.warmup)
+            hip = time_ms(lambda: ops.depth_to_points(d16, u3, t["v"], t["zs"], normals=True), a.iters, a.warmup)
             print(json.dumps({"workload": f"points+normals_u16_{frames}x{H}x{W}", "hip_ms": round(hip, 4),
                               "bytes_moved": 26 * px, "effective_GBps": round(26 * px / hip / 1e6, 1)}), flush=True)
-            al = _time_ms(lambda: ops.depth_align(d16, t["u"], t["v"], t["zs"], *RGB, t["rot"], t["trans"]), a.iters, a.warmup)
+            al = time_ms(lambda: ops.depth_align(d16, t["u"], t["v"], t["zs"], *RGB, t["rot"], t["trans"]), a.iters, a.warmup)
             print(json.dumps({"workload": f"alignment_u16_{frames}x{H}x{W}", "hip_ms": round(al, 4)}), flush=True)
 
 

@@ -20,7 +20,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from onnx_image_processing_amd import ops  # noqa: E402
-from test_gpu_ingest_perf import FORMULATIONS, WEIGHTS, WORKLOADS, _time_ms, traffic_bytes, workload  # noqa: E402
+from gpu_common import time_ms  # noqa: E402
+from test_gpu_ingest_perf import FORMULATIONS, WEIGHTS, WORKLOADS, traffic_bytes, workload  # noqa: E402
 
 COPY_RATE_GBS = 6290.0                 # measured float4 copy rate of the chip
 
@@ -50,7 +51,7 @@ def main():
         frames = workload(src, a.frames)
         for dtype, out_bytes in ((torch.uint8, 1), (torch.float32, 4)):
             fn = lambda: ops.ingest_frames(frames, h, w, out_dtype=dtype)  # noqa: E731
-            ms, med = window_ms(fn, a.iters, a.warmup), _time_ms(fn, min(a.iters, 50), 3)
+            ms, med = window_ms(fn, a.iters, a.warmup), time_ms(fn, min(a.iters, 50), 3)
             gbs = traffic_bytes(frames, h, w, out_bytes) / ms / 1e6
             print(json.dumps({"workload": f"{a.frames} x {name} {str(dtype).split('.')[-1]}", "hip_ms": round(ms, 4),
                               "hip_ms_single_call_median": round(med, 4), "gb_per_s": round(gbs, 1),

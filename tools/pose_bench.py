@@ -22,7 +22,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from onnx_image_processing_amd import ops  # noqa: E402
 from onnx_image_processing_amd.pytorch_model.geometry import RelativePoseEstimator  # noqa: E402
 from onnx_image_processing_amd.synth import synth_two_view, two_view_camera  # noqa: E402
-from test_gpu_pose_perf import THR, _time_ms, torch_hypotheses, workload  # noqa: E402
+from gpu_common import time_ms  # noqa: E402
+from test_gpu_pose_perf import THR, torch_hypotheses, workload  # noqa: E402
 
 
 def main():
@@ -55,9 +56,9 @@ def main():
     }
     shape = f"{a.pairs}x{a.n}x{H}"
     for name, fn in entries.items():
-        ms = _time_ms(fn, a.iters, a.warmup)
+        ms = time_ms(fn, a.iters, a.warmup)
         print(json.dumps({"workload": f"{name}_{shape}", "hip_ms": round(ms, 4), "pairs_per_s": round(a.pairs / ms * 1e3, 1)}), flush=True)
-    ref = _time_ms(lambda: torch_hypotheses(p1, p2, w["idx"], THR), max(5, a.iters // 4), 3)
+    ref = time_ms(lambda: torch_hypotheses(p1, p2, w["idx"], THR), max(5, a.iters // 4), 3)
     print(json.dumps({"workload": f"torch_gpu_hypotheses_{shape}", "torch_gpu_ms": round(ref, 4)}), flush=True)
 
 

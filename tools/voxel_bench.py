@@ -22,9 +22,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from onnx_image_processing_amd import _native, ops  # noqa: E402
 from onnx_image_processing_amd.synth import synth_depth_cloud  # noqa: E402
-from test_gpu_voxel_perf import _time_ms, torch_voxel  # noqa: E402
-
-DEV = "cuda:0"
+from gpu_common import DEV, time_ms  # noqa: E402
+from test_gpu_voxel_perf import torch_voxel  # noqa: E402
 
 
 def key_bits(pts: np.ndarray, leaf: float) -> int:
@@ -58,8 +57,8 @@ def main():
         packed = torch.cat(dev)
         offs = torch.tensor([0] + [c.shape[0] for c in clouds], dtype=torch.int64).cumsum(0).to(DEV)
         lf = torch.full((len(clouds),), leaf, dtype=torch.float32, device=DEV)
-        hip = _time_ms(lambda: ops.voxel_downsample_batch(packed, lf, offsets=offs), a.iters, a.warmup)
-        ref = _time_ms(lambda: [torch_voxel(c, leaf) for c in dev], max(3, a.iters // 4), 2)
+        hip = time_ms(lambda: ops.voxel_downsample_batch(packed, lf, offsets=offs), a.iters, a.warmup)
+        ref = time_ms(lambda: [torch_voxel(c, leaf) for c in dev], max(3, a.iters // 4), 2)
         n = packed.shape[0]
         bits = max(key_bits(c, leaf) for c in clouds)
         ws = _native.load().mi_voxel_downsample_workspace_bytes(len(clouds), n, 3)
