@@ -107,8 +107,14 @@ globals().update(_constants)            # MI_OK, MI_BAD_HARD, MI_SOLVER_NO_FORK,
 # not part of the product ABI; nothing in this package calls them
 DEBUG_SIGNATURES, _debug_restypes, _, _ = _read("mi355x_match_debug.h")
 RESTYPES.update(_debug_restypes)
+# include/mi355x_match_pgo.h: the pose-graph section of the ABI (K27), a header and a library of its own
+# (lib/libmi355x_match_pgo.so, load_pgo()): the product library exports include/mi355x_match.h and nothing else.  call()
+# finds the library of a name by itself.  Its limits are EXTRA_CONSTANTS["MI_PGO_MAX_NODES"], ...: a dictionary.
+EXTRA_SIGNATURES, _extra_restypes, _, EXTRA_CONSTANTS = _read("mi355x_match_pgo.h")
+RESTYPES.update(_extra_restypes)
 
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_debug.so")
+PGO_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_pgo.so")
 
 _lib = None            # the library every call() goes through: the product, unless inside debug_library()
 _product = None
@@ -138,6 +144,22 @@ def load() -> ctypes.CDLL:
             _product = _open(LIB_PATH, SIGNATURES)
         _lib = _product
     return _lib
+
+
+_pgo = None
+
+
+def load_pgo() -> ctypes.CDLL:
+    """lib/libmi355x_match_pgo.so, the entries of include/mi355x_match_pgo.h, loaded once."""
+    global _pgo
+    if _pgo is None:
+        _pgo = _open(PGO_LIB_PATH, EXTRA_SIGNATURES)
+    return _pgo
+
+
+def library_of(name: str) -> ctypes.CDLL:
+    """The library that exports the entry `name`."""
+    return load_pgo() if name in EXTRA_SIGNATURES else load()
 
 
 class debug_library:
@@ -214,7 +236,7 @@ def timings_ms() -> dict:
 
 
 def call(name: str, *args) -> None:
-    fn = getattr(load(), name)
+    fn = getattr(library_of(name), name)
     if _timers is None or (_timed_names is not None and name not in _timed_names):
         check(fn(*args), name)
         return

@@ -69,7 +69,7 @@ def _workspace(query: str, *args, device, refusal: str | None = None):
     """The library workspace of one call, sized by the `*_workspace_bytes` entry `query`(*args) -> (int64 tensor of
     ceil(bytes / 16) * 2 words, bytes).  The library is told the queried count, not the rounded one.  A size of 0 means
     the request is outside what the entry point covers: RuntimeError(refusal) for the ops that have a refusal text."""
-    wbytes = int(getattr(N.load(), query)(*args))
+    wbytes = int(getattr(N.library_of(query), query)(*args))
     if wbytes == 0 and refusal is not None:
         raise RuntimeError(refusal)
     return torch.empty(((wbytes + 15) // 16 * 2,), dtype=torch.int64, device=device), wbytes
@@ -1539,6 +1539,101 @@ def ba_refine(r: torch.Tensor, t: torch.Tensor, points: torch.Tensor, obs: torch
            point_ok.data_ptr(), cost0.data_ptr(), cost.data_ptr(), accepted.data_ptr(), info.data_ptr(), ok.data_ptr(),
            work.data_ptr(), wbytes, N.stream_ptr())
     return ro, to, xo, point_ok.view(torch.bool), cost0, cost, accepted, info, ok.view(torch.bool)
+
+
+# ---- K27 pose-graph optimisation (include/mi355x_match_pgo.h) ---------------------------------------------------------------
+
+PGO_MAX_NODES = N.EXTRA_CONSTANTS["MI_PGO_MAX_NODES"]
+PGO_MAX_EDGES = N.EXTRA_CONSTANTS["MI_PGO_MAX_EDGES"]
+PGO_MAX_ITERATIONS = N.EXTRA_CONSTANTS["MI_PGO_MAX_ITERATIONS"]
+PGO_MAX_PCG = N.EXTRA_CONSTANTS["MI_PGO_MAX_PCG"]
+
+
+def _pgo_graph(r: torch.Tensor, t: torch.Tensor, edge_index: torch.Tensor, r_meas: torch.Tensor, t_meas: torch.Tensor,
+               information: torch.Tensor, edge_valid: torch.Tensor | None, huber: float, what: str, fixed: torch.Tensor | None = None):
+    """The state and the edges of a batch of graphs as the C ABI reads them: r (B, N, 3, 3), t (B, N, 3), edge_index (B, E, 2),
+    r_meas (B, E, 3, 3), t_meas (B, E, 3), information (B, E, 6, 6), edge_valid (B, E) or None (every edge); fixed (B, N) where the entry takes it (its pointer is then the last of `ptrs`)."""
+    rr, tt, zr, zt, om = (a.float().contiguous() for a in (r, t, r_meas, t_meas, information))
+    if rr.dim() != 4 or tuple(rr.shape[2:]) != (3, 3) or edge_index.dim() != 3 or edge_index.shape[-1] != 2:
+        raise RuntimeError(f"{what}: poses must be (B, N, 3, 3) and edge_index (B, E, 2), got {tuple(r.shape)} and {tuple(edge_index.shape)}")
+    b, n, e = int(rr.shape[0]), int(rr.shape[1]), int(edge_index.shape[1])
+    if edge_valid is None:
+        edge_valid = torch.ones((b, e), dtype=torch.bool, device=rr.device)
+    if (tuple(tt.shape) != (b, n, 3) or edge_index.shape[0] != b or tuple(zr.shape) != (b, e, 3, 3) or tuple(zt.shape) != (b, e, 3)
+            or tuple(om.shape) != (b, e, 6, 6) or tuple(edge_valid.shape) != (b, e)):
+        raise RuntimeError(f"{what}: expected t ({b}, {n}, 3), r_meas ({b}, {e}, 3, 3), t_meas ({b}, {e}, 3), information ({b}, {e}, 6, 6) "
+                           f"and edge_valid ({b}, {e}), got {tuple(t.shape)}, {tuple(r_meas.shape)}, {tuple(t_meas.shape)}, "
+                           f"{tuple(information.shape)} and {tuple(edge_valid.shape)}")
+    if not 2 <= n <= PGO_MAX_NODES or not 1 <= e <= PGO_MAX_EDGES or b < 1:
+        raise RuntimeError(f"{what}: N = {n} nodes and E = {e} edges, supported: 2 .. {PGO_MAX_NODES} and 1 .. {PGO_MAX_EDGES}")
+    if not (huber >= 0 and huber < float("inf")):
+        raise RuntimeError(f"{what}: huber must be finite and not negative, got {huber}")
+    if fixed is not None and tuple(fixed.shape) != (b, n):
+        raise RuntimeError(f"{what}: fixed must be ({b}, {n}), got {tuple(fixed.shape)}")
+    ei = edge_index.to(I32).contiguous()
+    ev, fx = _validity_bytes(edge_valid), _validity_bytes(fixed)
+    ptrs = (N.dev(rr, F32, "r"), N.dev(tt, F32, "t"), N.dev(ei, I32, "edge_index"), N.dev(zr, F32, "r_meas"), N.dev(zt, F32, "t_meas"),
+            N.dev(om, F32, "information"), N.dev(ev, U8, "edge_valid")) + (() if fx is None else (N.dev(fx, U8, "fixed"),))
+    return ptrs, (rr, tt, ei, zr, zt, om, ev, fx), b, n, e
+
+
+def pgo_cost(r: torch.Tensor, t: torch.Tensor, edge_index: torch.Tensor, r_meas: torch.Tensor, t_meas: torch.Tensor,
+             information: torch.Tensor, edge_valid: torch.Tensor | None = None, huber: float = 0.0):
+    """`mi_pgo_cost`: the cost of a batch of pose graphs -> (chi2 (B, E) float32: e^T Omega e of every active edge, 0 elsewhere;
+    cost (B,) float32; active (B, E) bool)."""
+    ptrs, keep, b, n, e = _pgo_graph(r, t, edge_index, r_meas, t_meas, information, edge_valid, huber, "pgo_cost")
+    dev = keep[0].device
+    chi2 = torch.empty((b, e), dtype=F32, device=dev)
+    cost = torch.empty((b,), dtype=F32, device=dev)
+    active = torch.empty((b, e), dtype=U8, device=dev)
+    N.call("mi_pgo_cost", *ptrs, b, n, e, float(huber), chi2.data_ptr(), cost.data_ptr(), active.data_ptr(), N.stream_ptr())
+    return chi2, cost, active.view(torch.bool)
+
+
+def pgo_linearise(r: torch.Tensor, t: torch.Tensor, edge_index: torch.Tensor, r_meas: torch.Tensor, t_meas: torch.Tensor,
+                  information: torch.Tensor, fixed: torch.Tensor, edge_valid: torch.Tensor | None = None, huber: float = 0.0):
+    """`mi_pgo_linearise`: one undamped linearisation -> (diag (B, N, 6, 6): the diagonal blocks, zero for fixed and edgeless
+    nodes; off (B, E, 6, 6): the (i, j) block of every edge, zero for inactive edges and edges at a fixed node; g (B, N, 6);
+    cost (B,))."""
+    ptrs, keep, b, n, e = _pgo_graph(r, t, edge_index, r_meas, t_meas, information, edge_valid, huber, "pgo_linearise", fixed)
+    dev = keep[0].device
+    diag = torch.empty((b, n, 6, 6), dtype=F32, device=dev)
+    off = torch.empty((b, e, 6, 6), dtype=F32, device=dev)
+    g = torch.empty((b, n, 6), dtype=F32, device=dev)
+    cost = torch.empty((b,), dtype=F32, device=dev)
+    work, wbytes = _workspace("mi_pgo_workspace_bytes", b, n, e, device=dev)
+    N.call("mi_pgo_linearise", *ptrs, b, n, e, float(huber), diag.data_ptr(), off.data_ptr(), g.data_ptr(),
+           cost.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    return diag, off, g, cost
+
+
+def pgo_refine(r: torch.Tensor, t: torch.Tensor, edge_index: torch.Tensor, r_meas: torch.Tensor, t_meas: torch.Tensor,
+               information: torch.Tensor, fixed: torch.Tensor, edge_valid: torch.Tensor | None = None, iterations: int = 10,
+               pcg_iterations: int = 64, huber: float = 0.0):
+    """`mi_pgo_refine`: `iterations` Levenberg-Marquardt iterations of `pcg_iterations` conjugate-gradient trips each on every
+    graph in one launch -> (R (B, N, 3, 3), t (B, N, 3), chi2 (B, E), cost0 (B,), cost (B,), accepted (B,) int32, info
+    (B, N, 6, 6): each node's conditional information given its neighbours, ok (B,) bool).  Fixed nodes and nodes without an
+    active edge come back unchanged; where ok is False (no active edge, no fixed node, no free node with an edge, or a cost
+    that is not finite) everything does."""
+    if not 1 <= int(iterations) <= PGO_MAX_ITERATIONS:
+        raise RuntimeError(f"pgo_refine: iterations must be in 1 .. {PGO_MAX_ITERATIONS}, got {iterations}")
+    if not 1 <= int(pcg_iterations) <= PGO_MAX_PCG:
+        raise RuntimeError(f"pgo_refine: pcg_iterations must be in 1 .. {PGO_MAX_PCG}, got {pcg_iterations}")
+    ptrs, keep, b, n, e = _pgo_graph(r, t, edge_index, r_meas, t_meas, information, edge_valid, huber, "pgo_refine", fixed)
+    dev = keep[0].device
+    ro = torch.empty((b, n, 3, 3), dtype=F32, device=dev)
+    to = torch.empty((b, n, 3), dtype=F32, device=dev)
+    chi2 = torch.empty((b, e), dtype=F32, device=dev)
+    cost0 = torch.empty((b,), dtype=F32, device=dev)
+    cost = torch.empty((b,), dtype=F32, device=dev)
+    accepted = torch.empty((b,), dtype=I32, device=dev)
+    info = torch.empty((b, n, 6, 6), dtype=F32, device=dev)
+    ok = torch.empty((b,), dtype=U8, device=dev)
+    work, wbytes = _workspace("mi_pgo_workspace_bytes", b, n, e, device=dev)
+    N.call("mi_pgo_refine", *ptrs, b, n, e, int(iterations), int(pcg_iterations), float(huber), ro.data_ptr(),
+           to.data_ptr(), chi2.data_ptr(), cost0.data_ptr(), cost.data_ptr(), accepted.data_ptr(), info.data_ptr(), ok.data_ptr(),
+           work.data_ptr(), wbytes, N.stream_ptr())
+    return ro, to, chi2, cost0, cost, accepted, info, ok.view(torch.bool)
 
 
 # ---- K26 loop-closure retrieval (include/mi355x_match.h, "loop-closure retrieval") -------------------------------------------

@@ -5,9 +5,10 @@ from .direct_rgbd import DirectRgbdRefiner
 from .direct_tsdf_volume import DirectTsdfVolume
 from .essential_matrix_estimator import EssentialMatrixEstimator
 from .planar_pose import HomographyEstimator, PlanarPoseEstimator, TwoViewPoseEstimator
+from .pose_graph import PoseGraphOptimizer
 from .relative_pose import RelativePoseEstimator, triangulate_points
 from .rgbd_pose import RgbdPoseEstimator
 from .tsdf_volume import TsdfVolume
 
 __all__ = ["AbsolutePoseEstimator", "BundleAdjuster", "DenseRgbdRefiner", "DirectRgbdRefiner", "DirectTsdfVolume", "EssentialMatrixEstimator", "HomographyEstimator",
-           "PlanarPoseEstimator", "RelativePoseEstimator", "RgbdPoseEstimator", "TsdfVolume", "TwoViewPoseEstimator", "triangulate_points"]
+           "PlanarPoseEstimator", "PoseGraphOptimizer", "RelativePoseEstimator", "RgbdPoseEstimator", "TsdfVolume", "TwoViewPoseEstimator", "triangulate_points"]

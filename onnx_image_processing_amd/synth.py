@@ -546,3 +546,70 @@ def synth_place_descriptors(seed: int, n_frames: int, k: int, num_bits: int, fli
     order = np.argsort(draw(k, 1, 36)[:, 0], kind="stable")
     source = np.where(kept, np.arange(k), -1)[order].astype(np.int64)
     return db.view(np.int32), np.ascontiguousarray(rows[order]).view(np.int32), target, source
+
+
+def synth_pose_graph(seed: int, nodes: int, loops: int, sigma_rot: float, sigma_trans: float, false_loops: int = 0):
+    """A pose graph for the pose-graph kernels (K27): (R0, t0, edge_index, R_meas, t_meas, information, fixed, protected, R, t,
+    false_edge).
+
+    The truth: `nodes` cameras going TWICE round a closed ring in the x-z plane (0.15 m between neighbours, so a radius of
+    0.15 * (nodes / 2) / (2 pi) m), looking along the tangent, with a wobble of N(0, 0.02^2) m per axis on the centre and the
+    Rodrigues rotation of a N(0, 0.04^2) vector on the orientation; R (nodes, 3, 3), t (nodes, 3) float64 with X_c = R X + t.
+    Edges (i, j) carry the motion X_j = R_z X_i + t_z: nodes - 1 odometry edges (k, k + 1), then `loops` loop edges
+    (i, i + nodes // 2), i = l * ((nodes - nodes // 2) // loops) -- a place seen on the first lap and again on the second --,
+    then `false_loops` edges between hashed pairs.  A measurement is the true motion perturbed in the residual's coordinates:
+    R_z = Exp(w)^T R_p, t_z = Exp(w)^T (t_p - tau) with w ~ N(0, sigma_rot^2), tau ~ N(0, sigma_trans^2) per axis, so that the
+    edge's residual at the truth is exactly (w, tau); a false loop's (w, tau) is N(0, 0.5^2) rad and N(0, 1) m instead.
+    information (E, 6, 6) = diag(1 / sigma_rot^2 x 3, 1 / sigma_trans^2 x 3) (sigma = 0: the identity); fixed (nodes,) bool: node
+    0; protected (E,) bool: the odometry edges; false_edge (E,) bool.  The start R0, t0 (float32): node 0 at the truth, the
+    odometry chained from it.  edge_index int32, measurements and information float32.  float64 arithmetic on hashed integers:
+    the same graph everywhere."""
+    if nodes < 2 or loops < 0 or false_loops < 0 or 2 * loops > nodes:
+        raise ValueError(f"synth_pose_graph: nodes >= 2 and 0 <= 2 loops <= nodes, got {nodes} nodes, {loops} loops, {false_loops} false loops")
+
+    def uni(shape, salt):
+        idx = np.arange(int(np.prod(shape)), dtype=np.uint64)
+        return (((_hash3(seed, idx, np.uint64(salt) + 0 * idx, 37) >> np.uint64(11)).astype(np.float64) + 0.5) / float(1 << 53)).reshape(shape)
+
+    def normal(shape, salt):
+        return np.sqrt(-2.0 * np.log(uni(shape, salt))) * np.cos(2.0 * np.pi * uni(shape, salt + 1))
+
+    radius = BA_FRAME_SPACING * (nodes / 2.0) / (2.0 * np.pi)
+    ang = 4.0 * np.pi * np.arange(nodes) / nodes
+    centre = np.stack([radius * np.sin(ang), np.zeros(nodes), radius * (1.0 - np.cos(ang))], 1) + 0.02 * normal((nodes, 3), 0)
+    wob = 0.04 * normal((nodes, 3), 2)
+    R, t = np.zeros((nodes, 3, 3)), np.zeros((nodes, 3))
+    for k in range(nodes):
+        heading = _rodrigues64(np.array([0.0, ang[k], 0.0]))              # camera-to-world: the z axis along the tangent
+        R[k] = (heading @ _rodrigues64(wob[k])).T
+        t[k] = -R[k] @ centre[k]
+    step = (nodes - nodes // 2) // loops if loops else 0
+    pairs = [(k, k + 1) for k in range(nodes - 1)] + [(l * step, l * step + nodes // 2) for l in range(loops)]
+    for f in range(false_loops):
+        h = _hash3(seed, np.array([f, f], np.uint64), np.array([0, 1], np.uint64), 38)
+        i = int(h[0] % np.uint64(nodes))
+        j = (i + 2 + int(h[1] % np.uint64(max(nodes - 3, 1)))) % nodes
+        pairs.append((i, j))
+    E = len(pairs)
+    ei = np.array(pairs, np.int32).reshape(E, 2)
+    false_edge = np.arange(E) >= nodes - 1 + loops
+    w = sigma_rot * normal((E, 3), 4)
+    tau = sigma_trans * normal((E, 3), 6)
+    w[false_edge] = 0.5 * normal((E, 3), 8)[false_edge]
+    tau[false_edge] = 1.0 * normal((E, 3), 10)[false_edge]
+    zr, zt = np.zeros((E, 3, 3)), np.zeros((E, 3))
+    for e, (i, j) in enumerate(pairs):
+        Rp = R[j] @ R[i].T
+        tp = t[j] - Rp @ t[i]
+        Ew = _rodrigues64(w[e])
+        zr[e], zt[e] = Ew.T @ Rp, Ew.T @ (tp - tau[e])
+    sr = 1.0 / sigma_rot ** 2 if sigma_rot > 0 else 1.0
+    st = 1.0 / sigma_trans ** 2 if sigma_trans > 0 else 1.0
+    information = np.tile(np.diag([sr, sr, sr, st, st, st]), (E, 1, 1))
+    R0, t0 = R.copy(), t.copy()
+    for k in range(nodes - 1):
+        R0[k + 1], t0[k + 1] = zr[k] @ R0[k], zr[k] @ t0[k] + zt[k]
+    fixed = np.arange(nodes) == 0
+    protected = np.arange(E) < nodes - 1
+    return (R0.astype(np.float32), t0.astype(np.float32), ei, zr.astype(np.float32), zt.astype(np.float32), information.astype(np.float32),
+            fixed, protected, R, t, false_edge)
