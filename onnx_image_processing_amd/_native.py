@@ -112,9 +112,14 @@ RESTYPES.update(_debug_restypes)
 # finds the library of a name by itself.  Its limits are EXTRA_CONSTANTS["MI_PGO_MAX_NODES"], ...: a dictionary.
 EXTRA_SIGNATURES, _extra_restypes, _, EXTRA_CONSTANTS = _read("mi355x_match_pgo.h")
 RESTYPES.update(_extra_restypes)
+# include/mi355x_match_tracks.h: the landmark-track section (K28), likewise a header and a library of its own
+# (lib/libmi355x_match_tracks.so, load_tracks()), in dictionaries of its own: TRACKS_CONSTANTS["MI_TRACKS_MAX_FRAMES"], ...
+TRACKS_SIGNATURES, _tracks_restypes, _, TRACKS_CONSTANTS = _read("mi355x_match_tracks.h")
+RESTYPES.update(_tracks_restypes)
 
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_debug.so")
 PGO_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_pgo.so")
+TRACKS_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_tracks.so")
 
 _lib = None            # the library every call() goes through: the product, unless inside debug_library()
 _product = None
@@ -157,8 +162,21 @@ def load_pgo() -> ctypes.CDLL:
     return _pgo
 
 
+_tracks = None
+
+
+def load_tracks() -> ctypes.CDLL:
+    """lib/libmi355x_match_tracks.so, the entries of include/mi355x_match_tracks.h, loaded once."""
+    global _tracks
+    if _tracks is None:
+        _tracks = _open(TRACKS_LIB_PATH, TRACKS_SIGNATURES)
+    return _tracks
+
+
 def library_of(name: str) -> ctypes.CDLL:
     """The library that exports the entry `name`."""
+    if name in TRACKS_SIGNATURES:
+        return load_tracks()
     return load_pgo() if name in EXTRA_SIGNATURES else load()
 
 

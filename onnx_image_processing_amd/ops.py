@@ -1636,6 +1636,93 @@ def pgo_refine(r: torch.Tensor, t: torch.Tensor, edge_index: torch.Tensor, r_mea
     return ro, to, chi2, cost0, cost, accepted, info, ok.view(torch.bool)
 
 
+# ---- K28 landmark tracks (include/mi355x_match_tracks.h) ------------------------------------------------------------------------
+
+TRACKS_MAX_FRAMES = N.TRACKS_CONSTANTS["MI_TRACKS_MAX_FRAMES"]
+TRACKS_MAX_KEYPOINTS = N.TRACKS_CONSTANTS["MI_TRACKS_MAX_KEYPOINTS"]
+TRACKS_MAX_PAIRS = N.TRACKS_CONSTANTS["MI_TRACKS_MAX_PAIRS"]
+TRACKS_MAX_MATCHES = N.TRACKS_CONSTANTS["MI_TRACKS_MAX_MATCHES"]
+
+
+def _tracks_views(min_views: int, f: int, what: str) -> int:
+    if not 2 <= int(min_views) <= f:
+        raise RuntimeError(f"{what}: min_views must be in 2 .. {f}, got {min_views}")
+    return int(min_views)
+
+
+def tracks_build(keypoints: torch.Tensor, pair_frames: torch.Tensor, match_ij: torch.Tensor, match_valid: torch.Tensor,
+                 kp_valid: torch.Tensor | None = None, min_views: int = 2, landmarks: int = 2048):
+    """`mi_tracks_build`: the pairwise matches of a batch of windows -> landmark tracks.  keypoints (B, F, K, 2) float32, copied
+    and never interpreted; pair_frames (B, P, 2) integer (a, b); match_ij (B, P, M, 2) integer (i in a, j in b); match_valid
+    (B, P, M); kp_valid (B, F, K) or None (every keypoint) -> (track_kp (B, F, L) int32: keypoint index or -1, vis (B, F, L)
+    bool, track_keypoints (B, F, L, 2) float32, track_len (B, L) int32, kp_track (B, F, K) int32: slot, -2 for a conflicting
+    component's node, -1 otherwise, counts (B, 4) int32: components of >= 2 nodes, conflicting, eligible, kept)."""
+    kk = keypoints.float().contiguous()
+    if kk.dim() != 4 or kk.shape[-1] != 2 or pair_frames.dim() != 3 or pair_frames.shape[-1] != 2 or match_ij.dim() != 4 or match_ij.shape[-1] != 2:
+        raise RuntimeError(f"tracks_build: keypoints must be (B, F, K, 2), pair_frames (B, P, 2) and match_ij (B, P, M, 2), got "
+                           f"{tuple(keypoints.shape)}, {tuple(pair_frames.shape)} and {tuple(match_ij.shape)}")
+    b, f, k = (int(v) for v in kk.shape[:3])
+    p, m = int(match_ij.shape[1]), int(match_ij.shape[2])
+    if (tuple(pair_frames.shape) != (b, p, 2) or match_ij.shape[0] != b or tuple(match_valid.shape) != (b, p, m)
+            or (kp_valid is not None and tuple(kp_valid.shape) != (b, f, k))):
+        raise RuntimeError(f"tracks_build: expected pair_frames ({b}, {p}, 2), match_ij ({b}, {p}, {m}, 2), match_valid ({b}, {p}, {m}) and "
+                           f"kp_valid ({b}, {f}, {k}) or None, got {tuple(pair_frames.shape)}, {tuple(match_ij.shape)}, "
+                           f"{tuple(match_valid.shape)} and {None if kp_valid is None else tuple(kp_valid.shape)}")
+    l = int(landmarks)
+    if (b < 1 or not 2 <= f <= TRACKS_MAX_FRAMES or not 1 <= k <= TRACKS_MAX_KEYPOINTS or not 1 <= p <= TRACKS_MAX_PAIRS
+            or not 1 <= m <= TRACKS_MAX_MATCHES or not 1 <= l <= BA_MAX_LANDMARKS):
+        raise RuntimeError(f"tracks_build: F = {f} frames, K = {k} keypoints, P = {p} pairs, M = {m} matches and L = {l} landmarks, supported: "
+                           f"2 .. {TRACKS_MAX_FRAMES}, 1 .. {TRACKS_MAX_KEYPOINTS}, 1 .. {TRACKS_MAX_PAIRS}, 1 .. {TRACKS_MAX_MATCHES} and "
+                           f"1 .. {BA_MAX_LANDMARKS}")
+    mv = _tracks_views(min_views, f, "tracks_build")
+    pf, ij = pair_frames.to(I32).contiguous(), match_ij.to(I32).contiguous()
+    mval, kval = _validity_bytes(match_valid), _validity_bytes(kp_valid)
+    ptrs = (N.dev(pf, I32, "pair_frames"), N.dev(ij, I32, "match_ij"), N.dev(mval, U8, "match_valid"), N.opt(kval, U8, "kp_valid"),
+            N.dev(kk, F32, "keypoints"))
+    dev = kk.device
+    track_kp = torch.empty((b, f, l), dtype=I32, device=dev)
+    vis = torch.empty((b, f, l), dtype=U8, device=dev)
+    track_keypoints = torch.empty((b, f, l, 2), dtype=F32, device=dev)
+    track_len = torch.empty((b, l), dtype=I32, device=dev)
+    kp_track = torch.empty((b, f, k), dtype=I32, device=dev)
+    counts = torch.empty((b, 4), dtype=I32, device=dev)
+    work, wbytes = _workspace("mi_tracks_workspace_bytes", b, f, k, p, m, l, device=dev)
+    N.call("mi_tracks_build", *ptrs, b, f, k, p, m, mv, l, track_kp.data_ptr(), vis.data_ptr(), track_keypoints.data_ptr(),
+           track_len.data_ptr(), kp_track.data_ptr(), counts.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    return track_kp, vis.view(torch.bool), track_keypoints, track_len, kp_track, counts
+
+
+def tracks_triangulate(r: torch.Tensor, t: torch.Tensor, obs: torch.Tensor, vis: torch.Tensor, min_views: int = 2,
+                       max_e2: float = 1e-4, max_cos: float = 1.0):
+    """`mi_tracks_triangulate`: the N-view triangulation of every landmark slot of a batch of windows.  r (B, F, 3, 3), t
+    (B, F, 3) with X_c = R X + t, obs (B, F, L, 2) normalised (x, y), vis (B, F, L) -> (points (B, L, 3) float32, point_ok
+    (B, L) bool, vis_out (B, F, L) bool: vis where point_ok, e2max (B, L): the largest squared normalised reprojection
+    distance, cos_par (B, L): the cosine of the largest parallax angle between two seeing frames)."""
+    rr, tt, oo = (a.float().contiguous() for a in (r, t, obs))
+    if rr.dim() != 4 or tuple(rr.shape[2:]) != (3, 3) or oo.dim() != 4 or oo.shape[-1] != 2:
+        raise RuntimeError(f"tracks_triangulate: poses must be (B, F, 3, 3) and obs (B, F, L, 2), got {tuple(r.shape)} and {tuple(obs.shape)}")
+    b, f, l = int(rr.shape[0]), int(rr.shape[1]), int(oo.shape[2])
+    if tuple(tt.shape) != (b, f, 3) or tuple(oo.shape) != (b, f, l, 2) or tuple(vis.shape) != (b, f, l):
+        raise RuntimeError(f"tracks_triangulate: expected t ({b}, {f}, 3), obs ({b}, {f}, {l}, 2) and vis ({b}, {f}, {l}), got "
+                           f"{tuple(t.shape)}, {tuple(obs.shape)} and {tuple(vis.shape)}")
+    if b < 1 or not 2 <= f <= TRACKS_MAX_FRAMES or not 1 <= l <= BA_MAX_LANDMARKS:
+        raise RuntimeError(f"tracks_triangulate: F = {f} frames and L = {l} landmarks, supported: 2 .. {TRACKS_MAX_FRAMES} and 1 .. {BA_MAX_LANDMARKS}")
+    mv = _tracks_views(min_views, f, "tracks_triangulate")
+    if not (0 < max_e2 < float("inf")) or not (-1 < max_cos <= 1):
+        raise RuntimeError(f"tracks_triangulate: max_e2 must be positive and finite and max_cos in (-1, 1], got {max_e2} and {max_cos}")
+    vv = _validity_bytes(vis)
+    ptrs = (N.dev(rr, F32, "r"), N.dev(tt, F32, "t"), N.dev(oo, F32, "obs"), N.dev(vv, U8, "vis"))
+    dev = rr.device
+    points = torch.empty((b, l, 3), dtype=F32, device=dev)
+    point_ok = torch.empty((b, l), dtype=U8, device=dev)
+    vis_out = torch.empty((b, f, l), dtype=U8, device=dev)
+    e2max = torch.empty((b, l), dtype=F32, device=dev)
+    cos_par = torch.empty((b, l), dtype=F32, device=dev)
+    N.call("mi_tracks_triangulate", *ptrs, b, f, l, mv, float(max_e2), float(max_cos), points.data_ptr(), point_ok.data_ptr(),
+           vis_out.data_ptr(), e2max.data_ptr(), cos_par.data_ptr(), N.stream_ptr())
+    return points, point_ok.view(torch.bool), vis_out.view(torch.bool), e2max, cos_par
+
+
 # ---- K26 loop-closure retrieval (include/mi355x_match.h, "loop-closure retrieval") -------------------------------------------
 
 PLACE_MAX_DESCRIPTORS = N.MI_PLACE_MAX_DESCRIPTORS

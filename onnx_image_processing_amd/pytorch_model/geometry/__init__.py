@@ -4,6 +4,7 @@ from .dense_rgbd import DenseRgbdRefiner
 from .direct_rgbd import DirectRgbdRefiner
 from .direct_tsdf_volume import DirectTsdfVolume
 from .essential_matrix_estimator import EssentialMatrixEstimator
+from .landmark_tracks import LandmarkTracks
 from .planar_pose import HomographyEstimator, PlanarPoseEstimator, TwoViewPoseEstimator
 from .pose_graph import PoseGraphOptimizer
 from .relative_pose import RelativePoseEstimator, triangulate_points
@@ -11,4 +12,4 @@ from .rgbd_pose import RgbdPoseEstimator
 from .tsdf_volume import TsdfVolume
 
 __all__ = ["AbsolutePoseEstimator", "BundleAdjuster", "DenseRgbdRefiner", "DirectRgbdRefiner", "DirectTsdfVolume", "EssentialMatrixEstimator", "HomographyEstimator",
-           "PlanarPoseEstimator", "PoseGraphOptimizer", "RelativePoseEstimator", "RgbdPoseEstimator", "TsdfVolume", "TwoViewPoseEstimator", "triangulate_points"]
+           "LandmarkTracks", "PlanarPoseEstimator", "PoseGraphOptimizer", "RelativePoseEstimator", "RgbdPoseEstimator", "TsdfVolume", "TwoViewPoseEstimator", "triangulate_points"]

@@ -1,5 +1,6 @@
 """BundleAdjuster -- the joint refinement of a window of camera poses and the landmarks they share: what follows
-AbsolutePoseEstimator / RelativePoseEstimator and `triangulate_points` in a visual-odometry back end, and the host call
+AbsolutePoseEstimator / RelativePoseEstimator and `LandmarkTracks` (the window's matches as tracks with triangulated
+points: this module's arguments) in a visual-odometry back end, and the host call
 (g2o, Ceres, cv2.detail.BundleAdjusterReproj) it replaces.  Levenberg-Marquardt on the reprojection error with the
 landmarks eliminated by the Schur complement, a Huber loss, a fixed number of iterations, every window of the batch in one
 workgroup of one launch.  K25: `mi_normalise_keypoints`, `mi_ba_refine`, `mi_ba_cost`; the algorithm is stated in

@@ -613,3 +613,57 @@ def synth_pose_graph(seed: int, nodes: int, loops: int, sigma_rot: float, sigma_
     protected = np.arange(E) < nodes - 1
     return (R0.astype(np.float32), t0.astype(np.float32), ei, zr.astype(np.float32), zt.astype(np.float32), information.astype(np.float32),
             fixed, protected, R, t, false_edge)
+
+
+def synth_track_window(seed: int, frames: int, keypoints: int, landmarks: int, pair_span: int = 2, miss: float = 0.1,
+                       outlier_fraction: float = 0.1, noise_px: float = 0.5, pose_noise: float = 0.002):
+    """A window for the landmark-track kernels (K28): (keypoints, kp_id, pair_frames, match_ij, match_valid, R0, t0, R, t, X).
+
+    The scene is synth_ba_window(seed, frames, landmarks, visibility = 1 - miss, noise_px, pose_noise = pose_noise): its truth
+    R, t, X (float64), its perturbed start R0, t0 (float32, frame 0 at the truth; 0.002 rad is one pixel at this camera: poses
+    as a PnP on a few hundred matches leaves them) and its observations.  Every frame has `keypoints` keypoint slots:
+    the landmarks the frame sees go to slots chosen by a hashed permutation, the other slots are clutter, uniform over the
+    480 x 640 image.  keypoints (frames, keypoints, 2) float32 pixel (y, x); kp_id (frames, keypoints) int32: the planted
+    landmark, -1 for clutter.  pair_frames (P, 2) int32: every (a, b) with 0 < b - a <= pair_span, a ascending.  Per pair the
+    matcher is one-to-one: every landmark both frames see is matched; round(outlier_fraction * their number) of those matches,
+    chosen by a hashed ranking, have their end in b moved to a keypoint of b that no match of the pair uses (clutter, or a
+    landmark a does not see): wrong matches.  match_ij (P, M, 2) int32 with M = keypoints, match_valid (P, M) bool: the matches
+    at hashed positions of the list; every other record is padding whose index fields hold garbage (-1, 0x7fffffff, -2^31 or
+    a number that looks like an index).  float64 arithmetic on hashed integers: the same window everywhere."""
+    if frames < 2 or not 1 <= landmarks <= keypoints or not 1 <= pair_span < frames or not 0 <= miss < 1 or not 0 <= outlier_fraction <= 1:
+        raise ValueError(f"synth_track_window: frames >= 2, 1 <= landmarks <= keypoints, 1 <= pair_span < frames, 0 <= miss < 1, "
+                         f"0 <= outlier_fraction <= 1, got {frames}, {landmarks}, {keypoints}, {pair_span}, {miss}, {outlier_fraction}")
+    R0, t0, _, kp_l, visible, R, t, X, _ = synth_ba_window(seed, frames, landmarks, 1.0 - miss, noise_px, pose_noise=pose_noise)
+    height, width = TWO_VIEW_IMAGE
+
+    def uni(shape, salt):
+        idx = np.arange(int(np.prod(shape)), dtype=np.uint64)
+        return (((_hash3(seed, idx, np.uint64(salt) + 0 * idx, 41) >> np.uint64(11)).astype(np.float64) + 0.5) / float(1 << 53)).reshape(shape)
+
+    K = keypoints
+    kp = np.stack([(height - 1) * uni((frames, K), 0), (width - 1) * uni((frames, K), 1)], axis=-1).astype(np.float32)
+    kp_id = np.full((frames, K), -1, np.int32)
+    slot_of = np.full((frames, landmarks), -1, np.int64)
+    for f in range(frames):
+        seen = np.flatnonzero(visible[f])
+        slots = np.argsort(uni((K,), 10 + f), kind="stable")[:len(seen)]
+        kp[f, slots] = kp_l[f, seen]
+        kp_id[f, slots] = seen
+        slot_of[f, seen] = slots
+    pairs = [(a, b) for a in range(frames) for b in range(a + 1, min(a + pair_span, frames - 1) + 1)]
+    P, M = len(pairs), K
+    pick = np.floor(4.0 * uni((P, M, 2), 2)).astype(np.int64)
+    looks = np.floor(K * uni((P, M, 2), 3)).astype(np.int64)
+    match_ij = np.choose(pick, [np.full_like(looks, -1), np.full_like(looks, 0x7FFFFFFF), looks, np.full_like(looks, -(1 << 31))]).astype(np.int32)
+    match_valid = np.zeros((P, M), bool)
+    for p, (a, b) in enumerate(pairs):
+        both = np.flatnonzero((slot_of[a] >= 0) & (slot_of[b] >= 0))
+        i, j = slot_of[a, both].copy(), slot_of[b, both].copy()
+        free = np.setdiff1d(np.arange(K), j)
+        free = free[np.argsort(uni((K,), 100 + 3 * p)[free], kind="stable")]
+        wrong = np.argsort(uni((landmarks,), 101 + 3 * p)[both], kind="stable")[:min(int(round(outlier_fraction * len(both))), len(free))]
+        j[wrong] = free[:len(wrong)]
+        at = np.argsort(uni((M,), 102 + 3 * p), kind="stable")[:len(both)]
+        match_ij[p, at, 0], match_ij[p, at, 1] = i, j
+        match_valid[p, at] = True
+    return kp, kp_id, np.array(pairs, np.int32).reshape(P, 2), match_ij, match_valid, R0, t0, R, t, X

@@ -1,0 +1,411 @@
+"""K28 landmark tracks without a GPU: the numpy oracle against brute force on tiny graphs, the triangulation arithmetic
+(csrc/tracks_math.h) compiled for the host in tests/native/tracks_host.cpp -- by hipcc, as plain C++, and once more under the
+host sanitizers as that stand-alone program -- against the float64 oracle, the host-side argument checks of the entries (MI_E_*
+before any launch), the header of its own, the binding and the library's export list, the pose-graph pins, the Python module's
+constructor, its refusal of CPU tensors and the alias import, the generator's contract, what every scene of
+tests/test_gpu_tracks.py is there for, and the MEASUREMENT behind the tolerance of tests/test_gpu_tracks.py, asserted against
+its constant so that neither can drift from the other."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import test_gpu_tracks as G
+import tracks_oracle as TO
+from helpers import SANITIZE, build_host, host_program, run_host
+from onnx_image_processing_amd import _native as N
+from onnx_image_processing_amd.synth import synth_track_window
+
+NULL, SHAPE, PARAM, CAPACITY, ALIGN = -1, -2, -3, -4, -5
+F32, F64 = np.float32, np.float64
+MARGIN = 4.0
+NAN, INF = float("nan"), float("inf")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return N.load_tracks()
+
+
+p_keepalive = []
+
+
+@pytest.fixture(scope="module")
+def p():
+    buf = ctypes.create_string_buffer(1 << 16)
+    p_keepalive.append(buf)
+    return (ctypes.addressof(buf) + 255) & ~255          # 256-byte aligned fake "device" pointer: never dereferenced by a refused call
+
+
+# ---- the oracle ---------------------------------------------------------------------------------------------------------------------
+def _brute_labels(n, edges):
+    """the smallest node each node reaches: boolean transitive closure"""
+    reach = np.eye(n, dtype=bool)
+    for u, v in edges:
+        reach[u, v] = reach[v, u] = True
+    for _ in range(n):
+        reach = reach | ((reach.astype(np.int32) @ reach.astype(np.int32)) > 0)
+    return reach.argmax(1)
+
+
+def test_oracle_components_against_brute_force_on_tiny_graphs():
+    rng = np.random.default_rng(0)
+    for trial in range(200):
+        n = int(rng.integers(2, 13))
+        edges = [tuple(int(x) for x in rng.integers(0, n, 2)) for _ in range(int(rng.integers(0, 2 * n)))]
+        assert np.array_equal(TO.components(n, edges), _brute_labels(n, edges)), (n, edges)
+
+
+def test_oracle_build_against_brute_force_on_tiny_windows():
+    """every definition once more from the closure alone: conflict, eligibility, order, cut, the four counts"""
+    rng = np.random.default_rng(1)
+    for trial in range(100):
+        F, K, P, M, L = int(rng.integers(2, 5)), int(rng.integers(1, 5)), int(rng.integers(1, 5)), int(rng.integers(1, 5)), int(rng.integers(1, 4))
+        pf = rng.integers(-1, F + 1, (P, 2)).astype(np.int32)
+        ij = rng.integers(-1, K + 1, (P, M, 2)).astype(np.int32)
+        mv = rng.random((P, M)) < 0.8
+        kv = (rng.random((F, K)) < 0.9) if trial % 2 else None
+        kp = rng.random((F, K, 2)).astype(F32)
+        mn = int(rng.integers(2, F + 1))
+        o = TO.build(kp, pf, ij, mv, kv, mn, L)
+        edges = [(a * K + i, b * K + j) for p_, (a, b) in enumerate(pf) for (i, j), v in zip(ij[p_], mv[p_])
+                 if v and 0 <= a < F and 0 <= b < F and a != b and 0 <= i < K and 0 <= j < K and (kv is None or (kv[a, i] and kv[b, j]))]
+        lab = _brute_labels(F * K, edges)
+        comps = [np.flatnonzero(lab == r) for r in np.unique(lab)]
+        big = [c for c in comps if len(c) >= 2]
+        conf = [c for c in big if len(set(c // K)) < len(c)]
+        elig = sorted((c for c in big if len(set(c // K)) == len(c) and len(c) >= mn), key=lambda c: (-len(c), c.min()))
+        assert o["counts"].tolist() == [len(big), len(conf), len(elig), min(len(elig), L)]
+        want_track = np.full(F * K, -1)
+        for c in conf:
+            want_track[c] = -2
+        for s, c in enumerate(elig[:L]):
+            want_track[c] = s
+            assert o["track_len"][s] == len(c) and sorted(o["track_kp"][c // K, s].tolist()) == sorted((c % K).tolist())
+            assert np.array_equal(o["track_keypoints"][c // K, s], kp[c // K, c % K])
+        assert np.array_equal(o["kp_track"].reshape(-1), want_track)
+        assert o["vis"].sum() == sum(len(c) for c in elig[:L]) and np.array_equal(o["vis"], o["track_kp"] >= 0)
+        assert not o["track_keypoints"][~o["vis"]].any() and not o["track_len"][len(elig):].any()
+
+
+def test_oracle_triangulation_recovers_planted_points():
+    rng = np.random.default_rng(2)
+    from onnx_image_processing_amd.synth import synth_ba_window
+    R, t, X = synth_ba_window(3, 5, 40, noise_px=0.0)[5:8]
+    q = np.einsum("fij,lj->fli", R, X) + t[:, None]
+    obs = (q[..., :2] / q[..., 2:]).astype(F32)
+    vis = rng.random((5, 40)) < 0.8
+    vis[:2] = True
+    o = TO.triangulate(R, t, obs, vis, 2, 1e-6, 1.0)
+    assert o["usable"].all() and o["front"].all() and np.abs(o["points"] - X).max() < 2e-3 and o["e2max"].max() < 1e-9
+    # the closed form against numpy's solve of the same normal equations
+    for l in range(40):
+        A, b = np.zeros((3, 3)), np.zeros(3)
+        for f in np.flatnonzero(vis[:, l]):
+            Rf, tf = R[f].astype(F32).astype(F64), t[f].astype(F32).astype(F64)
+            m = np.array([obs[f, l, 0], obs[f, l, 1], 1.0], F64)
+            d = Rf.T @ m / np.linalg.norm(m)
+            Pm = np.eye(3) - np.outer(d, d)
+            A += Pm
+            b += Pm @ (-Rf.T @ tf)
+        assert np.abs(np.linalg.solve(A, b) - o["points"][l]).max() < 1e-8
+
+
+def test_build_scenes_show_what_they_are_for():
+    """the oracle's own view of the GPU test's scenes: each holds the case it was made for"""
+    bo = G.build_oracle
+    assert bo("1x1")["counts"].tolist() == [1, 0, 1, 1]
+    assert bo("chain-conflict")["counts"].tolist() == [3, 1, 2, 2] and bo("chain-conflict")["track_len"].tolist() == [3, 2, 0]
+    assert bo("conflict-via-third")["counts"].tolist() == [2, 1, 1, 1] and (bo("conflict-via-third")["kp_track"] == -2).sum() == 4
+    assert bo("chain16-reversed")["track_len"].tolist() == [16, 16, 0, 0]
+    w = G.build_scene("chain16-reversed")
+    assert w["pair_frames"][0].tolist() == [14, 15] and w["pair_frames"][-1].tolist() == [0, 1]
+    lens = bo("cut")["track_len"].tolist()
+    assert bo("cut")["counts"].tolist() == [20, 0, 20, 8] and sorted(lens, reverse=True) == lens and len(set(lens)) > 1
+    assert bo("repeats")["counts"].tolist() == [4, 0, 4, 4]
+    assert bo("padding")["counts"].tolist() == [1, 0, 1, 1] and bo("padding")["track_len"].tolist() == [3, 0, 0, 0]
+    c = bo("synth-6x64")["counts"]
+    assert c[1] > 0 and c[2] > 16
+    w = G.build_scene("largest")
+    assert w["keypoints"].shape == (16, 1024, 2) and w["match_valid"].shape == (15, 1024) and bo("largest")["counts"][2] > 2048
+    w = G.build_scene("5x37")
+    assert w["keypoints"].shape[:2] == (5, 37) and bo("5x37")["counts"][2] > bo("5x37")["counts"][3] == 8
+
+
+def test_generator_contract():
+    g = synth_track_window(3, 6, 64, 48)
+    kp, kp_id, pf, ij, mv, R0, t0, R, t, X = g
+    assert kp.shape == (6, 64, 2) and kp.dtype == F32 and kp_id.shape == (6, 64) and kp_id.dtype == np.int32
+    assert pf.tolist() == [[0, 1], [0, 2], [1, 2], [1, 3], [2, 3], [2, 4], [3, 4], [3, 5], [4, 5]] and pf.dtype == np.int32
+    assert ij.shape == (9, 64, 2) and ij.dtype == np.int32 and mv.shape == (9, 64) and mv.dtype == bool
+    assert R0.dtype == F32 and R.shape == (6, 3, 3) and X.shape == (48, 3) and np.array_equal(R0[0], R[0].astype(F32))
+    for f in range(6):                                     # a landmark at most once per frame; clutter everywhere else
+        ids = kp_id[f][kp_id[f] >= 0]
+        assert len(set(ids.tolist())) == len(ids) and ids.max() < 48 and (kp_id[f] < 0).sum() >= 16
+    q = np.einsum("fij,lj->fli", R, X) + t[:, None]
+    K = G.CAMERA
+    for f, k in zip(*np.nonzero(kp_id >= 0)):             # a planted keypoint is its landmark's projection, 0.5 px noise
+        l = kp_id[f, k]
+        px = np.array([K[1, 1] * q[f, l, 1] / q[f, l, 2] + K[1, 2], K[0, 0] * q[f, l, 0] / q[f, l, 2] + K[0, 2]])
+        assert np.abs(kp[f, k] - px).max() < 3.0
+    wrong = total = 0
+    for p_, (a, b) in enumerate(pf):
+        i, j = ij[p_, mv[p_], 0], ij[p_, mv[p_], 1]
+        assert i.min() >= 0 and i.max() < 64 and j.min() >= 0 and j.max() < 64 and len(set(i.tolist())) == len(i) and len(set(j.tolist())) == len(j)
+        assert (kp_id[a, i] >= 0).all()
+        wrong += int((kp_id[a, i] != kp_id[b, j]).sum())
+        total += len(i)
+        pad = ij[p_, ~mv[p_]]
+        assert ((pad == -1) | (pad == 0x7FFFFFFF) | (pad == -(1 << 31)) | ((pad >= 0) & (pad < 64))).all() and (pad < 0).any() and (pad == 0x7FFFFFFF).any()
+    assert 0.08 * total <= wrong <= 0.12 * total and (~mv).sum() > 0
+    again = synth_track_window(3, 6, 64, 48)
+    assert all(np.array_equal(x, y) for x, y in zip(g, again))
+    clean = synth_track_window(3, 6, 64, 48, outlier_fraction=0.0)
+    o = TO.build(*clean[:1], *clean[2:5], None, 2, 64)
+    assert o["counts"][1] == 0 and G.purity(clean[1], o["eligible"]).all()
+    for bad in (dict(frames=1), dict(landmarks=65), dict(pair_span=6), dict(miss=1.0)):
+        with pytest.raises(ValueError):
+            synth_track_window(**{**dict(seed=1, frames=6, keypoints=64, landmarks=48), **bad})
+
+
+def test_end_to_end_scene_gives_the_oracle_room():
+    """the two conditions of the GPU end-to-end test, on the oracle: >= 95 % of the point_ok landmarks pure, >= 90 % of the
+    pure eligible tracks point_ok"""
+    w = G.e2e_window()
+    R0, t0 = G.e2e_start(w)
+    o = TO.build(w[0], w[2], w[3], w[4], None, 2, 64)
+    tri = TO.triangulate(R0, t0, TO.normalise(o["track_keypoints"], G.CAMERA), o["vis"], 2, G.MAX_E2, G.MAX_COS)
+    pure = G.purity(w[1], o["eligible"])
+    ok = tri["point_ok"][:len(pure)]
+    print(f"counts {o['counts'].tolist()}, pure {int(pure.sum())}, point_ok {int(ok.sum())}")
+    assert (ok & pure).sum() >= 0.95 * ok.sum() and (ok & pure).sum() >= 0.90 * pure.sum() and ok.sum() >= 10 and not pure.all()
+    assert not G.excused(tri).any()
+
+
+# ---- the triangulation arithmetic on the host -----------------------------------------------------------------------------------
+tracks_host = host_program("tracks_host.cpp", hip=True)
+tracks_plain = host_program("tracks_host.cpp", hip=False)
+
+
+def _tri_text(names=G.TRI_NAMES):
+    lines = []
+    for name in names:
+        w = G.tri_scene(name)
+        for b in range(len(w["R"])):
+            F, L = w["vis"][b].shape
+            lines.append(f"{F} {L} {G.TRI_MIN_VIEWS} {G.MAX_E2:.9g} {G.MAX_COS:.9g}")
+            for f in range(F):
+                lines.append(" ".join("%.9g" % x for x in np.concatenate([w["R"][b, f].ravel(), w["t"][b, f]])))
+            for l in range(L):
+                lines.append(" ".join(f"{int(w['vis'][b, f, l])} {w['obs'][b, f, l, 0]:.9g} {w['obs'][b, f, l, 1]:.9g}" for f in range(F)))
+    return "\n".join(lines) + "\n"
+
+
+def _tri_wants(names=G.TRI_NAMES):
+    return [o for name in names for o in G.tri_oracle(name)]
+
+
+@pytest.fixture(scope="module")
+def measured(tracks_host, tracks_plain):
+    """the largest deviation of the host-compiled tracks_math.h from the float64 oracle over every triangulation scene"""
+    text = _tri_text()
+    raw = run_host(tracks_host, "tri", text)
+    assert raw == run_host(tracks_plain, "tri", text)            # the plain C++ build returns the hipcc build's bits
+    got = np.array([[float(v) for v in ln] for ln in raw], F64)
+    m, at = dict(points=0.0, e2max=0.0, cos_par=0.0, flags=0), 0
+    for o in _tri_wants():
+        L = len(o["point_ok"])
+        g = got[at:at + L]
+        at += L
+        m["flags"] += int((g[:, 0] != o["point_ok"]).sum() + (g[:, 1] != o["usable"]).sum() + (g[:, 2] != o["front"]).sum() + (g[:, 3] != o["seen"]).sum())
+        m["points"] = max(m["points"], (np.abs(g[:, 4:7] - o["points"]) / np.maximum(np.abs(o["points"]).max(-1, keepdims=True), 1.0)).max())
+        fin = np.isfinite(o["e2max"])
+        assert np.array_equal(np.isinf(g[:, 7]), ~fin)
+        m["e2max"] = max(m["e2max"], (np.abs(g[fin, 7] - o["e2max"][fin]) / G.MAX_E2).max() if fin.any() else 0.0)
+        m["cos_par"] = max(m["cos_par"], np.abs(g[:, 8] - o["cos_par"]).max())
+    assert at == len(got)
+    print("host tracks_math.h vs float64 oracle: " + ", ".join(f"{k} {v:.3e}" for k, v in m.items()))
+    return m
+
+
+def test_native_triangulation_matches_the_float64_oracle(measured):
+    assert measured["flags"] == 0
+    assert max(measured["points"], measured["e2max"], measured["cos_par"]) <= 1e-12         # float64, the same order: rounding of a few operations at most
+
+
+def test_gpu_tolerance_is_four_times_its_measurement(measured):
+    worst = max(measured["points"], measured["e2max"], measured["cos_par"])
+    assert MARGIN == G.MARGIN and MARGIN * worst <= G.TRI_TOL <= max(16 * MARGIN * worst, 0.0)
+    for name in G.TRI_NAMES:                                # at most 1 % of a scene's landmarks may be excused; every degenerate case is one
+        for o in G.tri_oracle(name):
+            assert G.excused(o).sum() <= 0.01 * len(o["point_ok"])
+    o = G.tri_oracle("degenerate")[0]
+    assert o["point_ok"].tolist() == [True, False, True, False, False, False, False]
+    assert not o["usable"][1] and o["usable"][3] and o["e2max"][3] > G.MAX_E2 and not o["usable"][4] and not o["usable"][5]
+    assert o["usable"][6] and o["e2max"][6] <= G.MAX_E2 and o["cos_par"][6] > G.MAX_COS
+    o = G.tri_oracle("behind")[0]
+    assert o["usable"][0] and not o["front"][0] and not o["point_ok"][0]
+    assert sum(int(o["point_ok"].sum()) for o in G.tri_oracle("tracks")) >= 40
+
+
+def test_native_harness_under_the_host_sanitizers(tmp_path):
+    """the same stand-alone program built with the host's address and undefined-behaviour sanitizers, run once"""
+    exe = build_host(tmp_path, "tracks_host.cpp", hip=True, extra=SANITIZE)
+    names = ["tracks", "ba-5x130", "degenerate", "behind"]
+    assert len(run_host(exe, "tri", _tri_text(names))) == sum(len(o["point_ok"]) for o in _tri_wants(names))
+
+
+# ---- the header of its own, the binding and the library ------------------------------------------------------------------------
+def test_the_tracks_header_is_bound_and_exported_and_compiles_as_c(lib, tmp_path):
+    """include/mi355x_match_tracks.h: every MI_API declaration is read, bound with its types and exported by
+    lib/libmi355x_match_tracks.so, which exports nothing else, and by no other library; its limits are the compiler's values;
+    it compiles as C99 on its own (it includes mi355x_match.h); ABI 3"""
+    import os
+    import re
+    import shutil
+    import subprocess
+    from ctypes import c_float, c_int, c_size_t, c_void_p
+    include = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(include, "mi355x_match_tracks.h")).read(), flags=re.S)
+    declared = sorted(set(re.findall(r"\b(mi_[a-z0-9_]+)\s*\(", text)))
+    assert declared == sorted(N.TRACKS_SIGNATURES) == ["mi_tracks_build", "mi_tracks_triangulate", "mi_tracks_workspace_bytes"]
+    assert len(re.findall(r"\bMI_API\b", re.sub(r"^\s*#.*$", "", text, flags=re.M))) == 3
+    assert not set(N.TRACKS_SIGNATURES) & (set(N.SIGNATURES) | set(N.EXTRA_SIGNATURES)) and N.load().mi_abi_version() == 3
+    vp, i, f = c_void_p, c_int, c_float
+    assert N.TRACKS_SIGNATURES["mi_tracks_workspace_bytes"] == [i] * 6 and N.RESTYPES["mi_tracks_workspace_bytes"] is c_size_t
+    assert N.TRACKS_SIGNATURES["mi_tracks_build"] == [vp] * 5 + [i] * 7 + [vp] * 7 + [c_size_t, vp] and N.RESTYPES["mi_tracks_build"] is i
+    assert N.TRACKS_SIGNATURES["mi_tracks_triangulate"] == [vp] * 4 + [i, i, i, i, f, f] + [vp] * 6
+    for name, argtypes in N.TRACKS_SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert list(fn.argtypes) == argtypes and fn.restype is N.RESTYPES[name], name
+    from onnx_image_processing_amd.build import LIB, PGO_LIB, TRACKS_LIB, TRACKS_SOURCES
+
+    def exports(path):
+        nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        return sorted(ln.split()[-1] for ln in nm.splitlines() if ln.strip())
+    assert exports(TRACKS_LIB) == declared and TRACKS_SOURCES == ["tracks.hip"]                 # ... and nothing else
+    assert not set(declared) & set(exports(LIB)) and not set(declared) & set(exports(PGO_LIB))
+    assert N.library_of("mi_tracks_build") is lib and N.library_of("mi_tracks_workspace_bytes") is lib
+    assert N.TRACKS_CONSTANTS == dict(MI_TRACKS_MAX_FRAMES=16, MI_TRACKS_MAX_KEYPOINTS=1024, MI_TRACKS_MAX_PAIRS=120, MI_TRACKS_MAX_MATCHES=1024)
+    assert N.TRACKS_CONSTANTS["MI_TRACKS_MAX_FRAMES"] == N.MI_BA_MAX_FRAMES
+    if shutil.which("gcc") is None:
+        pytest.skip("gcc not available")
+    src = tmp_path / "tracks_header.c"
+    src.write_text('#include <stdio.h>\n#include "mi355x_match_tracks.h"\nint main(void) {\n'
+                   + "".join(f'  printf("{k} %d\\n", (int){k});\n' for k in N.TRACKS_CONSTANTS) + "  return MI_OK;\n}\n")
+    exe = str(tmp_path / "tracks_header")
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", f"-I{include}", str(src), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()
+    assert dict(zip(out[::2], map(int, out[1::2]))) == N.TRACKS_CONSTANTS
+
+
+def test_the_pose_graph_pins_still_hold():
+    assert sorted(N.EXTRA_SIGNATURES) == ["mi_pgo_cost", "mi_pgo_linearise", "mi_pgo_refine", "mi_pgo_workspace_bytes"]
+    assert N.EXTRA_CONSTANTS == dict(MI_PGO_MAX_NODES=1024, MI_PGO_MAX_EDGES=4096, MI_PGO_MAX_ITERATIONS=32, MI_PGO_MAX_PCG=256)
+    assert N.library_of("mi_ba_cost") is N.load() and N.library_of("mi_pgo_cost") is N.load_pgo() and N.load_pgo() is not N.load_tracks()
+
+
+# ---- argument checks ------------------------------------------------------------------------------------------------------------
+def test_workspace_size(lib):
+    wb = lib.mi_tracks_workspace_bytes
+    assert wb(1, 2, 1, 1, 1, 1) == 16 and wb(3, 6, 64, 9, 64, 32) == 3 * wb(1, 6, 64, 9, 64, 32) and wb(1, 6, 64, 9, 63, 32) % 16 == 0
+    assert wb(1, 16, 1024, 120, 1024, 2048) == 120 * 1024 * 4 and wb(65535, 16, 1024, 120, 1024, 2048) == 65535 * 120 * 1024 * 4
+    for bad in ((0, 6, 64, 9, 64, 32), (3, 1, 64, 9, 64, 32), (3, 6, 0, 9, 64, 32), (3, 6, 64, 0, 64, 32), (3, 6, 64, 9, 0, 32), (3, 6, 64, 9, 64, 0),
+                (65536, 6, 64, 9, 64, 32), (3, 17, 64, 9, 64, 32), (3, 6, 1025, 9, 64, 32), (3, 6, 64, 121, 64, 32), (3, 6, 64, 9, 1025, 32),
+                (3, 6, 64, 9, 64, 2049)):
+        assert wb(*bad) == 0, bad
+
+
+def test_build_argument_checks(lib, p):
+    f, need = lib.mi_tracks_build, lib.mi_tracks_workspace_bytes(3, 6, 64, 9, 64, 32)
+    for i in (0, 1, 2, 4, 12, 13, 14, 15, 16, 17, 18):
+        a = [p, p, p, p, p, 3, 6, 64, 9, 64, 2, 32, p, p, p, p, p, p, p, need, None]
+        a[i] = None
+        assert f(*a) == NULL, i
+    a = [p, p, p, None, p, 0, 6, 64, 9, 64, 2, 32, p, p, p, p, p, p, p, need, None]             # kp_valid is optional
+    assert f(*a) == SHAPE
+
+    def call(batch=3, fr=6, k=64, pairs=9, m=64, mn=2, l=32, ws=p, wbytes=need):
+        return f(p, p, p, p, p, batch, fr, k, pairs, m, mn, l, p, p, p, p, p, p, ws, wbytes, None)
+    assert call(batch=0) == SHAPE and call(fr=1) == SHAPE and call(k=0) == SHAPE and call(pairs=0) == SHAPE and call(m=0) == SHAPE and call(l=0) == SHAPE
+    assert call(fr=-3) == SHAPE and call(batch=0, fr=17) == SHAPE
+    assert call(batch=65536) == PARAM and call(fr=17) == PARAM and call(k=1025) == PARAM and call(pairs=121) == PARAM and call(m=1025) == PARAM
+    assert call(l=2049) == PARAM
+    assert call(mn=1) == PARAM and call(mn=7) == PARAM and call(mn=0) == PARAM
+    assert call(wbytes=need - 1) == CAPACITY and call(wbytes=0) == CAPACITY and call(ws=p + 4) == ALIGN
+    assert call(mn=1, wbytes=0) == PARAM and call(k=0, mn=1) == SHAPE              # shape, then parameters, then the workspace
+
+
+def test_triangulate_argument_checks(lib, p):
+    f = lib.mi_tracks_triangulate
+    for i in (0, 1, 2, 3, 10, 11, 12, 13, 14):
+        a = [p, p, p, p, 3, 6, 32, 2, 1e-4, 0.9998, p, p, p, p, p, None]
+        a[i] = None
+        assert f(*a) == NULL, i
+
+    def call(batch=3, fr=6, l=32, mn=2, e2=1e-4, cs=0.9998):
+        return f(p, p, p, p, batch, fr, l, mn, e2, cs, p, p, p, p, p, None)
+    assert call(batch=0) == SHAPE and call(fr=1) == SHAPE and call(l=0) == SHAPE and call(l=-1) == SHAPE
+    assert call(batch=65536) == PARAM and call(fr=17) == PARAM and call(l=2049) == PARAM
+    assert call(mn=1) == PARAM and call(mn=7) == PARAM
+    assert call(e2=0.0) == PARAM and call(e2=-1.0) == PARAM and call(e2=NAN) == PARAM and call(e2=INF) == PARAM
+    assert call(cs=-1.0) == PARAM and call(cs=1.0000001) == PARAM and call(cs=NAN) == PARAM and call(cs=-INF) == PARAM
+    assert call(fr=1, mn=0) == SHAPE
+    assert N.load().mi_abi_version() == 3
+
+
+# ---- the module -----------------------------------------------------------------------------------------------------------------------
+def test_module_constructor_and_cpu_refusal():
+    from onnx_image_processing_amd import ops
+    from onnx_image_processing_amd.pytorch_model.geometry import LandmarkTracks
+    assert (ops.TRACKS_MAX_FRAMES, ops.TRACKS_MAX_KEYPOINTS, ops.TRACKS_MAX_PAIRS, ops.TRACKS_MAX_MATCHES) == (16, 1024, 120, 1024)
+    K = torch.from_numpy(G.CAMERA).float()
+    m = LandmarkTracks(K)
+    assert (m.max_landmarks, m.min_views, m.max_reproj_px, m.min_parallax_deg) == (2048, 2, 3.0, 1.0) and abs(m.max_cos - np.cos(np.radians(1.0))) < 1e-12
+    for kw in (dict(max_landmarks=0), dict(max_landmarks=2049), dict(min_views=1), dict(min_views=17), dict(max_reproj_px=0.0),
+               dict(max_reproj_px=float("nan")), dict(min_parallax_deg=-1.0), dict(min_parallax_deg=180.0)):
+        with pytest.raises(ValueError):
+            LandmarkTracks(K, **kw)
+    with pytest.raises(ValueError):
+        LandmarkTracks(torch.eye(4))
+    w = G.build_scene("synth-6x64")
+    a = [torch.from_numpy(np.ascontiguousarray(w[k])) for k in ("keypoints", "pair_frames", "match_ij", "match_valid")]
+    R, t = torch.eye(3).expand(6, 3, 3).contiguous(), torch.zeros(6, 3)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        m(*a, R, t)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        m(*(x[None] for x in a), R[None], t[None])
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        m.triangulate(R, t, torch.zeros(6, 8, 2), torch.ones(6, 8, dtype=torch.bool))
+    with pytest.raises(RuntimeError, match=r"\(B, F, K, 2\) or \(F, K, 2\)"):
+        m.build(a[0][..., :1], *a[1:])
+    b = [x[None] for x in a]
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        ops.tracks_build(*b)
+    with pytest.raises(RuntimeError, match="keypoints must be"):
+        ops.tracks_build(a[0], *b[1:])
+    with pytest.raises(RuntimeError, match="expected pair_frames"):
+        ops.tracks_build(b[0], b[1][:, :5], *b[2:])
+    with pytest.raises(RuntimeError, match="supported: 2 .. 16"):
+        ops.tracks_build(b[0][:, :1], *b[1:])
+    with pytest.raises(RuntimeError, match="min_views"):
+        ops.tracks_build(*b, None, 7)
+    obs, vis = torch.zeros(1, 6, 8, 2), torch.ones(1, 6, 8, dtype=torch.bool)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        ops.tracks_triangulate(R[None], t[None], obs, vis)
+    with pytest.raises(RuntimeError, match="expected t"):
+        ops.tracks_triangulate(R[None], t[None, :5], obs, vis)
+    with pytest.raises(RuntimeError, match="max_e2"):
+        ops.tracks_triangulate(R[None], t[None], obs, vis, 2, 0.0)
+    with pytest.raises(RuntimeError, match="max_e2"):
+        ops.tracks_triangulate(R[None], t[None], obs, vis, 2, 1e-4, -1.0)
+
+
+def test_exports_resolve_through_the_alias():
+    import onnx_image_processing_amd.pytorch_model.geometry as real
+    from pytorch_model.geometry import LandmarkTracks
+    assert LandmarkTracks is real.LandmarkTracks and "LandmarkTracks" in real.__all__
+    from pytorch_model.geometry.landmark_tracks import LandmarkTracks as again
+    assert again is LandmarkTracks

@@ -160,6 +160,14 @@ def main():
         res["pgo_cost"] = (timeit(lambda: ops.pgo_cost(*pg[:6], None, 3.0), args.iters), 0.0)
         res["pgo_linearise"] = (timeit(lambda: ops.pgo_linearise(*pg, None, 3.0), args.iters), 0.0)
         res["pgo_refine(10 x 64)"] = (timeit(lambda: ops.pgo_refine(*pg, None, 10, 64, 3.0), args.iters), 0.0)
+    if "tracks" in args.which:                 # K28 (not in the default list): one window of 8 frames x 512 keypoints per image of the batch
+        from onnx_image_processing_amd.synth import rgbd_camera, synth_track_window
+        g = [synth_track_window(700 + i, 8, 512, 400) for i in range(8)]
+        tw = [torch.from_numpy(np.ascontiguousarray(np.stack([g[i % 8][j] for i in range(n)]))).to(dev) for j in (0, 2, 3, 4, 5, 6)]
+        res["tracks_build"] = (timeit(lambda: ops.tracks_build(*tw[:4], None, 2, 512), args.iters), 0.0)
+        tk = ops.tracks_build(*tw[:4], None, 2, 512)
+        tobs = ops.normalise_keypoints(tk[2], torch.from_numpy(np.linalg.inv(rgbd_camera())).float().to(dev))
+        res["tracks_triangulate"] = (timeit(lambda: ops.tracks_triangulate(tw[4], tw[5], tobs, tk[1], 2, 3.3e-5, 0.99985), args.iters), 0.0)
     z, pitch = ops.cost_logscores_bits(bits, b2, True, 0.05)
     if "sinkhorn" in args.which:
         for mode, name in ((1, "sinkhorn_fused log-partials"), (2, "sinkhorn_fused prob-partials v1"),
