@@ -116,10 +116,15 @@ RESTYPES.update(_extra_restypes)
 # (lib/libmi355x_match_tracks.so, load_tracks()), in dictionaries of its own: TRACKS_CONSTANTS["MI_TRACKS_MAX_FRAMES"], ...
 TRACKS_SIGNATURES, _tracks_restypes, _, TRACKS_CONSTANTS = _read("mi355x_match_tracks.h")
 RESTYPES.update(_tracks_restypes)
+# include/mi355x_match_localmap.h: the local-map tracking section (K29), the same again (lib/libmi355x_match_localmap.so,
+# load_localmap()): LOCALMAP_CONSTANTS["MI_LOCALMAP_MAX_LANDMARKS"], ...
+LOCALMAP_SIGNATURES, _localmap_restypes, _, LOCALMAP_CONSTANTS = _read("mi355x_match_localmap.h")
+RESTYPES.update(_localmap_restypes)
 
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_debug.so")
 PGO_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_pgo.so")
 TRACKS_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_tracks.so")
+LOCALMAP_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_localmap.so")
 
 _lib = None            # the library every call() goes through: the product, unless inside debug_library()
 _product = None
@@ -173,8 +178,21 @@ def load_tracks() -> ctypes.CDLL:
     return _tracks
 
 
+_localmap = None
+
+
+def load_localmap() -> ctypes.CDLL:
+    """lib/libmi355x_match_localmap.so, the entries of include/mi355x_match_localmap.h, loaded once."""
+    global _localmap
+    if _localmap is None:
+        _localmap = _open(LOCALMAP_LIB_PATH, LOCALMAP_SIGNATURES)
+    return _localmap
+
+
 def library_of(name: str) -> ctypes.CDLL:
     """The library that exports the entry `name`."""
+    if name in LOCALMAP_SIGNATURES:
+        return load_localmap()
     if name in TRACKS_SIGNATURES:
         return load_tracks()
     return load_pgo() if name in EXTRA_SIGNATURES else load()

@@ -1723,6 +1723,98 @@ def tracks_triangulate(r: torch.Tensor, t: torch.Tensor, obs: torch.Tensor, vis:
     return points, point_ok.view(torch.bool), vis_out.view(torch.bool), e2max, cos_par
 
 
+# ---- K29 local-map tracking (include/mi355x_match_localmap.h) --------------------------------------------------------------------
+
+LOCALMAP_MAX_LANDMARKS = N.LOCALMAP_CONSTANTS["MI_LOCALMAP_MAX_LANDMARKS"]
+LOCALMAP_MAX_KEYPOINTS = N.LOCALMAP_CONSTANTS["MI_LOCALMAP_MAX_KEYPOINTS"]
+LOCALMAP_MAX_FRAMES = N.LOCALMAP_CONSTANTS["MI_LOCALMAP_MAX_FRAMES"]
+
+
+def _localmap_bits(bits: torch.Tensor, lead: int, what: str):
+    """Packed descriptors (..., W) int32 -- as `forward_bits` returns them -- or uint32 with `lead` leading dimensions, W = 8 or
+    16, as the C ABI reads them: (int32 tensor, W)."""
+    if bits.dim() != lead + 1 or bits.dtype not in (torch.int32, torch.uint32):
+        raise RuntimeError(f"{what} must be {lead + 1}-dimensional packed descriptors (..., W) int32, got {tuple(bits.shape)} {bits.dtype}")
+    b = bits.contiguous()
+    if b.dtype != I32:
+        b = b.view(I32)
+    if int(b.shape[-1]) not in (8, 16):
+        raise RuntimeError(f"{what}: {32 * int(b.shape[-1])}-bit descriptors, supported: 256 and 512")
+    return b, int(b.shape[-1])
+
+
+def localmap_descriptors(bits: torch.Tensor, track_kp: torch.Tensor):
+    """`mi_localmap_descriptors`: a representative descriptor per landmark slot.  bits (B, F, K, W) packed hard bits of the
+    window's frames, track_kp (B, F, L) integer as tracks_build returns it (anything outside 0 .. K - 1: not seen) ->
+    (rep_bits (B, L, W) int32: the words of the view whose median Hamming distance to the slot's views is smallest, the
+    lowest frame on a tie; rep_frame (B, L) int32: its frame, -1 for a slot nobody sees; rep_median (B, L) int32: that median,
+    num_bits + 1 for a slot nobody sees)."""
+    bb, w = _localmap_bits(bits, 3, "localmap_descriptors: bits")
+    b, f, k = (int(v) for v in bb.shape[:3])
+    if track_kp.dim() != 3 or tuple(track_kp.shape[:2]) != (b, f):
+        raise RuntimeError(f"localmap_descriptors: expected track_kp ({b}, {f}, L), got {tuple(track_kp.shape)}")
+    l = int(track_kp.shape[2])
+    if b < 1 or not 1 <= f <= LOCALMAP_MAX_FRAMES or not 1 <= k <= LOCALMAP_MAX_KEYPOINTS or not 1 <= l <= LOCALMAP_MAX_LANDMARKS:
+        raise RuntimeError(f"localmap_descriptors: F = {f} frames, K = {k} keypoints and L = {l} landmarks, supported: 1 .. {LOCALMAP_MAX_FRAMES}, "
+                           f"1 .. {LOCALMAP_MAX_KEYPOINTS} and 1 .. {LOCALMAP_MAX_LANDMARKS}")
+    tk = track_kp.to(I32).contiguous()
+    ptrs = (N.dev(bb, I32, "bits"), N.dev(tk, I32, "track_kp"))
+    dev = bb.device
+    rep_bits = torch.empty((b, l, w), dtype=I32, device=dev)
+    rep_frame = torch.empty((b, l), dtype=I32, device=dev)
+    rep_median = torch.empty((b, l), dtype=I32, device=dev)
+    N.call("mi_localmap_descriptors", *ptrs, b, f, k, l, 32 * w, rep_bits.data_ptr(), rep_frame.data_ptr(), rep_median.data_ptr(),
+           N.stream_ptr())
+    return rep_bits, rep_frame, rep_median
+
+
+def localmap_match(points: torch.Tensor, point_valid: torch.Tensor | None, rep_bits: torch.Tensor, r: torch.Tensor, t: torch.Tensor,
+                   cam: torch.Tensor, kp: torch.Tensor, kp_valid: torch.Tensor | None, kp_bits: torch.Tensor, height: int, width: int,
+                   min_depth: float, max_depth: float, radius: float, max_distance: int, ratio: float):
+    """`mi_localmap_match`: one frame per batch item against that item's landmarks, each searched inside a window round its
+    projection.  points (B, L, 3), point_valid (B, L) or None, rep_bits (B, L, W), the predicted pose r (B, 3, 3), t (B, 3) with
+    X_c = R X + t, cam (B, 4) = fx, fy, cx, cy, kp (B, K, 2) pixel (y, x), kp_valid (B, K) or None, kp_bits (B, K, W) ->
+    (proj (B, L, 2) float32 pixel (y, x) or (-1, -1), lm_state (B, L) uint8: 0 not in view, 1 empty window, 2 failed the distance
+    or ratio test, 3 lost its keypoint, 4 kept; lm_kp (B, L) int32; lm_distance (B, L) int32; match_keypoints (B, L, 2) float32;
+    kp_lm (B, K) int32; counts (B, 5) int32)."""
+    xx, rr, tt, cc, kk = (a.float().contiguous() for a in (points, r, t, cam, kp))
+    if xx.dim() != 3 or xx.shape[-1] != 3 or kk.dim() != 3 or kk.shape[-1] != 2:
+        raise RuntimeError(f"localmap_match: points must be (B, L, 3) and kp (B, K, 2), got {tuple(points.shape)} and {tuple(kp.shape)}")
+    b, l, k = int(xx.shape[0]), int(xx.shape[1]), int(kk.shape[1])
+    rb, w = _localmap_bits(rep_bits, 2, "localmap_match: rep_bits")
+    kb, kw = _localmap_bits(kp_bits, 2, "localmap_match: kp_bits")
+    if (tuple(rb.shape) != (b, l, w) or tuple(kb.shape) != (b, k, w) or kw != w or tuple(rr.shape) != (b, 3, 3) or tuple(tt.shape) != (b, 3)
+            or tuple(cc.shape) != (b, 4) or kk.shape[0] != b or (point_valid is not None and tuple(point_valid.shape) != (b, l))
+            or (kp_valid is not None and tuple(kp_valid.shape) != (b, k))):
+        raise RuntimeError(f"localmap_match: expected rep_bits ({b}, {l}, W), r ({b}, 3, 3), t ({b}, 3), cam ({b}, 4), kp ({b}, {k}, 2), kp_bits "
+                           f"({b}, {k}, W) and masks ({b}, {l}) / ({b}, {k}) or None, got {tuple(rep_bits.shape)}, {tuple(r.shape)}, {tuple(t.shape)}, "
+                           f"{tuple(cam.shape)}, {tuple(kp.shape)}, {tuple(kp_bits.shape)}, {None if point_valid is None else tuple(point_valid.shape)} "
+                           f"and {None if kp_valid is None else tuple(kp_valid.shape)}")
+    if b < 1 or b > 65535 or not 1 <= l <= LOCALMAP_MAX_LANDMARKS or not 1 <= k <= LOCALMAP_MAX_KEYPOINTS:
+        raise RuntimeError(f"localmap_match: B = {b}, L = {l} landmarks and K = {k} keypoints, supported: 1 .. 65535, 1 .. {LOCALMAP_MAX_LANDMARKS} "
+                           f"and 1 .. {LOCALMAP_MAX_KEYPOINTS}")
+    inf = float("inf")
+    if not (0 < min_depth < max_depth < inf) or not (0 < radius < inf) or not 0 <= int(max_distance) <= 32 * w or not (0 < ratio <= 1) \
+            or int(height) < 1 or int(width) < 1:
+        raise RuntimeError(f"localmap_match: need 0 < min_depth < max_depth < inf, 0 < radius < inf, 0 <= max_distance <= {32 * w}, 0 < ratio <= 1 "
+                           f"and height, width >= 1, got {min_depth}, {max_depth}, {radius}, {max_distance}, {ratio}, {height}, {width}")
+    pv, kv = _validity_bytes(point_valid), _validity_bytes(kp_valid)
+    ptrs = (N.dev(xx, F32, "points"), N.opt(pv, U8, "point_valid"), N.dev(rb, I32, "rep_bits"), N.dev(rr, F32, "r"), N.dev(tt, F32, "t"),
+            N.dev(cc, F32, "cam"), N.dev(kk, F32, "kp"), N.opt(kv, U8, "kp_valid"), N.dev(kb, I32, "kp_bits"))
+    dev = xx.device
+    proj = torch.empty((b, l, 2), dtype=F32, device=dev)
+    lm_state = torch.empty((b, l), dtype=U8, device=dev)
+    lm_kp = torch.empty((b, l), dtype=I32, device=dev)
+    lm_distance = torch.empty((b, l), dtype=I32, device=dev)
+    match_keypoints = torch.empty((b, l, 2), dtype=F32, device=dev)
+    kp_lm = torch.empty((b, k), dtype=I32, device=dev)
+    counts = torch.empty((b, 5), dtype=I32, device=dev)
+    N.call("mi_localmap_match", *ptrs, b, l, k, 32 * w, int(height), int(width), float(min_depth), float(max_depth), float(radius),
+           int(max_distance), float(ratio), proj.data_ptr(), lm_state.data_ptr(), lm_kp.data_ptr(), lm_distance.data_ptr(),
+           match_keypoints.data_ptr(), kp_lm.data_ptr(), counts.data_ptr(), N.stream_ptr())
+    return proj, lm_state, lm_kp, lm_distance, match_keypoints, kp_lm, counts
+
+
 # ---- K26 loop-closure retrieval (include/mi355x_match.h, "loop-closure retrieval") -------------------------------------------
 
 PLACE_MAX_DESCRIPTORS = N.MI_PLACE_MAX_DESCRIPTORS

@@ -5,6 +5,7 @@ from .direct_rgbd import DirectRgbdRefiner
 from .direct_tsdf_volume import DirectTsdfVolume
 from .essential_matrix_estimator import EssentialMatrixEstimator
 from .landmark_tracks import LandmarkTracks
+from .local_map import LocalMapTracker
 from .planar_pose import HomographyEstimator, PlanarPoseEstimator, TwoViewPoseEstimator
 from .pose_graph import PoseGraphOptimizer
 from .relative_pose import RelativePoseEstimator, triangulate_points
@@ -12,4 +13,4 @@ from .rgbd_pose import RgbdPoseEstimator
 from .tsdf_volume import TsdfVolume
 
 __all__ = ["AbsolutePoseEstimator", "BundleAdjuster", "DenseRgbdRefiner", "DirectRgbdRefiner", "DirectTsdfVolume", "EssentialMatrixEstimator", "HomographyEstimator",
-           "LandmarkTracks", "PlanarPoseEstimator", "PoseGraphOptimizer", "RelativePoseEstimator", "RgbdPoseEstimator", "TsdfVolume", "TwoViewPoseEstimator", "triangulate_points"]
+           "LandmarkTracks", "LocalMapTracker", "PlanarPoseEstimator", "PoseGraphOptimizer", "RelativePoseEstimator", "RgbdPoseEstimator", "TsdfVolume", "TwoViewPoseEstimator", "triangulate_points"]

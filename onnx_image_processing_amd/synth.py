@@ -667,3 +667,50 @@ def synth_track_window(seed: int, frames: int, keypoints: int, landmarks: int, p
         match_ij[p, at, 0], match_ij[p, at, 1] = i, j
         match_valid[p, at] = True
     return kp, kp_id, np.array(pairs, np.int32).reshape(P, 2), match_ij, match_valid, R0, t0, R, t, X
+
+
+def synth_localmap_window(seed: int, frames: int, keypoints: int, landmarks: int, num_bits: int, flip: float = 0.1, twins: float = 0.25,
+                          rotation_deg: float = 2.0, translation: float = 0.05, **window):
+    """A window for the local-map kernels (K29): synth_track_window(seed, frames, keypoints, landmarks, **window)'s tuple
+    (keypoints, kp_id, pair_frames, match_ij, match_valid, R0, t0, R, t, X) followed by (bits, R_pred, t_pred, twin_of).
+
+    Descriptors.  Every landmark has a BASE descriptor of num_bits uniform random bits (bit b in bit b % 32 of word b // 32).
+    round(twins * landmarks) landmarks, chosen among 1 .. landmarks - 1 by a hashed ranking, are TWINS: taken in ascending
+    order, twin l copies the base of a hashed landmark below l (repeated texture: what the ratio test and the claims are for);
+    twin_of (landmarks,) int32 is that landmark, -1 for the others.  bits (frames, keypoints, num_bits / 32) int32: a planted
+    keypoint holds its landmark's base with every bit flipped with probability `flip`, independently per observation; clutter
+    holds independent uniform bits.
+    The predicted pose of the LAST frame (float32): the truth R[-1], t[-1] moved by E, the rotation of rotation_deg degrees
+    about the axis (1, -1, 1) / sqrt 3, and by d = translation * (1, 1, 1) / sqrt 3 metres: R_pred = E R[-1], t_pred = E t[-1] + d.
+    Hashed integers only: the same arrays everywhere."""
+    if num_bits % 32 != 0 or num_bits <= 0:
+        raise ValueError(f"synth_localmap_window: num_bits must be a positive multiple of 32, got {num_bits}")
+    if not (0.0 <= flip <= 1.0 and 0.0 <= twins <= 1.0):
+        raise ValueError(f"synth_localmap_window: flip and twins must lie in [0, 1], got {flip} and {twins}")
+    base_window = synth_track_window(seed, frames, keypoints, landmarks, **window)
+    kp_id, R, t = base_window[1], base_window[7], base_window[8]
+    words = num_bits // 32
+
+    def draw(rows, cols, salt):                      # (rows, cols) uint64 hashes
+        r, c = np.broadcast_arrays(np.arange(rows, dtype=np.uint64)[:, None], np.arange(cols, dtype=np.uint64)[None, :])
+        return _hash3(seed, r, c, salt)
+
+    base = (draw(landmarks, words, 43) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    n_twins = min(int(round(twins * landmarks)), landmarks - 1)
+    twin_of = np.full(landmarks, -1, np.int32)
+    chosen = np.sort(1 + np.argsort(draw(landmarks - 1, 1, 44)[:, 0], kind="stable")[:n_twins]) if n_twins else np.zeros(0, np.int64)
+    source = draw(landmarks, 1, 45)[:, 0]
+    for l in chosen:
+        twin_of[l] = int(source[l] % np.uint64(l))
+        base[l] = base[twin_of[l]]
+    n = frames * keypoints
+    uniform = ((draw(n, num_bits, 46) >> np.uint64(11)).astype(np.float64) + 0.5) / float(1 << 53)
+    flips = (uniform < flip).reshape(n, words, 32)
+    mask = (flips.astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(axis=2).astype(np.uint32)
+    fresh = (draw(n, words, 47) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    ids = kp_id.reshape(n)
+    bits = np.where((ids >= 0)[:, None], base[np.maximum(ids, 0)] ^ mask, fresh).reshape(frames, keypoints, words)
+    E = _rodrigues64(np.radians(rotation_deg) * np.array([1.0, -1.0, 1.0]) / np.sqrt(3.0))
+    R_pred = (E @ R[-1]).astype(np.float32)
+    t_pred = (E @ t[-1] + translation * np.ones(3) / np.sqrt(3.0)).astype(np.float32)
+    return (*base_window, np.ascontiguousarray(bits).view(np.int32), R_pred, t_pred, twin_of)
