@@ -1620,6 +1620,247 @@ MI_API int mi_place_votes(const uint32_t *db_bits, const uint8_t *db_valid, int 
 MI_API int mi_place_select(const int32_t *votes, int q, int n, const int32_t *excl_lo, const int32_t *excl_hi, int min_votes,
                            int num_candidates, int32_t *cand_index, int32_t *cand_votes, mi_stream_t stream);
 
+/* ---- pose-graph optimisation (K27): odometry edges and loop edges move the whole trajectory so that the loop closes -----------
+ * K26 finds the old keyframe a new frame shows, K15 / K17 / K18 / K21 / K23 / K24 turn the pair into a relative pose with a
+ * 6x6 information matrix, K25 refines a window.  This section takes those edges and optimises every pose of the graph:
+ * Levenberg-Marquardt, each damped step solved by a fixed number of preconditioned conjugate-gradient trips with the
+ * block-Jacobi preconditioner, `batch` independent graphs per call (one per loop candidate of K26, say), one workgroup
+ * each.  The host calls users would reach for are g2o or GTSAM.  Four entries under the contract of the K15 / K23 / K25
+ * sections: pure functions of their arguments, no allocation, no synchronisation, no memset, one stream, no atomics, every
+ * sum in a fixed order (the same inputs give the same bits, alone or inside a batch), capturable into a hipGraph; outputs
+ * and workspace may hold anything on entry, every output element is written and outputs alias nothing; MI_E_* before any
+ * launch.
+ *
+ * State.  N nodes with poses r (batch, N, 3, 3), t (batch, N, 3) float32, X_c = R X + t (K23's convention).  fixed (batch, N)
+ *   bytes: non-zero = the node is held (the gauge; a map's keyframes in relocalisation).  2 <= N <= MI_PGO_MAX_NODES,
+ *   1 <= E <= MI_PGO_MAX_EDGES (below: MI_E_SHAPE, as batch < 1; above: MI_E_PARAM, as batch > 65535).  huber < 0 or not
+ *   finite: MI_E_PARAM.
+ * Edges.  edge_index (batch, E, 2) int32 (i, j); zr (batch, E, 3, 3), zt (batch, E, 3) float32: the measured motion X_j =
+ *   R_z X_i + t_z, what RgbdPoseEstimator, DenseRgbdRefiner, DirectRgbdRefiner and AbsolutePoseEstimator.forward_rgbd return
+ *   for (frame 1 = i, frame 2 = j); info (batch, E, 6, 6) float32 in (rotation, translation) order: Omega_rc = info[min(r, c),
+ *   max(r, c)], only the upper triangle enters the arithmetic; edge_valid (batch, E) bytes.  An edge is INACTIVE when its
+ *   byte is 0, i == j, an index lies outside [0, N), or one of the 9 + 3 + 36 numbers of zr, zt, info is not finite.  An
+ *   inactive edge is read no further, adds nothing and reports chi2 = 0: the padding of a ragged batch.  A node is LIVE
+ *   when it is not fixed and has an active edge.
+ * Threads.  256 per graph.  A sum "over the edges" (or over the 6N rows of a vector) is: each thread's float32 partial sum
+ *   over e = tid, tid + 256, ... in that order, wave_sum_dpp over the 64 lanes of each wave, then the four waves' sums added
+ *   in wave order in float64 starting from 0.  dot6(a, b) = ((((a0 b0 + a1 b1) + a2 b2) + a3 b3) + a4 b4) + a5 b5.
+ * Residual (float32, at the float32 poses).  R_p = R_j R_i^T, t_p = t_j - R_p t_i; R_d = R_p R_z^T, u = R_d t_z, t_d = t_p - u
+ *   (3x3 products and R x as ((a0 b0 + a1 b1) + a2 b2)); e = (Log R_d, t_d): the coordinates of K18's update (R <- Exp(w) R,
+ *   t <- Exp(w) t + tau), in which K18 / K21 / K23 express their information matrices.
+ * Log.  v = vee(R - R^T) / 2, s = |v|, c = (trace R - 1) / 2, theta = atan2(s, c).  c >= -0.9: phi = (theta / s) v, and
+ *   (1 + s^2 / 6) v where s < 1e-4.  c < -0.9 (theta above 154 degrees, where s -> 0 loses the axis): the axis from the
+ *   symmetric part -- m the largest diagonal element of R, a_m = sqrt((R_mm - c) / (1 - c)), a_n = (R_mn + R_nm) /
+ *   (2 (1 - c) a_m) -- with the sign of a . v, phi = theta a.  The branch is continuous up to pi; AT pi, v = 0 decides no
+ *   sign and phi = +pi a (the rotation by -pi a is the same one).  The linearisation of Log has no limit at pi (J_l^-1
+ *   stays finite there, k -> 1 / pi^2, but the residual jumps from pi a to -pi a): an edge does not converge across it.
+ * Cost.  oe = Omega e (oe_r = dot6(Omega_r, e)), chi2 = dot6(e, oe).  chi = sqrt(chi2); with huber > 0 and chi > huber:
+ *   rho = (2 huber) chi - huber huber and w = huber / chi; otherwise rho = chi2, w = 1.  An edge whose chi2 is not finite has
+ *   chi2 = rho = +inf.  cost = the sum of rho over the edges (above; inactive edges add 0), a float64, returned rounded to
+ *   float32.  Nothing active: 0.
+ * Jacobians (float32).  Exact to first order in the left perturbation of node i and of node j:
+ *       J_j = [[J_l^-1, 0], [-[t_d]x, I]],   J_i = [[-J_l^-1 R_p, 0], [-[u]x R_p, -R_p]]
+ *   with J_l^-1 = I - [phi]x / 2 + k ([phi] [phi]^T - theta^2 I) at phi = Log R_d, k = (1 - (theta / 2) cos(theta / 2) /
+ *   sin(theta / 2)) / theta^2, and k = (1/12 + theta^2 / 720) + theta^4 / 30240 where theta^2 < 1/16.
+ * Blocks, per active edge with a finite chi2 (an edge with chi2 = +inf adds zeros).  A_i = Omega J_i, A_j = Omega J_j
+ *   (A_rc = dot6 over k of Omega_rk J_kc);  H_ii = w J_i^T A_i, H_jj = w J_j^T A_j, H_ij = w J_i^T A_j (each element w times
+ *   dot6 over k; the upper triangles of H_ii and H_jj are computed and mirrored);  g_i = w J_i^T oe, g_j = w J_j^T oe.
+ *   H_ij = 0 when i or j is fixed.
+ * System.  Per live node n: D_n and g_n = the float32 sums of H_ii or H_jj (g_i or g_j) over the node's active edges IN
+ *   ASCENDING EDGE INDEX, starting from 0; every other node has D = 0, g = 0.
+ * Solve, of (H + lambda diag H) dx = -g with lambda rounded to float32.  Per live node M_n = D_n with the diagonal D_rr +
+ *   lambda D_rr in float64, factored L D L^T by K25's column algorithm under K18's pivot rule (max diag M_n > 0, every pivot
+ *   above 1e-6 max diag M_n and finite), the factors rounded to float32; a node that fails is FROZEN for this step (dx_n =
+ *   0, it acts as fixed).  z = M^-1 r per node, float32: y = r, y_k -= l_ki y_i for i ascending, z_k = y_k / d_k, z_k -=
+ *   l_ik z_i for i descending.  Vectors are float32 and 0 outside the live, unfrozen nodes.  x = 0, r = -g, z = M^-1 r,
+ *   p = z, rz = r . z.  Exactly pcg_iterations trips, no residual test:
+ *       (A p)_row = dot6(D_row, p_n), + (lambda D_rr) p_r, then + dot6 of the row of H_ij (of H_ij^T on side j) with p of
+ *       the other end, over the node's edges in ascending edge index;
+ *       pAp = p . A p;  dead <- dead or not (pAp > 0) or pAp not finite or rz == 0;  alpha = dead ? 0 : (float)(rz / pAp);
+ *       x += alpha p, r -= alpha A p, z = M^-1 r, rz' = r . z;  unless dead: p = z + (float)(rz' / rz) p, rz = rz'.
+ *   Every dot product is a sum over the 6N rows (above) into float64.  `dead` is a workgroup-uniform value read after a
+ *   barrier, and every barrier is reached by every thread on every trip; once dead every later trip changes nothing.
+ * Step.  K18's update of the float64 pose of every live, unfrozen node with dx_n, rounded to float32 for every line.
+ * Loop.  K25's: lambda = 1e-4 (float64).  `iterations` times: linearise at the state, solve with lambda, step to a candidate,
+ *   evaluate its cost; when that is finite and strictly lower (float64 sums compared), the candidate becomes the state and
+ *   lambda <- max(lambda / 10, 1e-9); otherwise lambda <- min(10 lambda, 1e6).  Never stops early.
+ * Refusal.  The initial cost is not finite, there is no active edge, no fixed node, or no live node.
+ * A long chain with few closures needs pcg_iterations of the order of its length: block-Jacobi PCG moves information one
+ * edge per trip and does not shorten a chain's diameter. */
+#define MI_PGO_MAX_NODES 1024
+#define MI_PGO_MAX_EDGES 4096
+#define MI_PGO_MAX_ITERATIONS 32
+#define MI_PGO_MAX_PCG 256
+
+/* Cost alone, the outlier test between rounds: chi2 (batch, E) float32, the unweighted chi2 of every active edge (+inf
+ * where it is not finite) and 0 for an inactive one; cost (batch) float32; active (batch, E) bytes.  One launch. */
+MI_API int mi_pgo_cost(const float *r, const float *t, const int32_t *edge_index, const float *zr, const float *zt,
+                       const float *info, const uint8_t *edge_valid, int batch, int nodes, int edges, float huber, float *chi2,
+                       float *cost, uint8_t *active, mi_stream_t stream);
+
+/* Workspace of mi_pgo_linearise and mi_pgo_refine: per graph the float64 state and candidate, their float32 roundings, the
+ * plan (edge ends, list offsets, lists), D, g and the factors per node and 120 floats per edge, every array rounded up to
+ * 16 bytes; 0 for an unsupported shape.  16-byte aligned (MI_E_ALIGN), any content; shorter: MI_E_CAPACITY. */
+MI_API size_t mi_pgo_workspace_bytes(int batch, int nodes, int edges);
+
+/* One undamped linearisation at the given state: diag (batch, N, 6, 6) float32, D_n, zero for a fixed or edgeless node;
+ * off (batch, E, 6, 6), H_ij, the (i, j) block, zero for an inactive edge and an edge that touches a fixed node; g
+ * (batch, N, 6); cost (batch).  One launch. */
+MI_API int mi_pgo_linearise(const float *r, const float *t, const int32_t *edge_index, const float *zr, const float *zt,
+                            const float *info, const uint8_t *edge_valid, const uint8_t *fixed, int batch, int nodes, int edges,
+                            float huber, float *diag, float *off, float *g, float *cost, void *workspace, size_t workspace_bytes,
+                            mi_stream_t stream);
+
+/* The whole loop in one launch.  1 <= iterations <= MI_PGO_MAX_ITERATIONS, 1 <= pcg_iterations <= MI_PGO_MAX_PCG
+ * (MI_E_PARAM).  r (batch, N, 3, 3), t (batch, N, 3): the final state (a node that is not live is its input's bits);
+ * chi2 (batch, E): the unweighted chi2 of mi_pgo_cost at the result; cost0, cost (batch) float32: the cost at the input and
+ * at the result; accepted (batch) int32: the number of accepted steps; info_out (batch, N, 6, 6): diag of mi_pgo_linearise at
+ * the result, bit for bit -- the CONDITIONAL information of each node given its neighbours, not the marginal; ok (batch)
+ * bytes.  A refused graph: ok = 0, the poses equal the inputs, chi2 = 0, accepted = 0, info_out = 0, cost0 = cost = +inf
+ * (0 when no edge is active). */
+MI_API int mi_pgo_refine(const float *r0, const float *t0, const int32_t *edge_index, const float *zr, const float *zt,
+                         const float *info, const uint8_t *edge_valid, const uint8_t *fixed, int batch, int nodes, int edges,
+                         int iterations, int pcg_iterations, float huber, float *r, float *t, float *chi2, float *cost0,
+                         float *cost, int32_t *accepted, float *info_out, uint8_t *ok, void *workspace, size_t workspace_bytes,
+                         mi_stream_t stream);
+
+/* ---- landmark tracks (K28): pairwise matches over a window of frames -> the track form K25 reads, and N-view triangulation ----
+ * The matcher's output is pairwise: keypoint indices (i, j) per frame pair (mi_match_pairs' match_ij, mi_mnn_extract's
+ * indices).  K25 wants a window in track form: one column per landmark, one row per frame.  This section is the join:
+ * mi_tracks_build labels the connected components of the match graph, rejects the ambiguous ones and orders the rest
+ * into landmark slots; mi_tracks_triangulate gives every slot a point from all the frames that see it.  The host code it
+ * replaces is a union-find, a gather and a per-landmark least-squares loop.  Entries under the contract of the K25 / K27
+ * sections: pure functions of their arguments, no allocation, no synchronisation, no memset, one stream, capturable into
+ * a hipGraph; outputs and workspace may hold anything on entry, every output element is written and outputs alias
+ * nothing; MI_E_* before any launch; the same inputs give the same bits, alone or inside a batch.
+ * Atomics.  No global atomics.  The labelling uses INTEGER atomics on LDS (atomicMin on a label, atomicOr / atomicAdd on a
+ *   root's frame mask and node count, atomicAdd on the four counters): every result below is defined by the inputs alone
+ *   -- a component's label is its smallest node, whatever order the hooks land in -- so the order in which they land
+ *   changes no output bit.  No floating-point value is ever combined atomically.
+ *
+ * Shapes.  2 <= F <= MI_TRACKS_MAX_FRAMES frames, 1 <= K <= MI_TRACKS_MAX_KEYPOINTS keypoints per frame, 1 <= P <=
+ *   MI_TRACKS_MAX_PAIRS listed pairs, 1 <= M <= MI_TRACKS_MAX_MATCHES match records per pair, 1 <= L <= MI_BA_MAX_LANDMARKS
+ *   slots (below: MI_E_SHAPE, as batch < 1; above: MI_E_PARAM, as batch > 65535).  min_views outside 2 .. F: MI_E_PARAM.
+ * Matches.  pair_frames (batch, P, 2) int32 (a, b); match_ij (batch, P, M, 2) int32 (i in a, j in b); match_valid
+ *   (batch, P, M) bytes; kp_valid (batch, F, K) bytes or NULL (every keypoint).  A match is ACTIVE when its byte is not 0,
+ *   0 <= a, b < F and a != b, 0 <= i, j < K, and both ends' kp_valid bytes are set.  Anything else is padding and is read
+ *   no further: the index fields of an invalid record may hold anything.  Reversed pairs (b, a), repeated pairs and
+ *   repeated matches are legal and change nothing.
+ * Components.  Node n = f K + k.  A COMPONENT is a connected component of the graph of the active matches; its LABEL is its
+ *   smallest node, its LENGTH its number of nodes.  It CONFLICTS when it holds two nodes of one frame; it is ELIGIBLE when
+ *   it does not and its length is at least min_views.  The eligible components ordered by (length descending, label
+ *   ascending) fill the slots 0, 1, ...; those beyond L are dropped.
+ * Triangulation (float64 throughout; the float32 inputs are widened exactly).  Over the frames f that see the landmark, in
+ *   ascending f: with the observation (x, y), n = sqrt((x x + y y) + 1),
+ *       d_k = ((R_0k x + R_1k y) + R_2k) / n      (d = R^T m / |m|, m = (x, y, 1): the ray in the world frame)
+ *       c_k = -((R_0k t_0 + R_1k t_1) + R_2k t_2) (the camera centre)
+ *       P_ij = [i == j] - d_i d_j;   A_ij += P_ij (i <= j);   b_i += (P_i0 c_0 + P_i1 c_1) + P_i2 c_2
+ *   from A = 0, b = 0.  Solve A X = b by the symmetric cofactor inverse: C_00 = A_11 A_22 - A_12 A_12, C_01 = A_02 A_12 - A_01
+ *   A_22, C_02 = A_01 A_12 - A_02 A_11, C_11 = A_00 A_22 - A_02 A_02, C_12 = A_01 A_02 - A_00 A_12, C_22 = A_00 A_11 - A_01 A_01, det =
+ *   (A_00 C_00 + A_01 C_01) + A_02 C_02, X_i = ((C_i0 b_0 + C_i1 b_1) + C_i2 b_2) / det.  USABLE (K25's pivot rule): with the
+ *   pivots p_0 = A_00, p_1 = C_22 / A_00, p_2 = det / C_22 and dmax the largest diagonal element of A: dmax > 0, every pivot
+ *   above 1e-6 dmax, every X_i finite.  Parallel rays fail it (so does a landmark nobody sees).
+ *   Per seeing frame: q_i = ((R_i0 X_0 + R_i1 X_1) + R_i2 X_2) + t_i; z = q_2; with z > 0, u = q_0 / z - x, v = q_1 / z - y, e2 =
+ *   u u + v v.  e2max = the largest e2 (+inf when a z is not positive or the solve is unusable).  cos_par = the smallest
+ *   (d_a0 d_b0 + d_a1 d_b1) + d_a2 d_b2 over the pairs a < b of seeing frames (1 with fewer than two).
+ *   point_ok: seen count >= min_views, usable, every z > 0, e2max <= max_e2 and cos_par <= max_cos (float64 comparisons). */
+#define MI_TRACKS_MAX_FRAMES 16
+#define MI_TRACKS_MAX_KEYPOINTS 1024
+#define MI_TRACKS_MAX_PAIRS 120
+#define MI_TRACKS_MAX_MATCHES 1024
+
+/* Workspace of mi_tracks_build: per window one int32 per match record (the two nodes of an active match, packed),
+ * rounded up to 16 bytes; 0 for an unsupported shape.  16-byte aligned (MI_E_ALIGN), any content; shorter: MI_E_CAPACITY. */
+MI_API size_t mi_tracks_workspace_bytes(int batch, int frames, int keypoints, int pairs, int matches, int landmarks);
+
+/* Matches to tracks.  One workgroup per window, one launch.  keypoints (batch, F, K, 2) float32 are copied and never
+ * interpreted.  track_kp (batch, F, L) int32: the keypoint index of slot l in frame f, or -1; vis (batch, F, L) bytes: 1
+ * where track_kp >= 0; track_keypoints (batch, F, L, 2) float32: that keypoint's two floats bit for bit, 0 where not seen;
+ * track_len (batch, L) int32; kp_track (batch, F, K) int32: the slot of the keypoint's component, -2 for a node of a
+ * conflicting component, -1 otherwise; counts (batch, 4) int32: components of >= 2 nodes, conflicting, eligible, kept =
+ * min(eligible, L).  An empty slot: -1 / 0 / 0 / 0. */
+MI_API int mi_tracks_build(const int32_t *pair_frames, const int32_t *match_ij, const uint8_t *match_valid,
+                           const uint8_t *kp_valid, const float *keypoints, int batch, int frames, int keypoints_per_frame,
+                           int pairs, int matches, int min_views, int landmarks, int32_t *track_kp, uint8_t *vis,
+                           float *track_keypoints, int32_t *track_len, int32_t *kp_track, int32_t *counts, void *workspace,
+                           size_t workspace_bytes, mi_stream_t stream);
+
+/* N-view triangulation of every slot.  One thread per landmark, one launch, no workspace.  r (batch, F, 3, 3), t (batch, F, 3)
+ * float32 with X_c = R X + t; obs (batch, F, L, 2) float32 normalised (x, y) as mi_normalise_keypoints writes them, read
+ * only where vis (batch, F, L) is not 0.  max_e2 (a normalised squared distance) must be > 0 and finite, max_cos (the cosine
+ * of the smallest accepted parallax angle) in (-1, 1] (MI_E_PARAM).  points (batch, L, 3) float32: X rounded, zeros when the
+ * solve is unusable; point_ok (batch, L) bytes; vis_out (batch, F, L) bytes: 1 where vis is set and point_ok, else 0 -- K25
+ * derives "active" from vis alone, so a failed landmark takes no part; e2max, cos_par (batch, L) float32, rounded. */
+MI_API int mi_tracks_triangulate(const float *r, const float *t, const float *obs, const uint8_t *vis, int batch, int frames,
+                                 int landmarks, int min_views, float max_e2, float max_cos, float *points, uint8_t *point_ok,
+                                 uint8_t *vis_out, float *e2max, float *cos_par, mi_stream_t stream);
+
+/* ---- local-map tracking (K29): a descriptor per landmark, and landmarks projected into a frame and matched in a window ----
+ * K28 produces triangulated landmarks, K23 wants 3-D to 2-D matches of a new frame.  This section is the join: a tracker that
+ * has a predicted pose projects its landmarks and searches a small window around each projection (ORB-SLAM's
+ * SearchByProjection in TrackLocalMap).  mi_localmap_descriptors gives every landmark slot the descriptor of one of its
+ * observations; mi_localmap_match matches one frame per batch item against that item's landmarks.  Entries under the contract
+ * of the K25 .. K28 sections: pure functions of their arguments, no allocation, no synchronisation, no memset, one stream,
+ * capturable into a hipGraph; outputs may hold anything on entry, every output element is written and outputs alias nothing;
+ * MI_E_* before any launch; the same inputs give the same bits, alone or inside a batch.
+ * Atomics.  No global atomics.  mi_localmap_match uses INTEGER atomics on LDS: atomicMin on a keypoint's claim word and
+ *   atomicAdd on the five state counters.  Every result below is defined by the inputs alone -- a keypoint's claim is the
+ *   smallest claim made on it, a count is a count -- so the order in which they land changes no output bit.  No
+ *   floating-point value is ever combined atomically.
+ *
+ * Descriptors.  The packed hard bits of mi_sparse_bad / mi_sparse_bad_oriented: num_bits is 256 or 512 (anything else:
+ *   MI_E_PARAM), W = num_bits / 32 words of 32 bits.  hamming(a, b) = popcount(a xor b) over the W words.  ABSENT = num_bits + 1.
+ * Shapes.  1 <= F <= MI_LOCALMAP_MAX_FRAMES, 1 <= K <= MI_LOCALMAP_MAX_KEYPOINTS, 1 <= L <= MI_LOCALMAP_MAX_LANDMARKS
+ *   (= MI_BA_MAX_LANDMARKS), 1 <= batch <= 65535 (below: MI_E_SHAPE; above: MI_E_PARAM).  Order of the checks: NULL, shape,
+ *   parameters. */
+#define MI_LOCALMAP_MAX_LANDMARKS 2048
+#define MI_LOCALMAP_MAX_KEYPOINTS 1024
+#define MI_LOCALMAP_MAX_FRAMES 16
+
+/* A representative descriptor per landmark slot.  bits (batch, F, K, W) uint32; track_kp (batch, F, L) int32 as
+ * mi_tracks_build writes it.  The VIEWS of slot l are the frames f, ascending, with 0 <= track_kp[f, l] < K; any other value
+ * means "not seen".  With n views, for view a: the n distances hamming(a, b) over all views b, a itself included (distance
+ * 0), sorted ascending; med_a is element (n - 1) / 2 (integer division) of that list.  The representative is the view with
+ * the smallest key med_a << 8 | f_a: the medoid under the median distance, the lowest frame on a tie (ORB-SLAM's
+ * ComputeDistinctiveDescriptors).  rep_bits (batch, L, W) uint32: that view's words, bit for bit; rep_frame (batch, L) int32:
+ * its frame; rep_median (batch, L) int32: its med.  n = 0: zeros, -1 and ABSENT.  16 lanes per slot, one launch. */
+MI_API int mi_localmap_descriptors(const uint32_t *bits, const int32_t *track_kp, int batch, int frames, int keypoints,
+                                   int landmarks, int num_bits, uint32_t *rep_bits, int32_t *rep_frame, int32_t *rep_median,
+                                   mi_stream_t stream);
+
+/* One frame per batch item against that item's landmarks.  One workgroup per item, one launch, no workspace.
+ * points (batch, L, 3) float32; point_valid (batch, L) bytes or NULL (every point); rep_bits (batch, L, W); r (batch, 3, 3),
+ * t (batch, 3) float32: the predicted pose, X_c = R X + t; cam (batch, 4) float32: fx, fy, cx, cy; kp (batch, K, 2) float32 in
+ * pixel (y, x) order; kp_valid (batch, K) bytes or NULL (every keypoint); kp_bits (batch, K, W).
+ * Parameters (MI_E_PARAM otherwise, NaN included): 0 < min_depth < max_depth, both finite; radius > 0 and finite;
+ *   0 <= max_distance <= num_bits; 0 < ratio <= 1; height, width >= 1.
+ * All geometry is float64; the float32 inputs are widened exactly and every operation is the one written here, in this order,
+ * unfused.
+ * 1. Projection.  q_i = ((R_i0 X_0 + R_i1 X_1) + R_i2 X_2) + t_i; z = q_2; u = fx (q_0 / z) + cx; v = fy (q_1 / z) + cy.  The
+ *    landmark is IN VIEW iff its point_valid byte is set, q_0, q_1, q_2 are finite, min_depth <= z <= max_depth,
+ *    0 <= u <= width - 1 and 0 <= v <= height - 1.  proj (batch, L, 2) float32: (v, u) rounded, (-1, -1) when not in view.
+ * 2. Window.  A valid keypoint j = (ky, kx) is in the window iff du du + dv dv <= radius radius with du = kx - u, dv = ky - v
+ *    (radius radius is the float64 product of the widened radius).
+ * 3. Nearest two (K26's rule, over the keypoints in the window).  The key of keypoint j is hamming(rep_l, kp_bits_j) << 16 | j;
+ *    key1 is the smallest key, key2 the smallest among the others; d1 = key1 >> 16, j1 = key1 & 0xffff, d2 = key2 >> 16.  An
+ *    empty window: d1 = ABSENT, j1 = -1; a window of one: d2 = ABSENT.
+ * 4. Candidate.  l is a CANDIDATE iff d1 <= max_distance and (float)d1 < ratio * (float)d2: one float32 multiply and one
+ *    compare, K26's vote.
+ * 5. One landmark per keypoint.  The claim of candidate l on j1 has the key d1 << 16 | l.  kp_lm (batch, K) int32: the l of the
+ *    smallest claim on j, or -1.  l is KEPT iff kp_lm[j1] == l.  A loser is not given its second choice.
+ * 6. Outputs.  lm_state (batch, L) bytes: 0 not in view, 1 in view with an empty window, 2 failed the distance or the ratio
+ *    test, 3 lost its keypoint to another landmark, 4 kept.  lm_kp (batch, L) int32: j1 if kept, else -1.  lm_distance
+ *    (batch, L) int32: d1 for the states 2 .. 4, else ABSENT.  match_keypoints (batch, L, 2) float32: the kept keypoint's two
+ *    floats bit for bit, else (-1, -1).  counts (batch, 5) int32: the number of landmarks in each state.
+ * points, match_keypoints and lm_state == 4 are the points3d, keypoints2d and valid of K23 (mi_pnp_ransac after
+ * mi_normalise_keypoints); kp_lm == -1 marks the keypoints left over for new landmarks. */
+MI_API int mi_localmap_match(const float *points, const uint8_t *point_valid, const uint32_t *rep_bits, const float *r,
+                             const float *t, const float *cam, const float *kp, const uint8_t *kp_valid, const uint32_t *kp_bits,
+                             int batch, int landmarks, int keypoints, int num_bits, int height, int width, float min_depth,
+                             float max_depth, float radius, int max_distance, float ratio, float *proj, uint8_t *lm_state,
+                             int32_t *lm_kp, int32_t *lm_distance, float *match_keypoints, int32_t *kp_lm, int32_t *counts,
+                             mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,24 +107,8 @@ globals().update(_constants)            # MI_OK, MI_BAD_HARD, MI_SOLVER_NO_FORK,
 # not part of the product ABI; nothing in this package calls them
 DEBUG_SIGNATURES, _debug_restypes, _, _ = _read("mi355x_match_debug.h")
 RESTYPES.update(_debug_restypes)
-# include/mi355x_match_pgo.h: the pose-graph section of the ABI (K27), a header and a library of its own
-# (lib/libmi355x_match_pgo.so, load_pgo()): the product library exports include/mi355x_match.h and nothing else.  call()
-# finds the library of a name by itself.  Its limits are EXTRA_CONSTANTS["MI_PGO_MAX_NODES"], ...: a dictionary.
-EXTRA_SIGNATURES, _extra_restypes, _, EXTRA_CONSTANTS = _read("mi355x_match_pgo.h")
-RESTYPES.update(_extra_restypes)
-# include/mi355x_match_tracks.h: the landmark-track section (K28), likewise a header and a library of its own
-# (lib/libmi355x_match_tracks.so, load_tracks()), in dictionaries of its own: TRACKS_CONSTANTS["MI_TRACKS_MAX_FRAMES"], ...
-TRACKS_SIGNATURES, _tracks_restypes, _, TRACKS_CONSTANTS = _read("mi355x_match_tracks.h")
-RESTYPES.update(_tracks_restypes)
-# include/mi355x_match_localmap.h: the local-map tracking section (K29), the same again (lib/libmi355x_match_localmap.so,
-# load_localmap()): LOCALMAP_CONSTANTS["MI_LOCALMAP_MAX_LANDMARKS"], ...
-LOCALMAP_SIGNATURES, _localmap_restypes, _, LOCALMAP_CONSTANTS = _read("mi355x_match_localmap.h")
-RESTYPES.update(_localmap_restypes)
 
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_debug.so")
-PGO_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_pgo.so")
-TRACKS_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_tracks.so")
-LOCALMAP_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_localmap.so")
 
 _lib = None            # the library every call() goes through: the product, unless inside debug_library()
 _product = None
@@ -154,48 +138,6 @@ def load() -> ctypes.CDLL:
             _product = _open(LIB_PATH, SIGNATURES)
         _lib = _product
     return _lib
-
-
-_pgo = None
-
-
-def load_pgo() -> ctypes.CDLL:
-    """lib/libmi355x_match_pgo.so, the entries of include/mi355x_match_pgo.h, loaded once."""
-    global _pgo
-    if _pgo is None:
-        _pgo = _open(PGO_LIB_PATH, EXTRA_SIGNATURES)
-    return _pgo
-
-
-_tracks = None
-
-
-def load_tracks() -> ctypes.CDLL:
-    """lib/libmi355x_match_tracks.so, the entries of include/mi355x_match_tracks.h, loaded once."""
-    global _tracks
-    if _tracks is None:
-        _tracks = _open(TRACKS_LIB_PATH, TRACKS_SIGNATURES)
-    return _tracks
-
-
-_localmap = None
-
-
-def load_localmap() -> ctypes.CDLL:
-    """lib/libmi355x_match_localmap.so, the entries of include/mi355x_match_localmap.h, loaded once."""
-    global _localmap
-    if _localmap is None:
-        _localmap = _open(LOCALMAP_LIB_PATH, LOCALMAP_SIGNATURES)
-    return _localmap
-
-
-def library_of(name: str) -> ctypes.CDLL:
-    """The library that exports the entry `name`."""
-    if name in LOCALMAP_SIGNATURES:
-        return load_localmap()
-    if name in TRACKS_SIGNATURES:
-        return load_tracks()
-    return load_pgo() if name in EXTRA_SIGNATURES else load()
 
 
 class debug_library:
@@ -272,7 +214,7 @@ def timings_ms() -> dict:
 
 
 def call(name: str, *args) -> None:
-    fn = getattr(library_of(name), name)
+    fn = getattr(load(), name)
     if _timers is None or (_timed_names is not None and name not in _timed_names):
         check(fn(*args), name)
         return

@@ -3,10 +3,8 @@
     python -m onnx_image_processing_amd.build [--force]
 
 hipcc cross-compiles without a GPU.  Output: onnx_image_processing_amd/lib/libmi355x_match.so -- the product: exports
-exactly include/mi355x_match.h --, lib/libmi355x_match_pgo.so (the pose-graph section, include/mi355x_match_pgo.h),
-lib/libmi355x_match_tracks.so (the landmark-track section, include/mi355x_match_tracks.h), lib/libmi355x_match_localmap.so (the
-local-map tracking section, include/mi355x_match_localmap.h) and lib/libmi355x_match_debug.so (the product's ABI plus the kernel-variant test hooks of
-include/mi355x_match_debug.h; tests/ and tools/ only).  All are git-ignored and travel to the GPU box with the working
+exactly include/mi355x_match.h -- and lib/libmi355x_match_debug.so (the same ABI plus the kernel-variant test hooks of
+include/mi355x_match_debug.h; tests/ and tools/ only).  Both are git-ignored and travel to the GPU box with the working
 tree.  Objects are rebuilt only when a source or header is newer.
 """
 from __future__ import annotations
@@ -26,20 +24,10 @@ LIB = os.path.join(LIBDIR, "libmi355x_match.so")
 DEBUG_LIB = os.path.join(LIBDIR, "libmi355x_match_debug.so")
 INCLUDE = os.path.join(os.path.dirname(PKG), "include")
 
-SOURCES = ["corner.hip", "nms.hip", "topk.hip", "bad.hip", "bad_oriented.hip", "bad_dense.hip", "orient.hip", "cost.hip", "sinkhorn.hip", "sinkhorn_dots.hip", "mnn.hip", "akaze.hip", "akaze_stream.hip", "essential.hip", "detectors.hip", "match_pairs.hip", "voxel.hip", "depth.hip", "threshold.hip", "pose.hip", "ingest.hip", "rigid.hip", "icp.hip", "photo.hip", "tsdf.hip", "surface.hip", "tsdf_gray.hip", "pnp.hip", "homography.hip", "ba.hip", "place.hip"]
+SOURCES = ["corner.hip", "nms.hip", "topk.hip", "bad.hip", "bad_oriented.hip", "bad_dense.hip", "orient.hip", "cost.hip", "sinkhorn.hip", "sinkhorn_dots.hip", "mnn.hip", "akaze.hip", "akaze_stream.hip", "essential.hip", "detectors.hip", "match_pairs.hip", "voxel.hip", "depth.hip", "threshold.hip", "pose.hip", "ingest.hip", "rigid.hip", "icp.hip", "photo.hip", "tsdf.hip", "surface.hip", "tsdf_gray.hip", "pnp.hip", "homography.hip", "ba.hip", "place.hip", "pgo.hip", "tracks.hip", "localmap.hip"]
 # sources that read a hook of csrc/hooks.h: compiled a second time for the debug library; every other object is shared
 HOOKED = ["corner.hip", "nms.hip", "topk.hip", "sinkhorn.hip", "sinkhorn_dots.hip", "akaze.hip", "bad_oriented.hip", "cost.hip", "mnn.hip"]
 DEBUG_ONLY = ["hooks.hip"]
-# a section of the ABI with a header and a library of its own: lib/libmi355x_match_pgo.so exports exactly
-# include/mi355x_match_pgo.h (K27); the product library stays the export of include/mi355x_match.h and nothing else
-PGO_LIB = os.path.join(LIBDIR, "libmi355x_match_pgo.so")
-PGO_SOURCES = ["pgo.hip"]
-# ... and lib/libmi355x_match_tracks.so exactly include/mi355x_match_tracks.h (K28)
-TRACKS_LIB = os.path.join(LIBDIR, "libmi355x_match_tracks.so")
-TRACKS_SOURCES = ["tracks.hip"]
-# ... and lib/libmi355x_match_localmap.so exactly include/mi355x_match_localmap.h (K29)
-LOCALMAP_LIB = os.path.join(LIBDIR, "libmi355x_match_localmap.so")
-LOCALMAP_SOURCES = ["localmap.hip"]
 # -ffp-contract=off: the corner response must not fuse a*b+c (bit parity with the reference's
 # op-by-op fp32); IEEE sqrt/div are hipcc's defaults and are relied upon.
 # -fvisibility=hidden: only the MI_API declarations of include/*.h are exported (no C++-mangled internals).
@@ -97,9 +85,6 @@ def build(force: bool = False, verbose: bool = True) -> str:
         debug_objs.append(want(src, ".dbg", ["-DMI_DEBUG_HOOKS"]) if src in HOOKED else o)
     for src in DEBUG_ONLY:
         debug_objs.append(want(src, ".dbg", ["-DMI_DEBUG_HOOKS"]))
-    pgo_objs = [want(src, "", []) for src in PGO_SOURCES]
-    tracks_objs = [want(src, "", []) for src in TRACKS_SOURCES]
-    localmap_objs = [want(src, "", []) for src in LOCALMAP_SOURCES]
 
     def run(cmd):
         if verbose:
@@ -114,10 +99,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
         list(ex.map(run, jobs))
     # Link to a temporary name and rename onto the final path: a process that waits for the library to appear (bench.py's
     # other ranks, a concurrent test run) must never dlopen a file the linker is still writing.  The debug library is
-    # linked FIRST, and the pose-graph, landmark-track and local-map libraries before the product, so that the product library's
-    # appearance means every library is complete.
-    for lib, members in ((DEBUG_LIB, debug_objs), (PGO_LIB, pgo_objs), (TRACKS_LIB, tracks_objs), (LOCALMAP_LIB, localmap_objs),
-                         (LIB, objs)):
+    # linked FIRST, so that the product library's appearance means both are complete.
+    for lib, members in ((DEBUG_LIB, debug_objs), (LIB, objs)):
         if jobs or force or _newer(lib, members + link_deps):
             tmp = f"{lib}.{os.getpid()}.tmp"
             try:

@@ -1,4 +1,4 @@
-// K29 local-map tracking (include/mi355x_match_localmap.h): a representative descriptor per landmark slot, and the landmarks
+// K29 local-map tracking (include/mi355x_match.h): a representative descriptor per landmark slot, and the landmarks
 // of a batch item projected into one frame by a predicted pose and matched, each inside a window round its projection.
 //
 // K29a localmap_descriptors_kernel: 16 lanes per slot, lane f = frame f.  A lane gathers its view's W words; W width-16
@@ -20,7 +20,6 @@
 // Built with -ffp-contract=off.  No global atomics; the LDS atomics are integer and order-independent (header): bitwise
 // reproducible.
 #include "common.h"
-#include "../../include/mi355x_match_localmap.h"
 #include "localmap_math.h"
 
 #include <math.h>

@@ -1,4 +1,4 @@
-// The arithmetic of K29 (localmap.hip; include/mi355x_match_localmap.h): a landmark's projection and its in-view gates, the
+// The arithmetic of K29 (localmap.hip; include/mi355x_match.h): a landmark's projection and its in-view gates, the
 // window test, the key of a keypoint, the best-two pair and its order-independent merge, K26's vote as the candidate test, the
 // claim key, and the median distance of a view for the representative descriptor.  float64 geometry in the header's stated
 // operation order, integers everywhere else.  Like tracks_math.h it is plain C++: any C++ compiler builds all of it (hipcc adds

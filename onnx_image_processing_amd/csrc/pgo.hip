@@ -1,4 +1,4 @@
-// K27 pose-graph optimisation (include/mi355x_match_pgo.h): Levenberg-Marquardt on the relative-pose
+// K27 pose-graph optimisation (include/mi355x_match.h): Levenberg-Marquardt on the relative-pose
 // edges of a graph of keyframes, every damped step solved by a fixed number of preconditioned conjugate-gradient trips with
 // the block-Jacobi preconditioner, batched over independent graphs under K25's contract.  The per-edge arithmetic and the
 // preconditioner solve are pgo_math.h's (on K18's icp_update_pose and K25's LDL^T).
@@ -16,7 +16,6 @@
 // K27a pgo_cost_kernel, K27b pgo_linearise_kernel, K27c pgo_refine_kernel.  Built with -ffp-contract=off; no atomics; every
 // reduction has a fixed order: bitwise reproducible.
 #include "common.h"
-#include "../../include/mi355x_match_pgo.h"
 #include "pgo_math.h"
 
 #include <math.h>

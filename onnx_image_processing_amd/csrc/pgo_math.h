@@ -1,4 +1,4 @@
-// The arithmetic of K27 (pgo.hip; include/mi355x_match_pgo.h): Log of a rotation, the inverse left
+// The arithmetic of K27 (pgo.hip; include/mi355x_match.h): Log of a rotation, the inverse left
 // Jacobian of SO(3), one edge's residual and its two 6x6 lines, the products a linearisation collects from them and the
 // solve with a node's factored preconditioner block.  Per-edge work is float32.  Like icp_math.h it needs no HIP header:
 // a plain C++ compiler builds everything except pgo_block_factor, which takes ba_math.h's LDL^T and so exists under hipcc

@@ -1,4 +1,4 @@
-// K28 landmark tracks (include/mi355x_match_tracks.h): the pairwise matches of a window of frames -> landmark tracks in the
+// K28 landmark tracks (include/mi355x_match.h): the pairwise matches of a window of frames -> landmark tracks in the
 // form K25 reads, and the N-view triangulation of every track, batched over independent windows.
 //
 // K28a tracks_build_kernel: one workgroup of 1024 threads per window; no workgroup ever waits for another.
@@ -18,7 +18,6 @@
 // Built with -ffp-contract=off.  No global atomics; the LDS atomics are integer and order-independent (header): bitwise
 // reproducible.
 #include "common.h"
-#include "../../include/mi355x_match_tracks.h"
 #include "tracks_math.h"
 
 #include <math.h>

@@ -1,4 +1,4 @@
-// The arithmetic of K28's triangulation (tracks.hip; include/mi355x_match_tracks.h, "Triangulation"): one landmark from all
+// The arithmetic of K28's triangulation (tracks.hip; include/mi355x_match.h, "Triangulation"): one landmark from all
 // the frames that see it -- the point closest to the viewing rays in the least-squares sense, by the symmetric 3x3 cofactor
 // inverse under K25's pivot rule -- and its gates.  float64 throughout, only + - * / and sqrt, every sum in the order the
 // header states.  Like icp_math.h it is plain C++: any C++ compiler builds all of it (hipcc adds the HIP markers).

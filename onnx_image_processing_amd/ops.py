@@ -69,7 +69,7 @@ def _workspace(query: str, *args, device, refusal: str | None = None):
     """The library workspace of one call, sized by the `*_workspace_bytes` entry `query`(*args) -> (int64 tensor of
     ceil(bytes / 16) * 2 words, bytes).  The library is told the queried count, not the rounded one.  A size of 0 means
     the request is outside what the entry point covers: RuntimeError(refusal) for the ops that have a refusal text."""
-    wbytes = int(getattr(N.library_of(query), query)(*args))
+    wbytes = int(getattr(N.load(), query)(*args))
     if wbytes == 0 and refusal is not None:
         raise RuntimeError(refusal)
     return torch.empty(((wbytes + 15) // 16 * 2,), dtype=torch.int64, device=device), wbytes
@@ -1541,12 +1541,12 @@ def ba_refine(r: torch.Tensor, t: torch.Tensor, points: torch.Tensor, obs: torch
     return ro, to, xo, point_ok.view(torch.bool), cost0, cost, accepted, info, ok.view(torch.bool)
 
 
-# ---- K27 pose-graph optimisation (include/mi355x_match_pgo.h) ---------------------------------------------------------------
+# ---- K27 pose-graph optimisation (include/mi355x_match.h, "pose-graph optimisation") -----------------------------------------
 
-PGO_MAX_NODES = N.EXTRA_CONSTANTS["MI_PGO_MAX_NODES"]
-PGO_MAX_EDGES = N.EXTRA_CONSTANTS["MI_PGO_MAX_EDGES"]
-PGO_MAX_ITERATIONS = N.EXTRA_CONSTANTS["MI_PGO_MAX_ITERATIONS"]
-PGO_MAX_PCG = N.EXTRA_CONSTANTS["MI_PGO_MAX_PCG"]
+PGO_MAX_NODES = N.MI_PGO_MAX_NODES
+PGO_MAX_EDGES = N.MI_PGO_MAX_EDGES
+PGO_MAX_ITERATIONS = N.MI_PGO_MAX_ITERATIONS
+PGO_MAX_PCG = N.MI_PGO_MAX_PCG
 
 
 def _pgo_graph(r: torch.Tensor, t: torch.Tensor, edge_index: torch.Tensor, r_meas: torch.Tensor, t_meas: torch.Tensor,
@@ -1636,12 +1636,12 @@ def pgo_refine(r: torch.Tensor, t: torch.Tensor, edge_index: torch.Tensor, r_mea
     return ro, to, chi2, cost0, cost, accepted, info, ok.view(torch.bool)
 
 
-# ---- K28 landmark tracks (include/mi355x_match_tracks.h) ------------------------------------------------------------------------
+# ---- K28 landmark tracks (include/mi355x_match.h, "landmark tracks") ---------------------------------------------------------
 
-TRACKS_MAX_FRAMES = N.TRACKS_CONSTANTS["MI_TRACKS_MAX_FRAMES"]
-TRACKS_MAX_KEYPOINTS = N.TRACKS_CONSTANTS["MI_TRACKS_MAX_KEYPOINTS"]
-TRACKS_MAX_PAIRS = N.TRACKS_CONSTANTS["MI_TRACKS_MAX_PAIRS"]
-TRACKS_MAX_MATCHES = N.TRACKS_CONSTANTS["MI_TRACKS_MAX_MATCHES"]
+TRACKS_MAX_FRAMES = N.MI_TRACKS_MAX_FRAMES
+TRACKS_MAX_KEYPOINTS = N.MI_TRACKS_MAX_KEYPOINTS
+TRACKS_MAX_PAIRS = N.MI_TRACKS_MAX_PAIRS
+TRACKS_MAX_MATCHES = N.MI_TRACKS_MAX_MATCHES
 
 
 def _tracks_views(min_views: int, f: int, what: str) -> int:
@@ -1723,11 +1723,11 @@ def tracks_triangulate(r: torch.Tensor, t: torch.Tensor, obs: torch.Tensor, vis:
     return points, point_ok.view(torch.bool), vis_out.view(torch.bool), e2max, cos_par
 
 
-# ---- K29 local-map tracking (include/mi355x_match_localmap.h) --------------------------------------------------------------------
+# ---- K29 local-map tracking (include/mi355x_match.h, "local-map tracking") ---------------------------------------------------
 
-LOCALMAP_MAX_LANDMARKS = N.LOCALMAP_CONSTANTS["MI_LOCALMAP_MAX_LANDMARKS"]
-LOCALMAP_MAX_KEYPOINTS = N.LOCALMAP_CONSTANTS["MI_LOCALMAP_MAX_KEYPOINTS"]
-LOCALMAP_MAX_FRAMES = N.LOCALMAP_CONSTANTS["MI_LOCALMAP_MAX_FRAMES"]
+LOCALMAP_MAX_LANDMARKS = N.MI_LOCALMAP_MAX_LANDMARKS
+LOCALMAP_MAX_KEYPOINTS = N.MI_LOCALMAP_MAX_KEYPOINTS
+LOCALMAP_MAX_FRAMES = N.MI_LOCALMAP_MAX_FRAMES
 
 
 def _localmap_bits(bits: torch.Tensor, lead: int, what: str):

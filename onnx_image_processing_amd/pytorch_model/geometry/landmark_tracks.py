@@ -2,7 +2,7 @@
 landmark tracks (one column per landmark, one row per frame), the ambiguous tracks are rejected, and every track gets a
 point from all the frames that see it.  The host code it replaces is a union-find over the window's keypoints, a gather and
 a per-landmark least-squares loop.  K28: `mi_tracks_build`, `mi_tracks_triangulate`; the definitions are stated in
-include/mi355x_match_tracks.h.  The reference has no counterpart (its roadmap lists map management as open)."""
+include/mi355x_match.h.  The reference has no counterpart (its roadmap lists map management as open)."""
 import math
 
 import torch

@@ -2,7 +2,7 @@
 gets the descriptor of one of its observations; a new frame with a predicted pose is matched against the landmarks by
 projecting each of them and searching a small window round the projection (ORB-SLAM's SearchByProjection in TrackLocalMap),
 instead of matching the frame in full against an old keyframe and translating the matches back to landmarks on the host.
-K29: `mi_localmap_descriptors`, `mi_localmap_match`; the definitions are stated in include/mi355x_match_localmap.h.  The
+K29: `mi_localmap_descriptors`, `mi_localmap_match`; the definitions are stated in include/mi355x_match.h.  The
 reference has no counterpart (its roadmap lists tracking against a map as open)."""
 import torch
 from torch import nn

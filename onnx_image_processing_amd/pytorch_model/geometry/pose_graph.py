@@ -2,7 +2,7 @@
 KeyframeDatabase and a pose estimator found move every keyframe pose so that all of them agree.  The host call it replaces
 is g2o or GTSAM.  Levenberg-Marquardt on the relative-pose residuals, every damped step by a fixed number of block-Jacobi
 preconditioned conjugate-gradient trips, a Huber loss, every graph of the batch in one workgroup of one launch.  K27:
-`mi_pgo_refine`, `mi_pgo_cost`; the algorithm is stated in include/mi355x_match_pgo.h.  The reference has no counterpart (its
+`mi_pgo_refine`, `mi_pgo_cost`; the algorithm is stated in include/mi355x_match.h.  The reference has no counterpart (its
 roadmap lists loop closure as open)."""
 import torch
 from torch import nn

@@ -1,4 +1,4 @@
-"""The numpy oracle of K29 (include/mi355x_match_localmap.h), written from the header's words: `descriptors` and `match` are
+"""The numpy oracle of K29 (include/mi355x_match.h), written from the header's words: `descriptors` and `match` are
 loops over landmarks and keypoints in Python floats (IEEE float64, the header's operation order); `match_vectorised` is the same
 definition as whole-array numpy operations.  tests/test_localmap_host.py holds the two against each other, `descriptors` against
 a brute force over sorted lists, and the host-compiled csrc/localmap_math.h against both.

@@ -1,4 +1,4 @@
-"""numpy restatement of K27, pose-graph optimisation (include/mi355x_match_pgo.h): the edge residual
+"""numpy restatement of K27, pose-graph optimisation (include/mi355x_match.h): the edge residual
 e = (Log R_d, t_d), its exact first-order lines, the cost with K25's Huber term, the undamped system, and Levenberg-Marquardt
 in two independent forms:
   (a) refine(..., dense=False): the stated algorithm -- block-Jacobi preconditioned conjugate gradients, exactly

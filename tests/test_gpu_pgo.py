@@ -259,7 +259,7 @@ def _raw_refine(a, n, e, its, trips, huber, fill):
         return torch.full((int(np.prod(shape)) * dt.itemsize,), fill, dtype=torch.uint8, device=DEV).view(dt).reshape(shape)
     outs = [mk((b, n, 3, 3), torch.float32), mk((b, n, 3), torch.float32), mk((b, e), torch.float32), mk((b,), torch.float32),
             mk((b,), torch.float32), mk((b,), torch.int32), mk((b, n, 6, 6), torch.float32), mk((b,), torch.uint8)]
-    wbytes = int(N.load_pgo().mi_pgo_workspace_bytes(b, n, e))
+    wbytes = int(N.load().mi_pgo_workspace_bytes(b, n, e))
     work = torch.full(((wbytes + 15) // 16 * 16,), fill, dtype=torch.uint8, device=DEV)
     r, t, ei, zr, zt, info, fixed, valid = a
     N.call("mi_pgo_refine", r.data_ptr(), t.data_ptr(), ei.data_ptr(), zr.data_ptr(), zt.data_ptr(), info.data_ptr(),

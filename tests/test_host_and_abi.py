@@ -61,6 +61,15 @@ def test_binding_covers_the_header(lib_path):
         "mi_sinkhorn_dots_status_word": ([vp, i, i, i], vp),                                                   # pointer return
         "mi_abi_version": ([], i),                                                                             # (void)
         "mi_icp_linearise": ([vp] * 6 + [i, i, i, f, f, f, f, i, f, f, vp, vp, c_size_t, vp], i),              # device double *
+        # the K27 / K28 / K29 sections
+        "mi_pgo_workspace_bytes": ([i, i, i], c_size_t),
+        "mi_pgo_cost": ([vp] * 7 + [i, i, i, f, vp, vp, vp, vp], i),
+        "mi_pgo_refine": ([vp] * 8 + [i, i, i, i, i, f] + [vp] * 9 + [c_size_t, vp], i),
+        "mi_tracks_workspace_bytes": ([i] * 6, c_size_t),
+        "mi_tracks_build": ([vp] * 5 + [i] * 7 + [vp] * 7 + [c_size_t, vp], i),
+        "mi_tracks_triangulate": ([vp] * 4 + [i, i, i, i, f, f] + [vp] * 6, i),
+        "mi_localmap_descriptors": ([vp] * 2 + [i] * 5 + [vp] * 4, i),
+        "mi_localmap_match": ([vp] * 9 + [i] * 6 + [f, f, f, i, f] + [vp] * 8, i),
     }
     for name, (argtypes, restype) in pinned.items():
         assert _native.SIGNATURES[name] == argtypes and _native.RESTYPES[name] is restype, name
@@ -71,8 +80,13 @@ def test_binding_covers_the_header(lib_path):
         text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
         return len(re.findall(r"\bMI_API\b", re.sub(r"^\s*#.*$", "", text, flags=re.M)))
 
-    assert len(_native.SIGNATURES) == api_tokens(HEADER) == 118
+    assert len(_native.SIGNATURES) == api_tokens(HEADER) == 127
     assert len(_native.DEBUG_SIGNATURES) == api_tokens(DEBUG_HEADER) == 7
+    sections = {"mi_pgo_": ["mi_pgo_cost", "mi_pgo_linearise", "mi_pgo_refine", "mi_pgo_workspace_bytes"],
+                "mi_tracks_": ["mi_tracks_build", "mi_tracks_triangulate", "mi_tracks_workspace_bytes"],
+                "mi_localmap_": ["mi_localmap_descriptors", "mi_localmap_match"]}
+    for prefix, names in sections.items():                   # the entries of the K27 / K28 / K29 sections, by name
+        assert [n for n in header_functions() if n.startswith(prefix)] == names, prefix
     for name in _native.SIGNATURES:                          # the types reach the loaded functions
         fn = getattr(_native.load(), name)
         assert list(fn.argtypes) == _native.SIGNATURES[name] and fn.restype is _native.RESTYPES[name], name
@@ -107,6 +121,11 @@ _OPS_ALIASES = {
     "BA_MAX_ITERATIONS": "MI_BA_MAX_ITERATIONS", "PLACE_MAX_DESCRIPTORS": "MI_PLACE_MAX_DESCRIPTORS",
     "PLACE_MAX_KEYFRAMES": "MI_PLACE_MAX_KEYFRAMES", "PLACE_MAX_CANDIDATES": "MI_PLACE_MAX_CANDIDATES",
     "ICP_MAX_STAGES": "MI_ICP_MAX_STAGES", "ICP_MAX_ITERATIONS": "MI_ICP_MAX_ITERATIONS", "INGEST_MAX_DIM": "MI_INGEST_MAX_DIM",
+    "PGO_MAX_NODES": "MI_PGO_MAX_NODES", "PGO_MAX_EDGES": "MI_PGO_MAX_EDGES", "PGO_MAX_ITERATIONS": "MI_PGO_MAX_ITERATIONS",
+    "PGO_MAX_PCG": "MI_PGO_MAX_PCG", "TRACKS_MAX_FRAMES": "MI_TRACKS_MAX_FRAMES", "TRACKS_MAX_KEYPOINTS": "MI_TRACKS_MAX_KEYPOINTS",
+    "TRACKS_MAX_PAIRS": "MI_TRACKS_MAX_PAIRS", "TRACKS_MAX_MATCHES": "MI_TRACKS_MAX_MATCHES",
+    "LOCALMAP_MAX_LANDMARKS": "MI_LOCALMAP_MAX_LANDMARKS", "LOCALMAP_MAX_KEYPOINTS": "MI_LOCALMAP_MAX_KEYPOINTS",
+    "LOCALMAP_MAX_FRAMES": "MI_LOCALMAP_MAX_FRAMES",
     "MI_SOLVER_DEFAULT": "MI_SOLVER_DEFAULT", "MI_SOLVER_MULTI_LAUNCH": "MI_SOLVER_MULTI_LAUNCH",
     "MI_SOLVER_NO_FORK": "MI_SOLVER_NO_FORK", "MI_SOLVER_DOTS_BELOW_1024": "MI_SOLVER_DOTS_BELOW_1024",
     "MI_SCHEDULE_UNDECIDED": "MI_SCHEDULE_UNDECIDED", "MI_SCHEDULE_CALLER_HELPER": "MI_SCHEDULE_CALLER_HELPER",
@@ -124,8 +143,14 @@ def test_struct_layout_and_constants_against_the_compiler(tmp_path):
     if shutil.which("gcc") is None:
         pytest.skip("gcc not available")
     constants = {k: v for k, v in vars(_native).items() if k.startswith("MI_") and isinstance(v, (int, float))}
-    assert len(constants) == 25 + 20                  # enum members + numeric macros of the header
+    assert len(constants) == 25 + 31                  # enum members + numeric macros of the header
     assert constants["MI_SCHEDULE_UNDECIDED"] == -1 and constants["MI_POSE_MAX_N"] == 2048
+    assert {k: v for k, v in constants.items() if k.startswith(("MI_PGO_", "MI_TRACKS_", "MI_LOCALMAP_"))} == dict(
+        MI_PGO_MAX_NODES=1024, MI_PGO_MAX_EDGES=4096, MI_PGO_MAX_ITERATIONS=32, MI_PGO_MAX_PCG=256,
+        MI_TRACKS_MAX_FRAMES=16, MI_TRACKS_MAX_KEYPOINTS=1024, MI_TRACKS_MAX_PAIRS=120, MI_TRACKS_MAX_MATCHES=1024,
+        MI_LOCALMAP_MAX_LANDMARKS=2048, MI_LOCALMAP_MAX_KEYPOINTS=1024, MI_LOCALMAP_MAX_FRAMES=16)
+    assert constants["MI_TRACKS_MAX_FRAMES"] == constants["MI_BA_MAX_FRAMES"]            # K28 builds the windows K25 reads
+    assert constants["MI_LOCALMAP_MAX_LANDMARKS"] == constants["MI_BA_MAX_LANDMARKS"]    # K29 tracks the landmarks K25 refines
     fields = [name for name, _ in _native.MatchParams._fields_]
     assert fields == ["block_size", "nms_radius", "max_keypoints", "score_threshold", "border_margin", "num_pairs", "pair_geom",
                       "pair_thr", "bad_plan", "normalize_descriptors", "epsilon", "unused_score", "sinkhorn_iterations",

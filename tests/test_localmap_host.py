@@ -37,7 +37,7 @@ NAN, INF = float("nan"), float("inf")
 
 @pytest.fixture(scope="module")
 def lib():
-    return N.load_localmap()
+    return N.load()
 
 
 p_keepalive = []
@@ -262,51 +262,6 @@ def test_end_to_end_scene_gives_the_oracle_room():
     correct = int((w[1][5][got["lm_kp"][kept]] == ids).sum())
     print(f"point_ok {int(tri['point_ok'].sum())}, counts {got['counts'].tolist()}, kept {len(kept)}, on the planted keypoint {correct}")
     assert len(kept) >= 12 and correct >= 0.9 * len(kept) and got["excused"].sum() == 0
-
-
-# ---- the header of its own, the binding and the library ------------------------------------------------------------------------
-def test_the_localmap_header_is_bound_and_exported_and_compiles_as_c(lib, tmp_path):
-    """include/mi355x_match_localmap.h: every MI_API declaration is read, bound with its types and exported by
-    lib/libmi355x_match_localmap.so, which exports nothing else, and by no other library; its limits are the compiler's values;
-    it compiles as C99 on its own (it includes mi355x_match.h); ABI 3"""
-    import os
-    import re
-    import shutil
-    import subprocess
-    from ctypes import c_float, c_int, c_void_p
-    include = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(include, "mi355x_match_localmap.h")).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(mi_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(N.LOCALMAP_SIGNATURES) == ["mi_localmap_descriptors", "mi_localmap_match"]
-    assert len(re.findall(r"\bMI_API\b", re.sub(r"^\s*#.*$", "", text, flags=re.M))) == 2
-    assert not set(N.LOCALMAP_SIGNATURES) & (set(N.SIGNATURES) | set(N.EXTRA_SIGNATURES) | set(N.TRACKS_SIGNATURES)) and N.load().mi_abi_version() == 3
-    vp, i, f = c_void_p, c_int, c_float
-    assert N.LOCALMAP_SIGNATURES["mi_localmap_descriptors"] == [vp] * 2 + [i] * 5 + [vp] * 4 and N.RESTYPES["mi_localmap_descriptors"] is i
-    assert N.LOCALMAP_SIGNATURES["mi_localmap_match"] == [vp] * 9 + [i] * 6 + [f, f, f, i, f] + [vp] * 8 and N.RESTYPES["mi_localmap_match"] is i
-    for name, argtypes in N.LOCALMAP_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == argtypes and fn.restype is N.RESTYPES[name], name
-    from onnx_image_processing_amd.build import LIB, LOCALMAP_LIB, LOCALMAP_SOURCES, PGO_LIB, TRACKS_LIB
-
-    def exports(path):
-        nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        return sorted(ln.split()[-1] for ln in nm.splitlines() if ln.strip())
-    assert exports(LOCALMAP_LIB) == declared and LOCALMAP_SOURCES == ["localmap.hip"]             # ... and nothing else
-    assert not any(set(declared) & set(exports(other)) for other in (LIB, PGO_LIB, TRACKS_LIB))
-    assert N.library_of("mi_localmap_match") is lib and N.library_of("mi_localmap_descriptors") is lib
-    assert N.library_of("mi_tracks_build") is N.load_tracks() and N.library_of("mi_pgo_cost") is N.load_pgo() and N.library_of("mi_ba_cost") is N.load()
-    assert N.LOCALMAP_CONSTANTS == dict(MI_LOCALMAP_MAX_LANDMARKS=2048, MI_LOCALMAP_MAX_KEYPOINTS=1024, MI_LOCALMAP_MAX_FRAMES=16)
-    assert N.LOCALMAP_CONSTANTS["MI_LOCALMAP_MAX_LANDMARKS"] == N.MI_BA_MAX_LANDMARKS
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not available")
-    src = tmp_path / "localmap_header.c"
-    src.write_text('#include <stdio.h>\n#include "mi355x_match_localmap.h"\nint main(void) {\n'
-                   + "".join(f'  printf("{k} %d\\n", (int){k});\n' for k in N.LOCALMAP_CONSTANTS) + "  return MI_OK;\n}\n")
-    exe = str(tmp_path / "localmap_header")
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", f"-I{include}", str(src), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()
-    assert dict(zip(out[::2], map(int, out[1::2]))) == N.LOCALMAP_CONSTANTS
 
 
 # ---- argument checks ------------------------------------------------------------------------------------------------------------

@@ -25,7 +25,7 @@ NAN, INF = float("nan"), float("inf")
 
 @pytest.fixture(scope="module")
 def lib():
-    return N.load_tracks()
+    return N.load()
 
 
 p_keepalive = []
@@ -254,57 +254,6 @@ def test_native_harness_under_the_host_sanitizers(tmp_path):
     exe = build_host(tmp_path, "tracks_host.cpp", hip=True, extra=SANITIZE)
     names = ["tracks", "ba-5x130", "degenerate", "behind"]
     assert len(run_host(exe, "tri", _tri_text(names))) == sum(len(o["point_ok"]) for o in _tri_wants(names))
-
-
-# ---- the header of its own, the binding and the library ------------------------------------------------------------------------
-def test_the_tracks_header_is_bound_and_exported_and_compiles_as_c(lib, tmp_path):
-    """include/mi355x_match_tracks.h: every MI_API declaration is read, bound with its types and exported by
-    lib/libmi355x_match_tracks.so, which exports nothing else, and by no other library; its limits are the compiler's values;
-    it compiles as C99 on its own (it includes mi355x_match.h); ABI 3"""
-    import os
-    import re
-    import shutil
-    import subprocess
-    from ctypes import c_float, c_int, c_size_t, c_void_p
-    include = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(include, "mi355x_match_tracks.h")).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(mi_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(N.TRACKS_SIGNATURES) == ["mi_tracks_build", "mi_tracks_triangulate", "mi_tracks_workspace_bytes"]
-    assert len(re.findall(r"\bMI_API\b", re.sub(r"^\s*#.*$", "", text, flags=re.M))) == 3
-    assert not set(N.TRACKS_SIGNATURES) & (set(N.SIGNATURES) | set(N.EXTRA_SIGNATURES)) and N.load().mi_abi_version() == 3
-    vp, i, f = c_void_p, c_int, c_float
-    assert N.TRACKS_SIGNATURES["mi_tracks_workspace_bytes"] == [i] * 6 and N.RESTYPES["mi_tracks_workspace_bytes"] is c_size_t
-    assert N.TRACKS_SIGNATURES["mi_tracks_build"] == [vp] * 5 + [i] * 7 + [vp] * 7 + [c_size_t, vp] and N.RESTYPES["mi_tracks_build"] is i
-    assert N.TRACKS_SIGNATURES["mi_tracks_triangulate"] == [vp] * 4 + [i, i, i, i, f, f] + [vp] * 6
-    for name, argtypes in N.TRACKS_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == argtypes and fn.restype is N.RESTYPES[name], name
-    from onnx_image_processing_amd.build import LIB, PGO_LIB, TRACKS_LIB, TRACKS_SOURCES
-
-    def exports(path):
-        nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        return sorted(ln.split()[-1] for ln in nm.splitlines() if ln.strip())
-    assert exports(TRACKS_LIB) == declared and TRACKS_SOURCES == ["tracks.hip"]                 # ... and nothing else
-    assert not set(declared) & set(exports(LIB)) and not set(declared) & set(exports(PGO_LIB))
-    assert N.library_of("mi_tracks_build") is lib and N.library_of("mi_tracks_workspace_bytes") is lib
-    assert N.TRACKS_CONSTANTS == dict(MI_TRACKS_MAX_FRAMES=16, MI_TRACKS_MAX_KEYPOINTS=1024, MI_TRACKS_MAX_PAIRS=120, MI_TRACKS_MAX_MATCHES=1024)
-    assert N.TRACKS_CONSTANTS["MI_TRACKS_MAX_FRAMES"] == N.MI_BA_MAX_FRAMES
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not available")
-    src = tmp_path / "tracks_header.c"
-    src.write_text('#include <stdio.h>\n#include "mi355x_match_tracks.h"\nint main(void) {\n'
-                   + "".join(f'  printf("{k} %d\\n", (int){k});\n' for k in N.TRACKS_CONSTANTS) + "  return MI_OK;\n}\n")
-    exe = str(tmp_path / "tracks_header")
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", f"-I{include}", str(src), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()
-    assert dict(zip(out[::2], map(int, out[1::2]))) == N.TRACKS_CONSTANTS
-
-
-def test_the_pose_graph_pins_still_hold():
-    assert sorted(N.EXTRA_SIGNATURES) == ["mi_pgo_cost", "mi_pgo_linearise", "mi_pgo_refine", "mi_pgo_workspace_bytes"]
-    assert N.EXTRA_CONSTANTS == dict(MI_PGO_MAX_NODES=1024, MI_PGO_MAX_EDGES=4096, MI_PGO_MAX_ITERATIONS=32, MI_PGO_MAX_PCG=256)
-    assert N.library_of("mi_ba_cost") is N.load() and N.library_of("mi_pgo_cost") is N.load_pgo() and N.load_pgo() is not N.load_tracks()
 
 
 # ---- argument checks ------------------------------------------------------------------------------------------------------------

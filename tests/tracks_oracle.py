@@ -1,4 +1,4 @@
-"""numpy oracle of K28 (include/mi355x_match_tracks.h) for ONE window: a serial union-find over the active matches, then the
+"""numpy oracle of K28 (include/mi355x_match.h) for ONE window: a serial union-find over the active matches, then the
 header's definitions word for word (label = smallest node, conflict, eligibility, the order by (length descending, label
 ascending), the cut at L), and the N-view triangulation in float64 in the header's stated operation order."""
 import numpy as np
