@@ -107,8 +107,14 @@ globals().update(_constants)            # MI_OK, MI_BAD_HARD, MI_SOLVER_NO_FORK,
 # not part of the product ABI; nothing in this package calls them
 DEBUG_SIGNATURES, _debug_restypes, _, _ = _read("mi355x_match_debug.h")
 RESTYPES.update(_debug_restypes)
+# include/mi355x_match_sim3.h: the similarity-alignment section of the ABI (K30), a header and a library of its own
+# (lib/libmi355x_match_sim3.so, load_sim3()): the product library exports include/mi355x_match.h and nothing else.  call()
+# finds the library of a name by itself.  Its limits are SIM3_CONSTANTS["MI_SIM3_MAX_N"], ...: a dictionary.
+SIM3_SIGNATURES, _sim3_restypes, _, SIM3_CONSTANTS = _read("mi355x_match_sim3.h")
+RESTYPES.update(_sim3_restypes)
 
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_debug.so")
+SIM3_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_sim3.so")
 
 _lib = None            # the library every call() goes through: the product, unless inside debug_library()
 _product = None
@@ -138,6 +144,22 @@ def load() -> ctypes.CDLL:
             _product = _open(LIB_PATH, SIGNATURES)
         _lib = _product
     return _lib
+
+
+_sim3 = None
+
+
+def load_sim3() -> ctypes.CDLL:
+    """lib/libmi355x_match_sim3.so, the entries of include/mi355x_match_sim3.h, loaded once."""
+    global _sim3
+    if _sim3 is None:
+        _sim3 = _open(SIM3_LIB_PATH, SIM3_SIGNATURES)
+    return _sim3
+
+
+def library_of(name: str) -> ctypes.CDLL:
+    """The library that exports the entry `name`."""
+    return load_sim3() if name in SIM3_SIGNATURES else load()
 
 
 class debug_library:
@@ -214,7 +236,7 @@ def timings_ms() -> dict:
 
 
 def call(name: str, *args) -> None:
-    fn = getattr(load(), name)
+    fn = getattr(library_of(name), name)
     if _timers is None or (_timed_names is not None and name not in _timed_names):
         check(fn(*args), name)
         return

@@ -69,7 +69,7 @@ def _workspace(query: str, *args, device, refusal: str | None = None):
     """The library workspace of one call, sized by the `*_workspace_bytes` entry `query`(*args) -> (int64 tensor of
     ceil(bytes / 16) * 2 words, bytes).  The library is told the queried count, not the rounded one.  A size of 0 means
     the request is outside what the entry point covers: RuntimeError(refusal) for the ops that have a refusal text."""
-    wbytes = int(getattr(N.load(), query)(*args))
+    wbytes = int(getattr(N.library_of(query), query)(*args))
     if wbytes == 0 and refusal is not None:
         raise RuntimeError(refusal)
     return torch.empty(((wbytes + 15) // 16 * 2,), dtype=torch.int64, device=device), wbytes
@@ -1329,6 +1329,112 @@ def rigid_ransac(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | N
     _ransac("mi_rigid_ransac", "rigid_ransac", rows, num_hypotheses, threshold, refine_rounds, seed,
             (r, t, inlier, best_h, count, rmse, ok))
     return r, t, inlier.view(torch.bool), best_h, count, rmse, ok.view(torch.bool)
+
+
+# ---- K30 similarity alignment (include/mi355x_match_sim3.h) -----------------------------------------------------------------
+
+SIM3_MAX_N = N.SIM3_CONSTANTS["MI_SIM3_MAX_N"]
+SIM3_POINT, SIM3_REPROJ = N.SIM3_CONSTANTS["MI_SIM3_POINT"], N.SIM3_CONSTANTS["MI_SIM3_REPROJ"]
+
+
+def _sim3_pairs(pts1, pts2, valid, what: str, metric: int | None = None):
+    """(B, N, 3) points of both maps"""
+    if metric is not None and metric not in (SIM3_POINT, SIM3_REPROJ):
+        raise RuntimeError(f"{what}: metric must be SIM3_POINT ({SIM3_POINT}) or SIM3_REPROJ ({SIM3_REPROJ}), got {metric}")
+    return _row_pairs(pts1, pts2, valid, what, (3, 3), SIM3_MAX_N, ("pts1", "pts2"))
+
+
+def sim3_hypotheses(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, num_hypotheses: int, threshold: float,
+                    metric: int = SIM3_REPROJ, seed: int = 0):
+    """`mi_sim3_hypotheses`: H 3-point similarities X2 = s R X1 + t per pair from the counter-based sampler, each scored on
+    every valid row under `metric` -> (srt_h (B, H, 13): R row-major, t, s; MSAC cost (B, H) float32, inlier count (B, H)
+    int32)."""
+    qa, qb, v, b, n = _sim3_pairs(pts1, pts2, valid, "sim3_hypotheses", metric)
+    h = int(num_hypotheses)
+    m_h = torch.empty((b, h, 13), dtype=F32, device=qa.device)
+    cost = torch.empty((b, h), dtype=F32, device=qa.device)
+    count = torch.empty((b, h), dtype=I32, device=qa.device)
+    N.call("mi_sim3_hypotheses", qa.data_ptr(), qb.data_ptr(), N.opt(v, U8, "valid"), b, n, h, float(threshold), int(metric),
+           int(seed) & 0xFFFFFFFF, m_h.data_ptr(), cost.data_ptr(), count.data_ptr(), N.stream_ptr())
+    return m_h, cost, count
+
+
+def sim3_refit(pts1: torch.Tensor, pts2: torch.Tensor, mask: torch.Tensor):
+    """`mi_sim3_refit`: Horn's rotation and Umeyama's scale over the masked rows -> (s (B,), R (B, 3, 3), t (B, 3), ok (B,)
+    bool)."""
+    q1, q2, v, b, n = _sim3_pairs(pts1, pts2, mask, "sim3_refit")
+    if v is None:
+        raise RuntimeError("sim3_refit needs a mask")
+    r, t = _pose_outputs(b, q1.device)
+    s = torch.empty((b,), dtype=F32, device=q1.device)
+    ok = torch.empty((b,), dtype=U8, device=q1.device)
+    N.call("mi_sim3_refit", q1.data_ptr(), q2.data_ptr(), N.dev(v, U8, "mask"), b, n, s.data_ptr(), r.data_ptr(), t.data_ptr(),
+           ok.data_ptr(), N.stream_ptr())
+    return s, r, t, ok.view(torch.bool)
+
+
+def sim3_ransac(pts1: torch.Tensor, pts2: torch.Tensor, valid: torch.Tensor | None, num_hypotheses: int, threshold: float,
+                metric: int = SIM3_REPROJ, refine_rounds: int = 3, seed: int = 0):
+    """`mi_sim3_ransac`: hypotheses, MSAC selection and refine_rounds rounds of refit-and-rescore in two launches ->
+    (s (B,), R (B, 3, 3), t (B, 3), inlier (B, N) bool, best_h (B,) int32, count (B,) int32, rmse (B,) float32 in the metric's
+    units, ok (B,) bool)."""
+    qa, qb, v, b, n = _sim3_pairs(pts1, pts2, valid, "sim3_ransac", metric)
+    dev, h = qa.device, int(num_hypotheses)
+    r, t = _pose_outputs(b, dev)
+    s = torch.empty((b,), dtype=F32, device=dev)
+    inlier, best_h, count = _ransac_outputs(b, n, dev)
+    rmse = torch.empty((b,), dtype=F32, device=dev)
+    ok = torch.empty((b,), dtype=U8, device=dev)
+    work, wbytes = _workspace("mi_sim3_ransac_workspace_bytes", b, n, h, device=dev,
+                              refusal=f"sim3_ransac: unsupported request (batch {b}, N {n}, {h} hypotheses)")
+    N.call("mi_sim3_ransac", qa.data_ptr(), qb.data_ptr(), N.opt(v, U8, "valid"), b, n, h, float(threshold), int(metric),
+           int(refine_rounds), int(seed) & 0xFFFFFFFF, s.data_ptr(), r.data_ptr(), t.data_ptr(), inlier.data_ptr(),
+           best_h.data_ptr(), count.data_ptr(), rmse.data_ptr(), ok.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    return s, r, t, inlier.view(torch.bool), best_h, count, rmse, ok.view(torch.bool)
+
+
+def sim3_apply(s: torch.Tensor, r: torch.Tensor, t: torch.Tensor, r_frames: torch.Tensor | None, t_frames: torch.Tensor | None,
+               points: torch.Tensor | None):
+    """`mi_sim3_apply`: map 1 moved into map 2's frame and units by (s (B,), R (B, 3, 3), t (B, 3)): frame poses r_frames
+    (B, F, 3, 3), t_frames (B, F, 3) (X_c = R_k X + t_k) and landmarks points (B, L, 3) -> (r_out, t_out, points_out) with
+    R_k' = R_k R^T, t_k' = s t_k - R_k' t, X' = s R X + t, float64 rounded once.  The poses or the points may be None (then
+    None comes back), not both."""
+    ss, rr, tt = s.float().contiguous(), r.float().contiguous(), t.float().contiguous()
+    if ss.dim() != 1 or ss.shape[0] < 1 or tuple(rr.shape) != (ss.shape[0], 3, 3) or tuple(tt.shape) != (ss.shape[0], 3):
+        raise RuntimeError(f"sim3_apply: s, R, t must be (B,), (B, 3, 3), (B, 3), got {tuple(s.shape)}, {tuple(r.shape)}, {tuple(t.shape)}")
+    b, dev = int(ss.shape[0]), ss.device
+    if (r_frames is None) != (t_frames is None):
+        raise RuntimeError("sim3_apply: r_frames and t_frames must be given together")
+    if r_frames is None and points is None:
+        raise RuntimeError("sim3_apply needs frame poses or points")
+    f = l = 0
+    rk = tk = x = r_out = t_out = x_out = None
+    if r_frames is not None:
+        rk, tk = r_frames.float().contiguous(), t_frames.float().contiguous()
+        if rk.dim() != 4 or tuple(rk.shape[::3]) != (b, 3) or rk.shape[2] != 3 or tuple(tk.shape) != (b, rk.shape[1], 3):
+            raise RuntimeError(f"sim3_apply: frame poses must be ({b}, F, 3, 3) and ({b}, F, 3), got {tuple(r_frames.shape)}, "
+                               f"{tuple(t_frames.shape)}")
+        f = int(rk.shape[1])
+    if points is not None:
+        x = points.float().contiguous()
+        if x.dim() != 3 or x.shape[0] != b or x.shape[2] != 3:
+            raise RuntimeError(f"sim3_apply: points must be ({b}, L, 3), got {tuple(points.shape)}")
+        l = int(x.shape[1])
+    if f + l < 1:
+        raise RuntimeError("sim3_apply: no frame and no point to move")
+    if f:
+        r_out, t_out = torch.empty_like(rk), torch.empty_like(tk)
+    if l:
+        x_out = torch.empty_like(x)
+    N.call("mi_sim3_apply", N.dev(ss, F32, "s"), N.dev(rr, F32, "R"), N.dev(tt, F32, "t"), b, f, l,
+           N.dev(rk, F32, "r_frames") if f else None, N.dev(tk, F32, "t_frames") if f else None,
+           N.dev(x, F32, "points") if l else None, r_out.data_ptr() if f else None, t_out.data_ptr() if f else None,
+           x_out.data_ptr() if l else None, N.stream_ptr())
+    if r_frames is not None and not f:
+        r_out, t_out = torch.empty_like(rk), torch.empty_like(tk)
+    if points is not None and not l:
+        x_out = torch.empty_like(x)
+    return r_out, t_out, x_out
 
 
 # ---- K23 absolute pose (include/mi355x_match.h, "absolute pose") ------------------------------------------------------------

@@ -714,3 +714,45 @@ def synth_localmap_window(seed: int, frames: int, keypoints: int, landmarks: int
     R_pred = (E @ R[-1]).astype(np.float32)
     t_pred = (E @ t[-1] + translation * np.ones(3) / np.sqrt(3.0)).astype(np.float32)
     return (*base_window, np.ascontiguousarray(bits).view(np.int32), R_pred, t_pred, twin_of)
+
+
+def synth_sim3_maps(seed: int, n: int, outliers: float, ray_noise: float, scale: float):
+    """Two camera-frame point sets of one scene for the similarity kernels (K30): (pts1, pts2, s, R, t, inlier).  pts1, pts2
+    (n, 3) float32: the landmarks in keyframe 1's camera frame and map-1 units, and in keyframe 2's camera frame and map-2
+    units; s = scale, R (3, 3), t (3,) float64 with X2 = s R X1 + t for the noise-free points; inlier (n,) bool, the planted
+    inlier mask.
+
+    synth_rgbd_pair's geometry: points uniform in [-2, 2] x [-1.5, 1.5] x [3, 9] in frame 1, R the Rodrigues rotation of a
+    N(0, 0.08^2) vector, t = scale * RGBD_BASELINE in a uniformly random direction.  The noise is the depth error of a
+    triangulated point, ALONG the rays: each point of either set is multiplied by max(1 + ray_noise * N(0, 1), 0.1), so its
+    projection into its own camera does not move.  round(outliers * n) rows, chosen by a hashed ranking, are outliers: their
+    point of frame 2 is scale times a fresh uniform point of the same box.  float64 arithmetic on hashed integers: the same
+    scene everywhere."""
+    if n < 1 or not 0 <= outliers <= 1 or not ray_noise >= 0 or not (scale > 0 and scale < float("inf")):
+        raise ValueError(f"synth_sim3_maps: n >= 1, 0 <= outliers <= 1, ray_noise >= 0, 0 < scale < inf, got {n}, {outliers}, "
+                         f"{ray_noise}, {scale}")
+    idx = np.arange(n, dtype=np.uint64)
+
+    def uni(rows, salt):
+        r = np.asarray(rows, dtype=np.uint64)
+        return ((_hash3(seed, r, np.uint64(salt) + 0 * r, 53) >> np.uint64(11)).astype(np.float64) + 0.5) / float(1 << 53)
+
+    def normal(rows, salt):
+        return np.sqrt(-2.0 * np.log(uni(rows, salt))) * np.cos(2.0 * np.pi * uni(rows, salt + 1))
+
+    def box(salt):
+        return np.stack([-2.0 + 4.0 * uni(idx, salt), -1.5 + 3.0 * uni(idx, salt + 1), 3.0 + 6.0 * uni(idx, salt + 2)], axis=1)
+
+    three = np.arange(3)
+    R = _rodrigues64(0.08 * normal(three, 40))
+    d = normal(three, 42)
+    t = float(scale) * RGBD_BASELINE * d / np.linalg.norm(d)
+    x1 = box(0)
+    x2 = float(scale) * (x1 @ R.T) + t
+    n_out = int(round(outliers * n))
+    inlier = np.ones(n, dtype=bool)
+    inlier[np.argsort(_hash3(seed, idx, np.uint64(15) + 0 * idx, 53), kind="stable")[:n_out]] = False
+    x2[~inlier] = (float(scale) * box(4))[~inlier]
+    x1 = x1 * np.maximum(1.0 + ray_noise * normal(idx, 8), 0.1)[:, None]
+    x2 = x2 * np.maximum(1.0 + ray_noise * normal(idx, 10), 0.1)[:, None]
+    return x1.astype(np.float32), x2.astype(np.float32), float(scale), R, t, inlier
