@@ -112,9 +112,14 @@ RESTYPES.update(_debug_restypes)
 # finds the library of a name by itself.  Its limits are SIM3_CONSTANTS["MI_SIM3_MAX_N"], ...: a dictionary.
 SIM3_SIGNATURES, _sim3_restypes, _, SIM3_CONSTANTS = _read("mi355x_match_sim3.h")
 RESTYPES.update(_sim3_restypes)
+# include/mi355x_match_simgraph.h: the similarity pose-graph section (K31), laid out as K30's: lib/libmi355x_match_simgraph.so,
+# load_simgraph(), SIMGRAPH_CONSTANTS["MI_SIMGRAPH_MAX_NODES"], ...
+SIMGRAPH_SIGNATURES, _simgraph_restypes, _, SIMGRAPH_CONSTANTS = _read("mi355x_match_simgraph.h")
+RESTYPES.update(_simgraph_restypes)
 
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_debug.so")
 SIM3_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_sim3.so")
+SIMGRAPH_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_simgraph.so")
 
 _lib = None            # the library every call() goes through: the product, unless inside debug_library()
 _product = None
@@ -157,9 +162,22 @@ def load_sim3() -> ctypes.CDLL:
     return _sim3
 
 
+_simgraph = None
+
+
+def load_simgraph() -> ctypes.CDLL:
+    """lib/libmi355x_match_simgraph.so, the entries of include/mi355x_match_simgraph.h, loaded once."""
+    global _simgraph
+    if _simgraph is None:
+        _simgraph = _open(SIMGRAPH_LIB_PATH, SIMGRAPH_SIGNATURES)
+    return _simgraph
+
+
 def library_of(name: str) -> ctypes.CDLL:
     """The library that exports the entry `name`."""
-    return load_sim3() if name in SIM3_SIGNATURES else load()
+    if name in SIM3_SIGNATURES:
+        return load_sim3()
+    return load_simgraph() if name in SIMGRAPH_SIGNATURES else load()
 
 
 class debug_library:

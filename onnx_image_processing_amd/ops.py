@@ -1742,6 +1742,150 @@ def pgo_refine(r: torch.Tensor, t: torch.Tensor, edge_index: torch.Tensor, r_mea
     return ro, to, chi2, cost0, cost, accepted, info, ok.view(torch.bool)
 
 
+# ---- K31 Sim(3) pose-graph optimisation (include/mi355x_match_simgraph.h) ----------------------------------------------------
+
+SIMGRAPH_MAX_NODES = N.SIMGRAPH_CONSTANTS["MI_SIMGRAPH_MAX_NODES"]
+SIMGRAPH_MAX_EDGES = N.SIMGRAPH_CONSTANTS["MI_SIMGRAPH_MAX_EDGES"]
+SIMGRAPH_MAX_ITERATIONS = N.SIMGRAPH_CONSTANTS["MI_SIMGRAPH_MAX_ITERATIONS"]
+SIMGRAPH_MAX_PCG = N.SIMGRAPH_CONSTANTS["MI_SIMGRAPH_MAX_PCG"]
+
+
+def _simgraph_graph(s: torch.Tensor, r: torch.Tensor, t: torch.Tensor, edge_index: torch.Tensor, s_meas: torch.Tensor,
+                    r_meas: torch.Tensor, t_meas: torch.Tensor, information: torch.Tensor, edge_valid: torch.Tensor | None, huber: float,
+                    what: str, fixed: torch.Tensor | None = None):
+    """The state and the edges of a batch of similarity graphs as the C ABI reads them: s (B, N), r (B, N, 3, 3), t (B, N, 3),
+    edge_index (B, E, 2), s_meas (B, E), r_meas (B, E, 3, 3), t_meas (B, E, 3), information (B, E, 7, 7), edge_valid (B, E) or
+    None (every edge); fixed (B, N) where the entry takes it (its pointer is then the last of `ptrs`)."""
+    ss, rr, tt, zs, zr, zt, om = (a.float().contiguous() for a in (s, r, t, s_meas, r_meas, t_meas, information))
+    if rr.dim() != 4 or tuple(rr.shape[2:]) != (3, 3) or edge_index.dim() != 3 or edge_index.shape[-1] != 2:
+        raise RuntimeError(f"{what}: rotations must be (B, N, 3, 3) and edge_index (B, E, 2), got {tuple(r.shape)} and {tuple(edge_index.shape)}")
+    b, n, e = int(rr.shape[0]), int(rr.shape[1]), int(edge_index.shape[1])
+    if edge_valid is None:
+        edge_valid = torch.ones((b, e), dtype=torch.bool, device=rr.device)
+    if (tuple(ss.shape) != (b, n) or tuple(tt.shape) != (b, n, 3) or edge_index.shape[0] != b or tuple(zs.shape) != (b, e)
+            or tuple(zr.shape) != (b, e, 3, 3) or tuple(zt.shape) != (b, e, 3) or tuple(om.shape) != (b, e, 7, 7)
+            or tuple(edge_valid.shape) != (b, e)):
+        raise RuntimeError(f"{what}: expected s ({b}, {n}), t ({b}, {n}, 3), s_meas ({b}, {e}), r_meas ({b}, {e}, 3, 3), t_meas ({b}, {e}, 3), "
+                           f"information ({b}, {e}, 7, 7) and edge_valid ({b}, {e}), got {tuple(s.shape)}, {tuple(t.shape)}, "
+                           f"{tuple(s_meas.shape)}, {tuple(r_meas.shape)}, {tuple(t_meas.shape)}, {tuple(information.shape)} and "
+                           f"{tuple(edge_valid.shape)}")
+    if not 2 <= n <= SIMGRAPH_MAX_NODES or not 1 <= e <= SIMGRAPH_MAX_EDGES or b < 1:
+        raise RuntimeError(f"{what}: N = {n} nodes and E = {e} edges, supported: 2 .. {SIMGRAPH_MAX_NODES} and 1 .. {SIMGRAPH_MAX_EDGES}")
+    if not (huber >= 0 and huber < float("inf")):
+        raise RuntimeError(f"{what}: huber must be finite and not negative, got {huber}")
+    if fixed is not None and tuple(fixed.shape) != (b, n):
+        raise RuntimeError(f"{what}: fixed must be ({b}, {n}), got {tuple(fixed.shape)}")
+    ei = edge_index.to(I32).contiguous()
+    ev, fx = _validity_bytes(edge_valid), _validity_bytes(fixed)
+    ptrs = (N.dev(ss, F32, "s"), N.dev(rr, F32, "r"), N.dev(tt, F32, "t"), N.dev(ei, I32, "edge_index"), N.dev(zs, F32, "s_meas"),
+            N.dev(zr, F32, "r_meas"), N.dev(zt, F32, "t_meas"), N.dev(om, F32, "information"),
+            N.dev(ev, U8, "edge_valid")) + (() if fx is None else (N.dev(fx, U8, "fixed"),))
+    return ptrs, (ss, rr, tt, ei, zs, zr, zt, om, ev, fx), b, n, e
+
+
+def simgraph_cost(s: torch.Tensor, r: torch.Tensor, t: torch.Tensor, edge_index: torch.Tensor, s_meas: torch.Tensor,
+                  r_meas: torch.Tensor, t_meas: torch.Tensor, information: torch.Tensor, edge_valid: torch.Tensor | None = None,
+                  huber: float = 0.0):
+    """`mi_simgraph_cost`: the cost of a batch of similarity graphs -> (chi2 (B, E) float32: e^T Omega e of every active edge, 0
+    elsewhere; cost (B,) float32; active (B, E) bool)."""
+    ptrs, keep, b, n, e = _simgraph_graph(s, r, t, edge_index, s_meas, r_meas, t_meas, information, edge_valid, huber, "simgraph_cost")
+    dev = keep[0].device
+    chi2 = torch.empty((b, e), dtype=F32, device=dev)
+    cost = torch.empty((b,), dtype=F32, device=dev)
+    active = torch.empty((b, e), dtype=U8, device=dev)
+    N.call("mi_simgraph_cost", *ptrs, b, n, e, float(huber), chi2.data_ptr(), cost.data_ptr(), active.data_ptr(), N.stream_ptr())
+    return chi2, cost, active.view(torch.bool)
+
+
+def simgraph_linearise(s: torch.Tensor, r: torch.Tensor, t: torch.Tensor, edge_index: torch.Tensor, s_meas: torch.Tensor,
+                       r_meas: torch.Tensor, t_meas: torch.Tensor, information: torch.Tensor, fixed: torch.Tensor,
+                       edge_valid: torch.Tensor | None = None, huber: float = 0.0):
+    """`mi_simgraph_linearise`: one undamped linearisation -> (diag (B, N, 7, 7): the diagonal blocks, zero for fixed and
+    edgeless nodes; off (B, E, 7, 7): the (i, j) block of every edge, zero for inactive edges and edges at a fixed node; g
+    (B, N, 7); cost (B,))."""
+    ptrs, keep, b, n, e = _simgraph_graph(s, r, t, edge_index, s_meas, r_meas, t_meas, information, edge_valid, huber,
+                                          "simgraph_linearise", fixed)
+    dev = keep[0].device
+    diag = torch.empty((b, n, 7, 7), dtype=F32, device=dev)
+    off = torch.empty((b, e, 7, 7), dtype=F32, device=dev)
+    g = torch.empty((b, n, 7), dtype=F32, device=dev)
+    cost = torch.empty((b,), dtype=F32, device=dev)
+    work, wbytes = _workspace("mi_simgraph_workspace_bytes", b, n, e, device=dev)
+    N.call("mi_simgraph_linearise", *ptrs, b, n, e, float(huber), diag.data_ptr(), off.data_ptr(), g.data_ptr(),
+           cost.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    return diag, off, g, cost
+
+
+def simgraph_refine(s: torch.Tensor, r: torch.Tensor, t: torch.Tensor, edge_index: torch.Tensor, s_meas: torch.Tensor,
+                    r_meas: torch.Tensor, t_meas: torch.Tensor, information: torch.Tensor, fixed: torch.Tensor,
+                    edge_valid: torch.Tensor | None = None, iterations: int = 10, pcg_iterations: int = 64, huber: float = 0.0):
+    """`mi_simgraph_refine`: `iterations` Levenberg-Marquardt iterations of `pcg_iterations` conjugate-gradient trips each on
+    every graph in one launch -> (s (B, N), R (B, N, 3, 3), t (B, N, 3), chi2 (B, E), cost0 (B,), cost (B,), accepted (B,) int32,
+    info (B, N, 7, 7): each node's conditional information given its neighbours, ok (B,) bool).  Fixed nodes and nodes without
+    an active edge come back unchanged; where ok is False (no active edge, no fixed node, no free node with an edge, or a cost
+    that is not finite -- a node scale that is not positive among the causes) everything does."""
+    if not 1 <= int(iterations) <= SIMGRAPH_MAX_ITERATIONS:
+        raise RuntimeError(f"simgraph_refine: iterations must be in 1 .. {SIMGRAPH_MAX_ITERATIONS}, got {iterations}")
+    if not 1 <= int(pcg_iterations) <= SIMGRAPH_MAX_PCG:
+        raise RuntimeError(f"simgraph_refine: pcg_iterations must be in 1 .. {SIMGRAPH_MAX_PCG}, got {pcg_iterations}")
+    ptrs, keep, b, n, e = _simgraph_graph(s, r, t, edge_index, s_meas, r_meas, t_meas, information, edge_valid, huber,
+                                          "simgraph_refine", fixed)
+    dev = keep[0].device
+    so = torch.empty((b, n), dtype=F32, device=dev)
+    ro = torch.empty((b, n, 3, 3), dtype=F32, device=dev)
+    to = torch.empty((b, n, 3), dtype=F32, device=dev)
+    chi2 = torch.empty((b, e), dtype=F32, device=dev)
+    cost0 = torch.empty((b,), dtype=F32, device=dev)
+    cost = torch.empty((b,), dtype=F32, device=dev)
+    accepted = torch.empty((b,), dtype=I32, device=dev)
+    info = torch.empty((b, n, 7, 7), dtype=F32, device=dev)
+    ok = torch.empty((b,), dtype=U8, device=dev)
+    work, wbytes = _workspace("mi_simgraph_workspace_bytes", b, n, e, device=dev)
+    N.call("mi_simgraph_refine", *ptrs, b, n, e, int(iterations), int(pcg_iterations), float(huber), so.data_ptr(), ro.data_ptr(),
+           to.data_ptr(), chi2.data_ptr(), cost0.data_ptr(), cost.data_ptr(), accepted.data_ptr(), info.data_ptr(), ok.data_ptr(),
+           work.data_ptr(), wbytes, N.stream_ptr())
+    return so, ro, to, chi2, cost0, cost, accepted, info, ok.view(torch.bool)
+
+
+def simgraph_correct(r_old: torch.Tensor | None, t_old: torch.Tensor | None, s: torch.Tensor | None, r: torch.Tensor | None,
+                     t: torch.Tensor | None, points: torch.Tensor | None, ref: torch.Tensor | None):
+    """`mi_simgraph_correct`: the map correction after a Sim(3) graph optimisation.  r_old (B, N, 3, 3), t_old (B, N, 3): the
+    metric keyframe poses before; s (B, N), r, t: the optimised state; points (B, L, 3) with ref (B, L) integer: landmarks and
+    the keyframe each is attached to -> (r_out, t_out, points_out): the metric poses (R', t' / s') and the landmarks
+    R'^T ((R_old X + t_old) - t') / s', float64 rounded once; a landmark whose ref is outside [0, N) is copied.  The five pose
+    arrays or the two landmark arrays may be None (then None comes back for them), not both."""
+    poses, marks = (r_old, t_old, s, r, t), (points, ref)
+    if any(a is None for a in poses) != all(a is None for a in poses) or (points is None) != (ref is None):
+        raise RuntimeError("simgraph_correct: r_old, t_old, s, r, t are given together or not at all, and so are points and ref")
+    if poses[0] is None and points is None:
+        raise RuntimeError("simgraph_correct needs poses or points")
+    b = int((s if s is not None else points).shape[0])
+    n = l = 0
+    ro = to = so = rn = tn = x = rf = r_out = t_out = x_out = None
+    if s is not None:
+        ro, to, so, rn, tn = (a.float().contiguous() for a in poses)
+        n = int(so.shape[1]) if so.dim() == 2 else -1
+        if n < 0 or any(tuple(a.shape) != (b, n, 3, 3) for a in (ro, rn)) or any(tuple(a.shape) != (b, n, 3) for a in (to, tn)):
+            raise RuntimeError(f"simgraph_correct: poses must be (B, N, 3, 3), (B, N, 3), (B, N), (B, N, 3, 3), (B, N, 3), got "
+                               f"{[tuple(a.shape) for a in poses]}")
+    if points is not None:
+        x, rf = points.float().contiguous(), ref.to(I32).contiguous()
+        if x.dim() != 3 or x.shape[0] != b or x.shape[2] != 3 or tuple(rf.shape) != tuple(x.shape[:2]):
+            raise RuntimeError(f"simgraph_correct: points must be ({b}, L, 3) and ref ({b}, L), got {tuple(points.shape)}, {tuple(ref.shape)}")
+        l = int(x.shape[1])
+    if b < 1 or n + l < 1:
+        raise RuntimeError("simgraph_correct: no pose and no point to correct")
+    if n:
+        r_out, t_out = torch.empty_like(rn), torch.empty_like(tn)
+    if l:
+        x_out = torch.empty_like(x)
+    on = lambda a, dt, what: N.opt(a if (a is None or a.numel()) else None, dt, what)
+    N.call("mi_simgraph_correct", on(ro, F32, "r_old"), on(to, F32, "t_old"), on(so, F32, "s"), on(rn, F32, "r"), on(tn, F32, "t"),
+           on(x, F32, "points"), on(rf, I32, "ref"), b, n, l, N.opt(r_out, F32, "r_out"), N.opt(t_out, F32, "t_out"),
+           N.opt(x_out, F32, "points_out"), N.stream_ptr())
+    return r_out, t_out, x_out
+
+
 # ---- K28 landmark tracks (include/mi355x_match.h, "landmark tracks") ---------------------------------------------------------
 
 TRACKS_MAX_FRAMES = N.MI_TRACKS_MAX_FRAMES

@@ -11,7 +11,8 @@ from .pose_graph import PoseGraphOptimizer
 from .relative_pose import RelativePoseEstimator, triangulate_points
 from .rgbd_pose import RgbdPoseEstimator
 from .similarity import SimilarityEstimator
+from .similarity_graph import SimilarityGraphOptimizer
 from .tsdf_volume import TsdfVolume
 
 __all__ = ["AbsolutePoseEstimator", "BundleAdjuster", "DenseRgbdRefiner", "DirectRgbdRefiner", "DirectTsdfVolume", "EssentialMatrixEstimator", "HomographyEstimator",
-           "LandmarkTracks", "LocalMapTracker", "PlanarPoseEstimator", "PoseGraphOptimizer", "RelativePoseEstimator", "RgbdPoseEstimator", "SimilarityEstimator", "TsdfVolume", "TwoViewPoseEstimator", "triangulate_points"]
+           "LandmarkTracks", "LocalMapTracker", "PlanarPoseEstimator", "PoseGraphOptimizer", "RelativePoseEstimator", "RgbdPoseEstimator", "SimilarityEstimator", "SimilarityGraphOptimizer", "TsdfVolume", "TwoViewPoseEstimator", "triangulate_points"]

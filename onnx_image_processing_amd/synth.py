@@ -615,6 +615,59 @@ def synth_pose_graph(seed: int, nodes: int, loops: int, sigma_rot: float, sigma_
             fixed, protected, R, t, false_edge)
 
 
+def synth_sim3_graph(seed: int, nodes: int, loops: int, sigma_rot: float, sigma_trans: float, sigma_scale: float, drift: float,
+                     false_loops: int = 0):
+    """A similarity pose graph for the Sim(3) pose-graph kernels (K31): (s0, R0, t0, edge_index, s_meas, R_meas, t_meas,
+    information, fixed, protected, s, R, t, false_edge) -- a monocular trajectory whose unit drifts, and the loops that show it.
+
+    The truth is synth_pose_graph(seed, nodes, loops, ...)'s ring with its edges (odometry, loops, false loops), metric:
+    s = ones (nodes,), R, t float64 with X_c = s R X + t.  Edges (i, j) carry the similarity X_j = s_z R_z X_i + t_z, the true
+    one perturbed in the residual's coordinates: s_z = exp(-sigma) s_p, R_z = Exp(w)^T R_p, t_z = exp(-sigma) Exp(w)^T (t_p - tau)
+    with w ~ N(0, sigma_rot^2), tau ~ N(0, sigma_trans^2) per axis and sigma ~ N(0, sigma_scale^2), so that the edge's residual
+    at the truth is exactly (w, tau, sigma).  ODOMETRY edges have sigma = 0: their scale is exactly 1, as relative poses taken
+    from a metric trajectory have.  A false loop's (w, tau, sigma) is N(0, 0.5^2) rad, N(0, 1) m and N(0, 0.5^2) instead.
+    information (E, 7, 7) = diag(1 / sigma_rot^2 x 3, 1 / sigma_trans^2 x 3, 1 / sigma_scale^2) (a sigma of 0: 1).  The start
+    (float32): node 0 at the truth, then the odometry chained with a scale drift of exp(drift) per edge:
+    s0[k + 1] = exp(drift) s0[k], R0[k + 1] = R_z R0[k], t0[k + 1] = exp(drift) R_z t0[k] + t_z -- the unit of node k is
+    exp(k drift) world units, which no odometry edge agrees with and only the loops can measure.  fixed: node 0; protected: the
+    odometry edges.  edge_index int32, measurements and information float32.  float64 arithmetic on hashed integers: the same
+    graph everywhere."""
+    if not (sigma_scale >= 0 and np.isfinite(drift)):
+        raise ValueError(f"synth_sim3_graph: sigma_scale >= 0 and a finite drift, got {sigma_scale} and {drift}")
+    _, _, ei, _, _, _, fixed, protected, R, t, false_edge = synth_pose_graph(seed, nodes, loops, 0.0, 0.0, false_loops)
+    E = len(ei)
+
+    def uni(shape, salt):
+        idx = np.arange(int(np.prod(shape)), dtype=np.uint64)
+        return (((_hash3(seed, idx, np.uint64(salt) + 0 * idx, 51) >> np.uint64(11)).astype(np.float64) + 0.5) / float(1 << 53)).reshape(shape)
+
+    def normal(shape, salt):
+        return np.sqrt(-2.0 * np.log(uni(shape, salt))) * np.cos(2.0 * np.pi * uni(shape, salt + 1))
+
+    w, tau, sig = sigma_rot * normal((E, 3), 0), sigma_trans * normal((E, 3), 2), sigma_scale * normal((E,), 4)
+    sig[protected] = 0.0
+    w[false_edge] = 0.5 * normal((E, 3), 6)[false_edge]
+    tau[false_edge] = 1.0 * normal((E, 3), 8)[false_edge]
+    sig[false_edge] = 0.5 * normal((E,), 10)[false_edge]
+    zs, zr, zt = np.zeros(E), np.zeros((E, 3, 3)), np.zeros((E, 3))
+    for e, (i, j) in enumerate(ei):
+        Rp = R[j] @ R[i].T
+        tp = t[j] - Rp @ t[i]
+        Ew = _rodrigues64(w[e])
+        zs[e] = np.exp(-sig[e])
+        zr[e], zt[e] = Ew.T @ Rp, zs[e] * (Ew.T @ (tp - tau[e]))
+    inv = lambda v: 1.0 / v ** 2 if v > 0 else 1.0
+    information = np.tile(np.diag([inv(sigma_rot)] * 3 + [inv(sigma_trans)] * 3 + [inv(sigma_scale)]), (E, 1, 1))
+    s0, R0, t0 = np.ones(nodes), R.copy(), t.copy()
+    gain = np.exp(drift)
+    for k in range(nodes - 1):
+        s0[k + 1] = gain * s0[k]
+        R0[k + 1], t0[k + 1] = zr[k] @ R0[k], gain * (zr[k] @ t0[k]) + zt[k]
+    f32 = np.float32
+    return (s0.astype(f32), R0.astype(f32), t0.astype(f32), ei, zs.astype(f32), zr.astype(f32), zt.astype(f32), information.astype(f32),
+            fixed, protected, np.ones(nodes), R, t, false_edge)
+
+
 def synth_track_window(seed: int, frames: int, keypoints: int, landmarks: int, pair_span: int = 2, miss: float = 0.1,
                        outlier_fraction: float = 0.1, noise_px: float = 0.5, pose_noise: float = 0.002):
     """A window for the landmark-track kernels (K28): (keypoints, kp_id, pair_frames, match_ij, match_valid, R0, t0, R, t, X).

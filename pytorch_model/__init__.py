@@ -18,6 +18,7 @@ MI355X implementation (the very same module objects, not copies):
     from pytorch_model.geometry import LandmarkTracks                   (no counterpart in the reference: matches -> BA windows)
     from pytorch_model.geometry import LocalMapTracker                  (no counterpart in the reference: landmarks -> a new frame)
     from pytorch_model.geometry import SimilarityEstimator              (no counterpart in the reference: Sim(3) between two maps)
+    from pytorch_model.geometry import SimilarityGraphOptimizer         (no counterpart in the reference: 7-DoF loop closing)
 
 The one sub-package outside the mirrored set (`vo`, host-side numpy / OpenCV and camera drivers) does not
 exist and raises ImportError.
