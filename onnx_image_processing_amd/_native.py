@@ -116,10 +116,15 @@ RESTYPES.update(_sim3_restypes)
 # load_simgraph(), SIMGRAPH_CONSTANTS["MI_SIMGRAPH_MAX_NODES"], ...
 SIMGRAPH_SIGNATURES, _simgraph_restypes, _, SIMGRAPH_CONSTANTS = _read("mi355x_match_simgraph.h")
 RESTYPES.update(_simgraph_restypes)
+# include/mi355x_match_flow.h: the feature-tracking section (K32), laid out as K30's: lib/libmi355x_match_flow.so, load_flow(),
+# FLOW_CONSTANTS["MI_FLOW_MAX_RADIUS"], ...
+FLOW_SIGNATURES, _flow_restypes, _, FLOW_CONSTANTS = _read("mi355x_match_flow.h")
+RESTYPES.update(_flow_restypes)
 
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_debug.so")
 SIM3_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_sim3.so")
 SIMGRAPH_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_simgraph.so")
+FLOW_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_flow.so")
 
 _lib = None            # the library every call() goes through: the product, unless inside debug_library()
 _product = None
@@ -173,8 +178,21 @@ def load_simgraph() -> ctypes.CDLL:
     return _simgraph
 
 
+_flow = None
+
+
+def load_flow() -> ctypes.CDLL:
+    """lib/libmi355x_match_flow.so, the entries of include/mi355x_match_flow.h, loaded once."""
+    global _flow
+    if _flow is None:
+        _flow = _open(FLOW_LIB_PATH, FLOW_SIGNATURES)
+    return _flow
+
+
 def library_of(name: str) -> ctypes.CDLL:
     """The library that exports the entry `name`."""
+    if name in FLOW_SIGNATURES:
+        return load_flow()
     if name in SIM3_SIGNATURES:
         return load_sim3()
     return load_simgraph() if name in SIMGRAPH_SIGNATURES else load()

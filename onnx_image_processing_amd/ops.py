@@ -2606,3 +2606,120 @@ def ingest_frames(frames: torch.Tensor, height: int, width: int, *, channel_orde
     N.call("mi_ingest_frames", frames.data_ptr(), b, hs, ws, c, frames.stride(1), frames.stride(0),
            _CHANNEL_ORDERS[channel_order], out.data_ptr(), int(out_dtype == F32), height, width, N.stream_ptr())
     return out
+
+
+# ---- K32 feature tracking (include/mi355x_match_flow.h) -----------------------------------------------------------------------
+
+FLOW_MAX_LEVELS, FLOW_MAX_RADIUS, FLOW_MAX_K = (N.FLOW_CONSTANTS[k] for k in ("MI_FLOW_MAX_LEVELS", "MI_FLOW_MAX_RADIUS", "MI_FLOW_MAX_K"))
+FLOW_MAX_ITERATIONS, FLOW_MAX_CELLS = N.FLOW_CONSTANTS["MI_FLOW_MAX_ITERATIONS"], N.FLOW_CONSTANTS["MI_FLOW_MAX_CELLS"]
+FLOW_OK, FLOW_PADDING, FLOW_FLAT, FLOW_LEFT = (N.FLOW_CONSTANTS[k] for k in ("MI_FLOW_OK", "MI_FLOW_PADDING", "MI_FLOW_FLAT", "MI_FLOW_LEFT"))
+
+
+class FlowPyramid:
+    """The pyramid block of `mi_flow_pyramid`: `data` (the library's layout, float32 behind an int64 workspace tensor) and
+    the request it was built for.  level(l) is a (B, h_l, w_l) float32 view of it."""
+
+    def __init__(self, data: torch.Tensor, batch: int, h: int, w: int, levels: int) -> None:
+        self.data, self.batch, self.h, self.w, self.levels = data, batch, h, w, levels
+
+    def level(self, l: int) -> torch.Tensor:
+        if not 0 <= l < self.levels:
+            raise IndexError(f"level {l} of a {self.levels}-level pyramid")
+        off, h, w = 0, self.h, self.w
+        for _ in range(l):
+            off = (off + self.batch * h * w * 4 + 255) // 256 * 256
+            h, w = (h + 1) // 2, (w + 1) // 2
+        return self.data.view(F32)[off // 4: off // 4 + self.batch * h * w].view(self.batch, h, w)
+
+
+def flow_pyramid(frames: torch.Tensor, levels: int) -> FlowPyramid:
+    """`mi_flow_pyramid`: gray frames (B, H, W) or (B, 1, H, W), uint8 or float32 (the outputs of ingest_frames), to the
+    `levels`-level cv2.pyrDown pyramid the tracker reads."""
+    if not frames.is_cuda:
+        raise RuntimeError(f"flow_pyramid: frames must live on the GPU (got device {frames.device}); this package has no CPU path")
+    if frames.dtype not in (U8, F32):
+        raise RuntimeError(f"flow_pyramid: frames must be uint8 or float32, got {frames.dtype}")
+    if frames.dim() == 4 and frames.shape[1] == 1:
+        frames = frames[:, 0]
+    if frames.dim() != 3 or frames.numel() == 0:
+        raise RuntimeError(f"flow_pyramid: frames must be (B, H, W) or (B, 1, H, W), got {tuple(frames.shape)}")
+    src = frames.contiguous()
+    b, h, w = (int(v) for v in src.shape)
+    data, nbytes = _workspace("mi_flow_pyramid_bytes", b, h, w, int(levels), device=src.device,
+                              refusal=f"flow_pyramid: unsupported request (batch {b}, {h} x {w}, {levels} levels: 1 .. {FLOW_MAX_LEVELS} "
+                                      "levels, the top level at least 5 x 5)")
+    N.call("mi_flow_pyramid", src.data_ptr(), int(src.dtype == U8), b, h, w, int(levels), data.data_ptr(), nbytes, N.stream_ptr())
+    return FlowPyramid(data, b, h, w, int(levels))
+
+
+def _flow_keypoints(t: torch.Tensor, what: str, batch: int | None = None):
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} must live on the GPU (got device {t.device}); this package has no CPU path")
+    q = t.float().contiguous()
+    if q.dim() != 3 or q.shape[2] != 2 or (batch is not None and q.shape[0] != batch) or q.shape[1] < 1:
+        raise RuntimeError(f"{what} must be (B, K, 2) (y, x) pixel coordinates, got {tuple(t.shape)}")
+    return q
+
+
+def flow_track(pyr1: FlowPyramid, pyr2: FlowPyramid, keypoints1: torch.Tensor, guess: torch.Tensor | None = None, radius: int = 7,
+               max_iterations: int = 30, epsilon: float = 0.01, min_eigen: float = 1e-3):
+    """`mi_flow_track`: keypoints1 (B, K, 2) (y, x) of frame 1 followed into frame 2 by pyramidal Lucas-Kanade ->
+    (keypoints2 (B, K, 2), status (B, K) bool, code (B, K) uint8 FLOW_OK / FLOW_PADDING / FLOW_FLAT / FLOW_LEFT, residual
+    (B, K) mean |e| at level 0, iterations (B, K) int32).  guess (B, K, 2): a predicted displacement (dy, dx) or None."""
+    if (pyr1.batch, pyr1.h, pyr1.w, pyr1.levels) != (pyr2.batch, pyr2.h, pyr2.w, pyr2.levels):
+        raise RuntimeError("flow_track: the two pyramids differ in batch, size or levels")
+    kp = _flow_keypoints(keypoints1, "flow_track: keypoints1", pyr1.batch)
+    g = None if guess is None else _flow_keypoints(guess, "flow_track: guess", pyr1.batch)
+    if g is not None and g.shape != kp.shape:
+        raise RuntimeError(f"flow_track: guess must be {tuple(kp.shape)}, got {tuple(g.shape)}")
+    b, k, dev = pyr1.batch, int(kp.shape[1]), kp.device
+    kp2 = torch.empty((b, k, 2), dtype=F32, device=dev)
+    status, code = torch.empty((b, k), dtype=U8, device=dev), torch.empty((b, k), dtype=U8, device=dev)
+    residual = torch.empty((b, k), dtype=F32, device=dev)
+    iterations = torch.empty((b, k), dtype=I32, device=dev)
+    N.call("mi_flow_track", pyr1.data.data_ptr(), pyr2.data.data_ptr(), kp.data_ptr(), N.opt(g, F32, "guess"), b, pyr1.h, pyr1.w,
+           pyr1.levels, k, int(radius), int(max_iterations), float(epsilon), float(min_eigen), kp2.data_ptr(), status.data_ptr(),
+           code.data_ptr(), residual.data_ptr(), iterations.data_ptr(), N.stream_ptr())
+    return kp2, status.view(torch.bool), code, residual, iterations
+
+
+def flow_check(keypoints1: torch.Tensor, keypoints_back: torch.Tensor, status_fwd: torch.Tensor, status_bwd: torch.Tensor,
+               max_distance: float):
+    """`mi_flow_check`: the forward-backward test -> (status (B, K) bool, fb_distance (B, K) float32, +inf where either
+    track was lost)."""
+    kp = _flow_keypoints(keypoints1, "flow_check: keypoints1")
+    back = _flow_keypoints(keypoints_back, "flow_check: keypoints_back", int(kp.shape[0]))
+    sf, sb = _validity_bytes(status_fwd), _validity_bytes(status_bwd)
+    b, k = int(kp.shape[0]), int(kp.shape[1])
+    if back.shape != kp.shape or tuple(sf.shape) != (b, k) or tuple(sb.shape) != (b, k):
+        raise RuntimeError(f"flow_check: keypoints must both be ({b}, {k}, 2) and the statuses ({b}, {k})")
+    status = torch.empty((b, k), dtype=U8, device=kp.device)
+    fb = torch.empty((b, k), dtype=F32, device=kp.device)
+    N.call("mi_flow_check", kp.data_ptr(), back.data_ptr(), N.dev(sf, U8, "status_fwd"), N.dev(sb, U8, "status_bwd"), b, k,
+           float(max_distance), status.data_ptr(), fb.data_ptr(), N.stream_ptr())
+    return status.view(torch.bool), fb
+
+
+def flow_replenish(keypoints: torch.Tensor, status: torch.Tensor, candidates: torch.Tensor, cand_count: torch.Tensor | None, h: int,
+                   w: int, cell: int = 16):
+    """`mi_flow_replenish`: lost slots (status 0) of keypoints (B, K, 2) refilled from score-descending candidates
+    (B, C, 2), the first cand_count[b] (B,) int32 of them real (None: all), one per cell of cell x cell pixels that holds no
+    live keypoint -> (keypoints_out (B, K, 2), is_new (B, K) bool, counts (B, 3) int32: live, accepted, filled)."""
+    kp = _flow_keypoints(keypoints, "flow_replenish: keypoints")
+    b, k = int(kp.shape[0]), int(kp.shape[1])
+    cand = _flow_keypoints(candidates, "flow_replenish: candidates", b)
+    st = _validity_bytes(status)
+    if tuple(st.shape) != (b, k):
+        raise RuntimeError(f"flow_replenish: status must be ({b}, {k}), got {tuple(st.shape)}")
+    n_cand = int(cand.shape[1])
+    if cand_count is None:
+        cand_count = torch.full((b,), n_cand, dtype=I32, device=kp.device)
+    cc = cand_count.to(I32).contiguous()
+    if tuple(cc.shape) != (b,):
+        raise RuntimeError(f"flow_replenish: cand_count must be ({b},), got {tuple(cc.shape)}")
+    out = torch.empty((b, k, 2), dtype=F32, device=kp.device)
+    is_new = torch.empty((b, k), dtype=U8, device=kp.device)
+    counts = torch.empty((b, 3), dtype=I32, device=kp.device)
+    N.call("mi_flow_replenish", kp.data_ptr(), N.dev(st, U8, "status"), cand.data_ptr(), N.dev(cc, I32, "cand_count"), b, k, n_cand,
+           int(h), int(w), int(cell), out.data_ptr(), is_new.data_ptr(), counts.data_ptr(), N.stream_ptr())
+    return out, is_new.view(torch.bool), counts

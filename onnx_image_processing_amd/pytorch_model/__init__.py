@@ -6,5 +6,6 @@ the arithmetic runs in the hand-written gfx950 kernels behind include/mi355x_mat
 Inputs must be GPU tensors (there is no CPU fallback).  `geometry.relative_pose` and `ingest` have no module in the
 reference: they are its hosts' OpenCV steps (pose from matches; colour frame to gray model frame) on the device.
 `retrieval` (KeyframeDatabase: which stored keyframe is this frame?) has none either: loop closure detection and
-relocalisation are open boxes of the reference's roadmap.
+relocalisation are open boxes of the reference's roadmap.  `tracking` (FeatureTracker: pyramidal Lucas-Kanade between two
+frames) has none: the reference's hosts call OpenCV for it.
 """

@@ -809,3 +809,42 @@ def synth_sim3_maps(seed: int, n: int, outliers: float, ray_noise: float, scale:
     x1 = x1 * np.maximum(1.0 + ray_noise * normal(idx, 8), 0.1)[:, None]
     x2 = x2 * np.maximum(1.0 + ray_noise * normal(idx, 10), 0.1)[:, None]
     return x1.astype(np.float32), x2.astype(np.float32), float(scale), R, t, inlier
+
+
+def synth_flow_pair(seed: int, height: int, width: int, angle_deg: float = 0.0, scale: float = 1.0, shift=(0.0, 0.0),
+                    lam=(6.0, 64.0), terms: int = 24, quantise: bool = False):
+    """Two frames that a tracker can follow (the hash images above are per-pixel noise and cannot be): exact samples of ONE
+    analytic function I(x, y) = 128 + sum_m a_m sin(2 pi (fx_m x + fy_m y) + phi_m) with `terms` waves of wavelengths
+    log-uniform in `lam`, directions uniform, a_m proportional to sqrt(lambda_m) and scaled to sum to 110 (so I stays inside
+    [18, 238]).  Frame 1 is I at the pixel centres q = (x, y); frame 2 is I(A^-1 (q - d)) with A = scale * rotation by
+    angle_deg about the frame centre c (A p = scale R (p - c) + c) and d = shift = (dx, dy), so that the point p of frame 1
+    is seen at A p + d in frame 2 with no interpolation involved.  Returns (frame1, frame2, A (2, 3) float64 acting on
+    (x, y, 1), d (2,) float64); the frames are (height, width) float32, or rounded to uint8 with `quantise`."""
+    if height < 1 or width < 1 or terms < 1 or not 0 < lam[0] <= lam[1] or not scale > 0:
+        raise ValueError("synth_flow_pair: height, width, terms >= 1, 0 < lam[0] <= lam[1], scale > 0")
+    rng = np.random.default_rng(seed)
+    wavelength = np.exp(rng.uniform(np.log(lam[0]), np.log(lam[1]), terms))
+    theta = rng.uniform(0.0, 2.0 * np.pi, terms)
+    phi = rng.uniform(0.0, 2.0 * np.pi, terms)
+    fx, fy = np.cos(theta) / wavelength, np.sin(theta) / wavelength
+    amp = np.sqrt(wavelength)
+    amp *= 110.0 / amp.sum()
+
+    def image(x, y):
+        out = np.full(x.shape, 128.0)
+        for m in range(terms):
+            out += amp[m] * np.sin(2.0 * np.pi * (fx[m] * x + fy[m] * y) + phi[m])
+        return out
+
+    ang = np.deg2rad(angle_deg)
+    lin = scale * np.array([[np.cos(ang), -np.sin(ang)], [np.sin(ang), np.cos(ang)]])
+    centre = np.array([(width - 1) / 2.0, (height - 1) / 2.0])
+    A = np.concatenate([lin, (centre - lin @ centre)[:, None]], axis=1)
+    d = np.array([float(shift[0]), float(shift[1])])
+    y, x = np.mgrid[0:height, 0:width].astype(np.float64)
+    inv = np.linalg.inv(lin)
+    qx, qy = x - d[0] - A[0, 2], y - d[1] - A[1, 2]
+    f1, f2 = image(x, y), image(inv[0, 0] * qx + inv[0, 1] * qy, inv[1, 0] * qx + inv[1, 1] * qy)
+    if quantise:
+        return np.rint(f1).astype(np.uint8), np.rint(f2).astype(np.uint8), A, d
+    return f1.astype(np.float32), f2.astype(np.float32), A, d
