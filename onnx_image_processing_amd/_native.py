@@ -120,11 +120,16 @@ RESTYPES.update(_simgraph_restypes)
 # FLOW_CONSTANTS["MI_FLOW_MAX_RADIUS"], ...
 FLOW_SIGNATURES, _flow_restypes, _, FLOW_CONSTANTS = _read("mi355x_match_flow.h")
 RESTYPES.update(_flow_restypes)
+# include/mi355x_match_stereo.h: the stereo-depth section (K33), laid out as K30's: lib/libmi355x_match_stereo.so, load_stereo(),
+# STEREO_CONSTANTS["MI_STEREO_MAX_DISPARITIES"], ...
+STEREO_SIGNATURES, _stereo_restypes, _, STEREO_CONSTANTS = _read("mi355x_match_stereo.h")
+RESTYPES.update(_stereo_restypes)
 
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_debug.so")
 SIM3_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_sim3.so")
 SIMGRAPH_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_simgraph.so")
 FLOW_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_flow.so")
+STEREO_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_stereo.so")
 
 _lib = None            # the library every call() goes through: the product, unless inside debug_library()
 _product = None
@@ -189,8 +194,21 @@ def load_flow() -> ctypes.CDLL:
     return _flow
 
 
+_stereo = None
+
+
+def load_stereo() -> ctypes.CDLL:
+    """lib/libmi355x_match_stereo.so, the entries of include/mi355x_match_stereo.h, loaded once."""
+    global _stereo
+    if _stereo is None:
+        _stereo = _open(STEREO_LIB_PATH, STEREO_SIGNATURES)
+    return _stereo
+
+
 def library_of(name: str) -> ctypes.CDLL:
     """The library that exports the entry `name`."""
+    if name in STEREO_SIGNATURES:
+        return load_stereo()
     if name in FLOW_SIGNATURES:
         return load_flow()
     if name in SIM3_SIGNATURES:

@@ -2723,3 +2723,78 @@ def flow_replenish(keypoints: torch.Tensor, status: torch.Tensor, candidates: to
     N.call("mi_flow_replenish", kp.data_ptr(), N.dev(st, U8, "status"), cand.data_ptr(), N.dev(cc, I32, "cand_count"), b, k, n_cand,
            int(h), int(w), int(cell), out.data_ptr(), is_new.data_ptr(), counts.data_ptr(), N.stream_ptr())
     return out, is_new.view(torch.bool), counts
+
+
+# ---- K33 stereo depth (include/mi355x_match_stereo.h) -------------------------------------------------------------------------
+
+STEREO_OK, STEREO_NOT_UNIQUE, STEREO_LR = (N.STEREO_CONSTANTS[k] for k in ("MI_STEREO_OK", "MI_STEREO_NOT_UNIQUE", "MI_STEREO_LR"))
+STEREO_DISPARITIES = (64, 128, 256)
+I16, U16, I64 = torch.int16, torch.uint16, torch.int64
+
+
+def _stereo_frames(t: torch.Tensor, what: str, dtypes, shape=None):
+    """(B, H, W) or (B, 1, H, W) on the GPU, of one of `dtypes`, contiguous; `shape`: the (B, H, W) it must have"""
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} must live on the GPU (got device {t.device}); this package has no CPU path")
+    if t.dtype not in dtypes:
+        raise RuntimeError(f"{what} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+    if t.dim() == 4 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != 3 or t.numel() == 0 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise RuntimeError(f"{what} must be {'(B, H, W) or (B, 1, H, W)' if shape is None else tuple(shape)}, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def stereo_census(gray: torch.Tensor) -> torch.Tensor:
+    """`mi_stereo_census`: gray frames (B, H, W) or (B, 1, H, W), uint8 or float32 (the outputs of ingest_frames) -> the 9 x 7
+    census words (B, H, W), 62 bits each in an int64 tensor (torch has no arithmetic on uint64; the bits are the library's)."""
+    g = _stereo_frames(gray, "stereo_census: gray", (U8, F32))
+    b, h, w = (int(v) for v in g.shape)
+    census = torch.empty((b, h, w), dtype=I64, device=g.device)
+    N.call("mi_stereo_census", g.data_ptr(), int(g.dtype == U8), b, h, w, census.data_ptr(), N.stream_ptr())
+    return census
+
+
+def stereo_aggregate(census_left: torch.Tensor, census_right: torch.Tensor, max_disparity: int = 128, paths: int = 8, p1: int = 10,
+                     p2: int = 120) -> torch.Tensor:
+    """`mi_stereo_aggregate`: the census words of a rectified pair -> the semi-global sums S (B, H, W, max_disparity) uint16
+    over `paths` (4 or 8) directions with the penalties 0 <= p1 <= p2 <= 255.  max_disparity is 64, 128 or 256."""
+    cl = _stereo_frames(census_left, "stereo_aggregate: census_left", (I64,))
+    cr = _stereo_frames(census_right, "stereo_aggregate: census_right", (I64,), cl.shape)
+    b, h, w = (int(v) for v in cl.shape)
+    d = int(max_disparity)
+    volume = torch.empty((b, h, w, d if d > 0 else 1), dtype=U16, device=cl.device)
+    work, wbytes = _workspace("mi_stereo_workspace_bytes", b, h, w, d, int(paths), device=cl.device)
+    N.call("mi_stereo_aggregate", cl.data_ptr(), cr.data_ptr(), b, h, w, d, int(paths), int(p1), int(p2), volume.data_ptr(),
+           work.data_ptr() if wbytes else None, wbytes, N.stream_ptr())
+    return volume
+
+
+def stereo_select(volume: torch.Tensor, uniqueness: int = 10, lr_max_diff: int = 1, want_right: bool = True):
+    """`mi_stereo_select`: S (B, H, W, D) uint16 -> (disparity (B, H, W) float32, -1 on a rejected pixel; disparity_right
+    (B, H, W) int16, or None with want_right=False, which needs lr_max_diff < 0; code (B, H, W) uint8: STEREO_OK,
+    STEREO_NOT_UNIQUE, STEREO_LR)."""
+    if not want_right and lr_max_diff >= 0:
+        raise ValueError("stereo_select: the left-right test (lr_max_diff >= 0) needs the right view's disparities")
+    if not volume.is_cuda:
+        raise RuntimeError(f"stereo_select: volume must live on the GPU (got device {volume.device}); this package has no CPU path")
+    if volume.dtype != U16 or volume.dim() != 4 or volume.numel() == 0:
+        raise RuntimeError(f"stereo_select: volume must be (B, H, W, D) uint16, got {tuple(volume.shape)} {volume.dtype}")
+    v = volume.contiguous()
+    b, h, w, d = (int(x) for x in v.shape)
+    disparity = torch.empty((b, h, w), dtype=F32, device=v.device)
+    right = torch.empty((b, h, w), dtype=I16, device=v.device) if want_right else None
+    code = torch.empty((b, h, w), dtype=U8, device=v.device)
+    N.call("mi_stereo_select", v.data_ptr(), b, h, w, d, int(uniqueness), int(lr_max_diff), disparity.data_ptr(),
+           None if right is None else right.data_ptr(), code.data_ptr(), N.stream_ptr())
+    return disparity, right, code
+
+
+def stereo_depth(disparity: torch.Tensor, fb: float, min_disparity: float = 0.5) -> torch.Tensor:
+    """`mi_stereo_depth`: disparity (B, H, W) or (B, 1, H, W) float32 -> depth of the same shape, fb / disparity where
+    disparity >= min_disparity and 0 elsewhere; fb = fx * baseline in the unit the depth is wanted in."""
+    d = _stereo_frames(disparity, "stereo_depth: disparity", (F32,))
+    b, h, w = (int(v) for v in d.shape)
+    depth = torch.empty((b, h, w), dtype=F32, device=d.device)
+    N.call("mi_stereo_depth", d.data_ptr(), b, h, w, float(fb), float(min_disparity), depth.data_ptr(), N.stream_ptr())
+    return depth.view(disparity.shape)

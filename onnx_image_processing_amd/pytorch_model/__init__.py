@@ -7,5 +7,6 @@ Inputs must be GPU tensors (there is no CPU fallback).  `geometry.relative_pose`
 reference: they are its hosts' OpenCV steps (pose from matches; colour frame to gray model frame) on the device.
 `retrieval` (KeyframeDatabase: which stored keyframe is this frame?) has none either: loop closure detection and
 relocalisation are open boxes of the reference's roadmap.  `tracking` (FeatureTracker: pyramidal Lucas-Kanade between two
-frames) has none: the reference's hosts call OpenCV for it.
+frames) has none: the reference's hosts call OpenCV for it.  `stereo` (StereoMatcher: a rectified pair to disparity and depth by
+census and semi-global matching) has none either: the reference's OAK-D back end uses the camera's own stereo engine.
 """

@@ -848,3 +848,41 @@ def synth_flow_pair(seed: int, height: int, width: int, angle_deg: float = 0.0, 
     if quantise:
         return np.rint(f1).astype(np.uint8), np.rint(f2).astype(np.uint8), A, d
     return f1.astype(np.float32), f2.astype(np.float32), A, d
+
+
+def synth_stereo_pair(seed: int, height: int, width: int, d_background: float = 4.0, d_box: float = 20.0, d_ramp=(6.0, 16.0),
+                      noise: float = 2.0, quantise: bool = False):
+    """A rectified stereo pair with a known disparity: the left view is per-pixel random texture, and its true disparity is a
+    background plane at `d_background`, a foreground box at `d_box` (rows height/5 .. height/2, columns width/3 .. 2 width/3)
+    and, in the lowest third of the rows, a ramp from d_ramp[0] at the left border to d_ramp[1] at the right one.  The right
+    view is the left one splatted to x_right = rint(x - d) with a depth test (the larger disparity wins a contested pixel);
+    pixels that nothing lands on are filled with fresh texture, and uniform noise of +-`noise` gray levels is added to the
+    right view.  Returns (left, right, disparity (height, width) float32, visible (height, width) bool: the left pixel
+    lands inside the right frame and wins its pixel there); the views are float32 clipped to [0, 255], or rounded to uint8
+    with `quantise`.  Deterministic in `seed`."""
+    if height < 1 or width < 1 or min(d_background, d_box, d_ramp[0], d_ramp[1]) < 0 or noise < 0:
+        raise ValueError("synth_stereo_pair: height, width >= 1, disparities and noise >= 0")
+    rng = np.random.default_rng(seed)
+    left = rng.integers(0, 256, (height, width)).astype(np.float64)
+    y, x = np.mgrid[0:height, 0:width]
+    disp = np.full((height, width), float(d_background))
+    ramp = y >= height - height // 3
+    disp[ramp] = (d_ramp[0] + (d_ramp[1] - d_ramp[0]) * x / max(width - 1, 1))[ramp]
+    box = (y >= height // 5) & (y < height // 2) & (x >= width // 3) & (x < 2 * width // 3)
+    disp[box] = float(d_box)
+    xr = np.rint(x - disp).astype(np.int64)
+    inside = (xr >= 0) & (xr < width)
+    order = np.argsort(disp[inside], kind="stable")                          # ascending: the nearest surface is written last
+    ys, xs, xrs = y[inside][order], x[inside][order], xr[inside][order]
+    right = np.full((height, width), np.nan)
+    owner = np.full((height, width), -1, np.int64)
+    for i in range(len(ys)):                                                 # in order: a repeated target keeps the last writer
+        right[ys[i], xrs[i]] = left[ys[i], xs[i]]
+        owner[ys[i], xrs[i]] = ys[i] * width + xs[i]
+    visible = inside & (owner[y, np.clip(xr, 0, width - 1)] == y * width + x)
+    holes = np.isnan(right)
+    right[holes] = rng.integers(0, 256, int(holes.sum())).astype(np.float64)
+    right = np.clip(right + rng.uniform(-noise, noise, (height, width)), 0.0, 255.0)
+    if quantise:
+        return left.astype(np.uint8), np.rint(right).astype(np.uint8), disp.astype(np.float32), visible
+    return left.astype(np.float32), right.astype(np.float32), disp.astype(np.float32), visible

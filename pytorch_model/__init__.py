@@ -20,6 +20,7 @@ MI355X implementation (the very same module objects, not copies):
     from pytorch_model.geometry import SimilarityEstimator              (no counterpart in the reference: Sim(3) between two maps)
     from pytorch_model.geometry import SimilarityGraphOptimizer         (no counterpart in the reference: 7-DoF loop closing)
     from pytorch_model.tracking import FeatureTracker                   (no counterpart in the reference: KLT tracking, its hosts' cv2 step)
+    from pytorch_model.stereo import StereoMatcher                      (no counterpart in the reference: a stereo rig's depth, cv2.StereoSGBM)
 
 The one sub-package outside the mirrored set (`vo`, host-side numpy / OpenCV and camera drivers) does not
 exist and raises ImportError.
