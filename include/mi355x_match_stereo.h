@@ -25,7 +25,8 @@ extern "C" {
  * batch < 1, h < 1, w < 1: MI_E_SHAPE.  batch h w >= 2^26 (MI_STEREO_MAX_PIXELS; the volume limit below at D = 64): MI_E_PARAM.
  *
  * The inputs are RECTIFIED: a scene point lies on the same row of both views, at x_right = x_left - d with d >= 0.
- * Undistortion and rectification are not part of this section, and neither are speckle or median post-filters.
+ * Undistortion and rectification are the K34 section's (include/mi355x_match_rectify.h: mi_rectify_stereo_rig, mi_rectify_map,
+ * mi_rectify_remap); speckle and median post-filters are not part of the library.
  *
  * Census.  gray is (batch, h, w), uint8 or float32 (the two outputs of mi_ingest_frames); census is (batch, h, w) uint64.
  *   The window is 9 wide and 7 high.  Bit k of pixel (y, x) belongs to the k-th offset (dy, dx), dy = -3 .. 3 outer,

@@ -124,12 +124,17 @@ RESTYPES.update(_flow_restypes)
 # STEREO_CONSTANTS["MI_STEREO_MAX_DISPARITIES"], ...
 STEREO_SIGNATURES, _stereo_restypes, _, STEREO_CONSTANTS = _read("mi355x_match_stereo.h")
 RESTYPES.update(_stereo_restypes)
+# include/mi355x_match_rectify.h: the camera-rectification section (K34), laid out as K30's: lib/libmi355x_match_rectify.so,
+# load_rectify(), RECTIFY_CONSTANTS["MI_RECTIFY_OUTSIDE"], ...
+RECTIFY_SIGNATURES, _rectify_restypes, _, RECTIFY_CONSTANTS = _read("mi355x_match_rectify.h")
+RESTYPES.update(_rectify_restypes)
 
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_debug.so")
 SIM3_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_sim3.so")
 SIMGRAPH_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_simgraph.so")
 FLOW_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_flow.so")
 STEREO_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_stereo.so")
+RECTIFY_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_rectify.so")
 
 _lib = None            # the library every call() goes through: the product, unless inside debug_library()
 _product = None
@@ -205,8 +210,21 @@ def load_stereo() -> ctypes.CDLL:
     return _stereo
 
 
+_rectify = None
+
+
+def load_rectify() -> ctypes.CDLL:
+    """lib/libmi355x_match_rectify.so, the entries of include/mi355x_match_rectify.h, loaded once."""
+    global _rectify
+    if _rectify is None:
+        _rectify = _open(RECTIFY_LIB_PATH, RECTIFY_SIGNATURES)
+    return _rectify
+
+
 def library_of(name: str) -> ctypes.CDLL:
     """The library that exports the entry `name`."""
+    if name in RECTIFY_SIGNATURES:
+        return load_rectify()
     if name in STEREO_SIGNATURES:
         return load_stereo()
     if name in FLOW_SIGNATURES:

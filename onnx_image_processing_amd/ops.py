@@ -2798,3 +2798,114 @@ def stereo_depth(disparity: torch.Tensor, fb: float, min_disparity: float = 0.5)
     depth = torch.empty((b, h, w), dtype=F32, device=d.device)
     N.call("mi_stereo_depth", d.data_ptr(), b, h, w, float(fb), float(min_disparity), depth.data_ptr(), N.stream_ptr())
     return depth.view(disparity.shape)
+
+
+# ---- K34 camera rectification (include/mi355x_match_rectify.h) ----------------------------------------------------------------
+
+RECTIFY_PINHOLE, RECTIFY_FISHEYE = N.RECTIFY_CONSTANTS["MI_RECTIFY_PINHOLE"], N.RECTIFY_CONSTANTS["MI_RECTIFY_FISHEYE"]
+RECTIFY_NEAREST, RECTIFY_LINEAR = N.RECTIFY_CONSTANTS["MI_RECTIFY_NEAREST"], N.RECTIFY_CONSTANTS["MI_RECTIFY_LINEAR"]
+RECTIFY_OUTSIDE, RECTIFY_SUBPIXEL_BITS = N.RECTIFY_CONSTANTS["MI_RECTIFY_OUTSIDE"], N.RECTIFY_CONSTANTS["MI_RECTIFY_SUBPIXEL_BITS"]
+RECTIFY_MAX_ITERATIONS, RECTIFY_MAX_DIM = N.RECTIFY_CONSTANTS["MI_RECTIFY_MAX_ITERATIONS"], N.RECTIFY_CONSTANTS["MI_RECTIFY_MAX_DIM"]
+RECTIFY_MODELS = {"pinhole": RECTIFY_PINHOLE, "fisheye": RECTIFY_FISHEYE}
+_RECTIFY_TYPES = {U8: N.RECTIFY_CONSTANTS["MI_RECTIFY_U8"], U16: N.RECTIFY_CONSTANTS["MI_RECTIFY_U16"], F32: N.RECTIFY_CONSTANTS["MI_RECTIFY_F32"]}
+
+
+def _rectify_doubles(values, count: int, what: str):
+    """a host array of `count` doubles for the C ABI from a tensor, an array or a nested list; None stays None (NULL)"""
+    if values is None:
+        return None
+    flat = torch.as_tensor(values, dtype=torch.float64, device="cpu").reshape(-1)
+    if flat.numel() != count:
+        raise ValueError(f"{what} must have {count} elements, got {flat.numel()}")
+    return (N.c_double * count)(*flat.tolist())
+
+
+def rectify_model(model) -> int:
+    """"pinhole" / "fisheye" or the constant itself -> RECTIFY_PINHOLE / RECTIFY_FISHEYE"""
+    if model in RECTIFY_MODELS:
+        return RECTIFY_MODELS[model]
+    if model in RECTIFY_MODELS.values() and not isinstance(model, str):
+        return int(model)
+    raise ValueError(f"model must be 'pinhole' or 'fisheye', got {model!r}")
+
+
+def rectify_coeffs(dist_coeffs, model: int):
+    """distortion coefficients as the entries take them: MI_RECTIFY_COEFFS doubles.  Pinhole: OpenCV's 4, 5 or 8
+    (k1 k2 p1 p2 [k3 [k4 k5 k6]]), None for none; fisheye: k1 .. k4.  The missing ones are 0."""
+    flat = [] if dist_coeffs is None else torch.as_tensor(dist_coeffs, dtype=torch.float64, device="cpu").reshape(-1).tolist()
+    legal = (0, 4, 5, 8) if model == RECTIFY_PINHOLE else (0, 4, 8)
+    if len(flat) not in legal:
+        raise ValueError(f"dist_coeffs must have one of {legal} elements for this model, got {len(flat)}")
+    return _rectify_doubles(flat + [0.0] * (8 - len(flat)), 8, "dist_coeffs")
+
+
+def rectify_map(camera_matrix, dist_coeffs, size, new_camera_matrix, out_size=None, rotation=None, model="pinhole", device="cuda",
+                want_mask: bool = True):
+    """`mi_rectify_map`: the sampling map of one camera, cv2.initUndistortRectifyMap's counterpart.  size = (height, width) of the
+    source frames, out_size that of the rectified ones (default: size); the cameras, coefficients and rotation are host values
+    (tensors, arrays or lists).  -> (map (h, w, 2) int32: source x, y in 1/32 pixel or RECTIFY_OUTSIDE; mask (h, w) uint8, 1
+    where every tap lies inside the source, or None with want_mask=False), on `device`."""
+    if torch.device(device).type != "cuda":
+        raise RuntimeError(f"rectify_map: the map must live on the GPU (got device {device}); this package has no CPU path")
+    m = rectify_model(model)
+    (sh, sw), (h, w) = (int(v) for v in size), (int(v) for v in (out_size or size))
+    out = torch.empty((max(h, 1), max(w, 1), 2), dtype=torch.int32, device=device)
+    mask = torch.empty((max(h, 1), max(w, 1)), dtype=U8, device=device) if want_mask else None
+    N.call("mi_rectify_map", m, _rectify_doubles(camera_matrix, 9, "camera_matrix"), rectify_coeffs(dist_coeffs, m),
+           _rectify_doubles(rotation, 9, "rotation"), _rectify_doubles(new_camera_matrix, 9, "new_camera_matrix"), sh, sw, h, w,
+           out.data_ptr(), None if mask is None else mask.data_ptr(), N.stream_ptr())
+    return out, mask
+
+
+def rectify_remap(frames: torch.Tensor, map: torch.Tensor, interpolation: int | None = None, border_value: float = 0.0) -> torch.Tensor:
+    """`mi_rectify_remap`: frames (B, H, W) or (B, 1, H, W), uint8, uint16 or float32, through one map (h, w, 2) int32 of
+    rectify_map -> (B, h, w) or (B, 1, h, w) of the same type, cv2.remap for a batch.  interpolation: RECTIFY_LINEAR (the
+    default for uint8 and float32) or RECTIFY_NEAREST (the default for uint16, which has no LINEAR: depth is not blended); a
+    tap outside the source reads border_value."""
+    src = _stereo_frames(frames, "rectify_remap: frames", (U8, U16, F32))
+    if not map.is_cuda:
+        raise RuntimeError(f"rectify_remap: map must live on the GPU (got device {map.device}); this package has no CPU path")
+    if map.dtype != torch.int32 or map.dim() != 3 or map.shape[2] != 2 or map.numel() == 0:
+        raise RuntimeError(f"rectify_remap: map must be (h, w, 2) int32, got {tuple(map.shape)} {map.dtype}")
+    mp = map.contiguous()
+    b, sh, sw = (int(v) for v in src.shape)
+    h, w = int(mp.shape[0]), int(mp.shape[1])
+    if interpolation is None:
+        interpolation = RECTIFY_NEAREST if src.dtype == U16 else RECTIFY_LINEAR
+    dst = torch.empty((b, h, w), dtype=src.dtype, device=src.device)
+    N.call("mi_rectify_remap", src.data_ptr(), _RECTIFY_TYPES[src.dtype], b, sh, sw, mp.data_ptr(), h, w, int(interpolation),
+           float(border_value), dst.data_ptr(), N.stream_ptr())
+    return dst.view(b, 1, h, w) if frames.dim() == 4 else dst
+
+
+def rectify_points(pts: torch.Tensor, camera_matrix, dist_coeffs, rotation=None, new_camera_matrix=None, model="pinhole",
+                   iterations: int = 10, max_residual_px: float = 0.5):
+    """`mi_rectify_points`: raw pixel coordinates (B, n, 2) float32 in (x, y) order -> (out (B, n, 2) float32, ok (B, n) bool),
+    cv2.undistortPoints for a batch.  out is normalised (x, y) after `rotation` when new_camera_matrix is None -- what the pose
+    estimators take --, else pixels of that camera; (0, 0) where ok is False (no undistorted point reproduces the input within
+    max_residual_px, a value is not finite, the point is behind the rectified camera, or beyond the fisheye model's limit)."""
+    if not pts.is_cuda:
+        raise RuntimeError(f"rectify_points: pts must live on the GPU (got device {pts.device}); this package has no CPU path")
+    if pts.dtype != F32 or pts.dim() != 3 or pts.shape[2] != 2 or pts.numel() == 0:
+        raise RuntimeError(f"rectify_points: pts must be (B, n, 2) float32, got {tuple(pts.shape)} {pts.dtype}")
+    m = rectify_model(model)
+    p = pts.contiguous()
+    b, n = int(p.shape[0]), int(p.shape[1])
+    out = torch.empty((b, n, 2), dtype=F32, device=p.device)
+    ok = torch.empty((b, n), dtype=U8, device=p.device)
+    N.call("mi_rectify_points", p.data_ptr(), b, n, m, _rectify_doubles(camera_matrix, 9, "camera_matrix"), rectify_coeffs(dist_coeffs, m),
+           _rectify_doubles(rotation, 9, "rotation"), _rectify_doubles(new_camera_matrix, 9, "new_camera_matrix"), int(iterations),
+           float(max_residual_px), out.data_ptr(), ok.data_ptr(), N.stream_ptr())
+    return out, ok.view(torch.bool)
+
+
+def rectify_stereo_rig(k1, k2, rotation, translation, size):
+    """`mi_rectify_stereo_rig` (host only, no GPU): two cameras with X2 = R X1 + t, camera 1 on the left, and the output size
+    (height, width) -> (r1, r2, k_new: (3, 3) float64 CPU tensors; baseline; fb = f * baseline, what stereo_depth wants),
+    cv2.stereoRectify without trigonometry.  Map the left camera with (k1, dist1, r1, k_new), the right with (k2, dist2, r2, k_new)."""
+    h, w = (int(v) for v in size)
+    r1, r2, k_new = ((N.c_double * 9)() for _ in range(3))
+    baseline, fb = N.c_double(), N.c_double()
+    N.call("mi_rectify_stereo_rig", _rectify_doubles(k1, 9, "k1"), _rectify_doubles(k2, 9, "k2"), _rectify_doubles(rotation, 9, "rotation"),
+           _rectify_doubles(translation, 3, "translation"), h, w, r1, r2, k_new, N.ctypes.byref(baseline), N.ctypes.byref(fb))
+    return tuple(torch.tensor(list(a), dtype=torch.float64).view(3, 3) for a in (r1, r2, k_new)) + (baseline.value, fb.value)

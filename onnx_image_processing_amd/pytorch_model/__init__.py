@@ -9,4 +9,6 @@ reference: they are its hosts' OpenCV steps (pose from matches; colour frame to 
 relocalisation are open boxes of the reference's roadmap.  `tracking` (FeatureTracker: pyramidal Lucas-Kanade between two
 frames) has none: the reference's hosts call OpenCV for it.  `stereo` (StereoMatcher: a rectified pair to disparity and depth by
 census and semi-global matching) has none either: the reference's OAK-D back end uses the camera's own stereo engine.
+`calibration` (Undistorter, StereoRectifier: lens undistortion and stereo rectification of frames and keypoints) has none: the
+reference keeps fx, fy, cx, cy of a camera and drops its distortion coefficients.
 """

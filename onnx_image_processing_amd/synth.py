@@ -886,3 +886,91 @@ def synth_stereo_pair(seed: int, height: int, width: int, d_background: float = 
     if quantise:
         return left.astype(np.uint8), np.rint(right).astype(np.uint8), disp.astype(np.float32), visible
     return left.astype(np.float32), right.astype(np.float32), disp.astype(np.float32), visible
+
+
+def synth_distorted_rig(seed: int, height: int, width: int, model: str = "pinhole", disparity: float = 12.0, terms: int = 48,
+                        lam=(3.0, 24.0), quantise: bool = False):
+    """The raw left and right views of a textured plane as a stereo rig with real lenses sees it: two cameras with lens
+    distortion (`model` "pinhole": radial-tangential, or "fisheye": Kannala-Brandt; different coefficients per camera) and a
+    small relative rotation.  The plane is fronto-parallel in the RECTIFIED frame of the rig (x along the baseline, z the mean
+    optical axis made orthogonal to it), at the depth where the rectified disparity is `disparity` pixels everywhere; its
+    texture is a smooth band-limited sum of `terms` sinusoids with wavelengths lam[0] .. lam[1] in rectified pixels.  Each raw
+    pixel is rendered exactly, without resampling: its ray comes from the inverse lens model (iterated to convergence in
+    float64), meets the plane, and the texture is evaluated there.  Returns (left, right, rig): the views (height, width)
+    float32 in [0, 255], or rounded to uint8 with `quantise`, and rig = dict(k1, d1, k2, d2, R, T: X2 = R X1 + T; model;
+    disparity; depth: the plane's depth in T's unit; focal: the rectified focal length (fy1 + fy2) / 2; baseline).
+    Deterministic in `seed`."""
+    if height < 1 or width < 1 or model not in ("pinhole", "fisheye") or not disparity > 0 or terms < 1 or not 0 < lam[0] <= lam[1]:
+        raise ValueError("synth_distorted_rig: height, width, terms >= 1, model 'pinhole' or 'fisheye', disparity > 0, 0 < lam[0] <= lam[1]")
+    rng = np.random.default_rng(seed)
+    wavelength = np.exp(rng.uniform(np.log(lam[0]), np.log(lam[1]), terms))
+    theta, phi = rng.uniform(0.0, 2.0 * np.pi, terms), rng.uniform(0.0, 2.0 * np.pi, terms)
+    wx, wy = np.cos(theta) / wavelength, np.sin(theta) / wavelength
+    amp = np.sqrt(wavelength)
+    amp *= 110.0 / amp.sum()
+
+    def texture(x, y):
+        out = np.full(x.shape, 128.0)
+        for m in range(terms):
+            out += amp[m] * np.sin(2.0 * np.pi * (wx[m] * x + wy[m] * y) + phi[m])
+        return out
+
+    f1, f2 = 0.9 * width, 0.92 * width
+    k1 = np.array([[f1, 0.0, (width - 1) / 2.0 + 1.5], [0.0, f1, (height - 1) / 2.0 - 1.0], [0.0, 0.0, 1.0]])
+    k2 = np.array([[f2, 0.0, (width - 1) / 2.0 - 2.0], [0.0, f2, (height - 1) / 2.0 + 0.5], [0.0, 0.0, 1.0]])
+    if model == "pinhole":
+        d1 = np.array([-0.27, 0.08, 0.0012, -0.0015, -0.01, 0.0, 0.0, 0.0])
+        d2 = np.array([-0.22, 0.05, -0.0010, 0.0008, 0.0, 0.0, 0.0, 0.0])
+    else:
+        d1 = np.array([-0.035, 0.006, -0.001, 0.0, 0.0, 0.0, 0.0, 0.0])
+        d2 = np.array([-0.020, 0.003, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0])
+    ax, ay, az = 0.02, -0.03, 0.015
+    rot = (np.array([[np.cos(az), -np.sin(az), 0.0], [np.sin(az), np.cos(az), 0.0], [0.0, 0.0, 1.0]]) @
+           np.array([[np.cos(ay), 0.0, np.sin(ay)], [0.0, 1.0, 0.0], [-np.sin(ay), 0.0, np.cos(ay)]]) @
+           np.array([[1.0, 0.0, 0.0], [0.0, np.cos(ax), -np.sin(ax)], [0.0, np.sin(ax), np.cos(ax)]]))
+    centre2 = np.array([0.1, 0.003, -0.002])                                 # camera 2 in camera 1's frame
+    t = -rot @ centre2
+    baseline = float(np.linalg.norm(t))
+    # the rectified frame (include/mi355x_match_rectify.h, "Stereo rig")
+    x_axis = centre2 / baseline
+    y_axis = np.cross(np.array([0.0, 0.0, 1.0]) + rot.T @ np.array([0.0, 0.0, 1.0]), x_axis)
+    y_axis /= np.linalg.norm(y_axis)
+    r1 = np.stack([x_axis, y_axis, np.cross(x_axis, y_axis)])
+    r2 = r1 @ rot.T
+    focal = (k1[1, 1] + k2[1, 1]) / 2.0
+    depth = focal * baseline / disparity
+
+    def rays(k, d):
+        """the normalised undistorted coordinates of every raw pixel"""
+        v, u = np.mgrid[0:height, 0:width].astype(np.float64)
+        xd, yd = (u - k[0, 2]) / k[0, 0], (v - k[1, 2]) / k[1, 1]
+        if model == "fisheye":
+            thd = np.sqrt(xd * xd + yd * yd)
+            th = thd.copy()
+            for _ in range(30):
+                t2 = th * th
+                th = th - (th * (1 + t2 * (d[0] + t2 * (d[1] + t2 * (d[2] + t2 * d[3])))) - thd) / \
+                    (1 + t2 * (3 * d[0] + t2 * (5 * d[1] + t2 * (7 * d[2] + t2 * 9 * d[3]))))
+            s = np.where(thd > 0, np.tan(th) / np.where(thd > 0, thd, 1.0), 1.0)
+            return xd * s, yd * s
+        x, y = xd.copy(), yd.copy()
+        for _ in range(60):
+            r2_ = x * x + y * y
+            icd = (1 + r2_ * (d[5] + r2_ * (d[6] + r2_ * d[7]))) / (1 + r2_ * (d[0] + r2_ * (d[1] + r2_ * d[4])))
+            a = 2 * x * y
+            x, y = (xd - (d[2] * a + d[3] * (r2_ + 2 * x * x))) * icd, (yd - (d[2] * (r2_ + 2 * y * y) + d[3] * a)) * icd
+        return x, y
+
+    def view(k, d, r_rect, origin_x):
+        x, y = rays(k, d)
+        dx, dy, dz = (r_rect[i, 0] * x + r_rect[i, 1] * y + r_rect[i, 2] for i in range(3))
+        s = depth / dz
+        px, py = origin_x + s * dx, s * dy                                    # the point of the plane, in the rectified frame
+        return np.clip(texture(focal * px / depth, focal * py / depth), 0.0, 255.0)
+
+    left, right = view(k1, d1, r1, 0.0), view(k2, d2, r2, baseline)
+    rig = dict(k1=k1, d1=d1, k2=k2, d2=d2, R=rot, T=t, model=model, disparity=float(disparity), depth=float(depth), focal=float(focal),
+               baseline=baseline)
+    if quantise:
+        return np.rint(left).astype(np.uint8), np.rint(right).astype(np.uint8), rig
+    return left.astype(np.float32), right.astype(np.float32), rig
