@@ -26,7 +26,8 @@ extern "C" {
  *
  * The inputs are RECTIFIED: a scene point lies on the same row of both views, at x_right = x_left - d with d >= 0.
  * Undistortion and rectification are the K34 section's (include/mi355x_match_rectify.h: mi_rectify_stereo_rig, mi_rectify_map,
- * mi_rectify_remap); speckle and median post-filters are not part of the library.
+ * mi_rectify_remap); the speckle and median post-filters are the K35 section's (include/mi355x_match_filter.h: mi_filter_speckle,
+ * mi_filter_median), applied to the disparity this section writes.
  *
  * Census.  gray is (batch, h, w), uint8 or float32 (the two outputs of mi_ingest_frames); census is (batch, h, w) uint64.
  *   The window is 9 wide and 7 high.  Bit k of pixel (y, x) belongs to the k-th offset (dy, dx), dy = -3 .. 3 outer,

@@ -128,6 +128,10 @@ RESTYPES.update(_stereo_restypes)
 # load_rectify(), RECTIFY_CONSTANTS["MI_RECTIFY_OUTSIDE"], ...
 RECTIFY_SIGNATURES, _rectify_restypes, _, RECTIFY_CONSTANTS = _read("mi355x_match_rectify.h")
 RESTYPES.update(_rectify_restypes)
+# include/mi355x_match_filter.h: the disparity post-filter section (K35), laid out as K30's: lib/libmi355x_match_filter.so,
+# load_filter(), FILTER_CONSTANTS["MI_FILTER_SPECKLE"], ...
+FILTER_SIGNATURES, _filter_restypes, _, FILTER_CONSTANTS = _read("mi355x_match_filter.h")
+RESTYPES.update(_filter_restypes)
 
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_debug.so")
 SIM3_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_sim3.so")
@@ -135,6 +139,7 @@ SIMGRAPH_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_simgraph.so")
 FLOW_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_flow.so")
 STEREO_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_stereo.so")
 RECTIFY_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_rectify.so")
+FILTER_LIB_PATH = os.path.join(_PKG, "lib", "libmi355x_match_filter.so")
 
 _lib = None            # the library every call() goes through: the product, unless inside debug_library()
 _product = None
@@ -221,8 +226,21 @@ def load_rectify() -> ctypes.CDLL:
     return _rectify
 
 
+_filter = None
+
+
+def load_filter() -> ctypes.CDLL:
+    """lib/libmi355x_match_filter.so, the entries of include/mi355x_match_filter.h, loaded once."""
+    global _filter
+    if _filter is None:
+        _filter = _open(FILTER_LIB_PATH, FILTER_SIGNATURES)
+    return _filter
+
+
 def library_of(name: str) -> ctypes.CDLL:
     """The library that exports the entry `name`."""
+    if name in FILTER_SIGNATURES:
+        return load_filter()
     if name in RECTIFY_SIGNATURES:
         return load_rectify()
     if name in STEREO_SIGNATURES:

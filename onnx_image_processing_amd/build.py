@@ -7,7 +7,8 @@ exactly include/mi355x_match.h --, lib/libmi355x_match_sim3.so (the similarity-a
 lib/libmi355x_match_simgraph.so (the similarity pose-graph section, include/mi355x_match_simgraph.h),
 lib/libmi355x_match_flow.so (the feature-tracking section, include/mi355x_match_flow.h),
 lib/libmi355x_match_stereo.so (the stereo-depth section, include/mi355x_match_stereo.h),
-lib/libmi355x_match_rectify.so (the camera-rectification section, include/mi355x_match_rectify.h)
+lib/libmi355x_match_rectify.so (the camera-rectification section, include/mi355x_match_rectify.h),
+lib/libmi355x_match_filter.so (the disparity post-filter section, include/mi355x_match_filter.h)
 and lib/libmi355x_match_debug.so (the product's ABI plus the kernel-variant test hooks of
 include/mi355x_match_debug.h; tests/ and tools/ only).  All are git-ignored and travel to the GPU box with the working
 tree.  Objects are rebuilt only when a source or header is newer.
@@ -49,6 +50,9 @@ STEREO_SOURCES = ["stereo.hip"]
 # ... and K34's: lib/libmi355x_match_rectify.so exports exactly include/mi355x_match_rectify.h
 RECTIFY_LIB = os.path.join(LIBDIR, "libmi355x_match_rectify.so")
 RECTIFY_SOURCES = ["rectify.hip"]
+# ... and K35's: lib/libmi355x_match_filter.so exports exactly include/mi355x_match_filter.h
+FILTER_LIB = os.path.join(LIBDIR, "libmi355x_match_filter.so")
+FILTER_SOURCES = ["filter.hip"]
 # -ffp-contract=off: the corner response must not fuse a*b+c (bit parity with the reference's
 # op-by-op fp32); IEEE sqrt/div are hipcc's defaults and are relied upon.
 # -fvisibility=hidden: only the MI_API declarations of include/*.h are exported (no C++-mangled internals).
@@ -111,6 +115,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     flow_objs = [want(src, "", []) for src in FLOW_SOURCES]
     stereo_objs = [want(src, "", []) for src in STEREO_SOURCES]
     rectify_objs = [want(src, "", []) for src in RECTIFY_SOURCES]
+    filter_objs = [want(src, "", []) for src in FILTER_SOURCES]
 
     def run(cmd):
         if verbose:
@@ -125,10 +130,11 @@ def build(force: bool = False, verbose: bool = True) -> str:
         list(ex.map(run, jobs))
     # Link to a temporary name and rename onto the final path: a process that waits for the library to appear (bench.py's
     # other ranks, a concurrent test run) must never dlopen a file the linker is still writing.  The debug library is
-    # linked FIRST, and the section libraries (K30 to K34) before the product, so that the product library's appearance means
+    # linked FIRST, and the section libraries (K30 to K35) before the product, so that the product library's appearance means
     # every library is complete.
     for lib, members in ((DEBUG_LIB, debug_objs), (SIM3_LIB, sim3_objs), (SIMGRAPH_LIB, simgraph_objs),
-                         (FLOW_LIB, flow_objs), (STEREO_LIB, stereo_objs), (RECTIFY_LIB, rectify_objs), (LIB, objs)):
+                         (FLOW_LIB, flow_objs), (STEREO_LIB, stereo_objs), (RECTIFY_LIB, rectify_objs),
+                         (FILTER_LIB, filter_objs), (LIB, objs)):
         if jobs or force or _newer(lib, members + link_deps):
             tmp = f"{lib}.{os.getpid()}.tmp"
             try:

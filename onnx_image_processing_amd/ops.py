@@ -2909,3 +2909,52 @@ def rectify_stereo_rig(k1, k2, rotation, translation, size):
     N.call("mi_rectify_stereo_rig", _rectify_doubles(k1, 9, "k1"), _rectify_doubles(k2, 9, "k2"), _rectify_doubles(rotation, 9, "rotation"),
            _rectify_doubles(translation, 3, "translation"), h, w, r1, r2, k_new, N.ctypes.byref(baseline), N.ctypes.byref(fb))
     return tuple(torch.tensor(list(a), dtype=torch.float64).view(3, 3) for a in (r1, r2, k_new)) + (baseline.value, fb.value)
+
+
+# ---- K35 disparity post-filters (include/mi355x_match_filter.h) ---------------------------------------------------------------
+
+FILTER_SPECKLE, FILTER_NO_LABEL = N.FILTER_CONSTANTS["MI_FILTER_SPECKLE"], N.FILTER_CONSTANTS["MI_FILTER_NO_LABEL"]
+FILTER_MEDIANS = (3, 5)
+_FILTER_TYPES = {U8: N.FILTER_CONSTANTS["MI_FILTER_U8"], F32: N.FILTER_CONSTANTS["MI_FILTER_F32"]}
+
+
+def filter_components(values: torch.Tensor, min_valid: float, max_diff: float, want_sizes: bool = True):
+    """`mi_filter_components`: frames (B, H, W) or (B, 1, H, W), uint8 (a class map) or float32 -> (labels int32 of the same shape:
+    the smallest y * W + x of the pixel's 4-connected component, FILTER_NO_LABEL on an invalid pixel; sizes int32: the pixel count
+    of its component, 0 on an invalid pixel, or None with want_sizes=False).  A pixel is valid iff value >= min_valid; two
+    neighbours are joined iff both are valid and |a - b| <= max_diff."""
+    v = _stereo_frames(values, "filter_components: values", (U8, F32))
+    b, h, w = (int(x) for x in v.shape)
+    labels = torch.empty((b, h, w), dtype=I32, device=v.device)
+    sizes = torch.empty((b, h, w), dtype=I32, device=v.device) if want_sizes else None
+    work, wbytes = _workspace("mi_filter_workspace_bytes", b, h, w, device=v.device,
+                              refusal=f"filter_components: {b} frames of {h} x {w} are outside what mi_filter_components covers")
+    N.call("mi_filter_components", v.data_ptr(), _FILTER_TYPES[v.dtype], b, h, w, float(min_valid), float(max_diff), labels.data_ptr(),
+           None if sizes is None else sizes.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    return labels.view(values.shape), None if sizes is None else sizes.view(values.shape)
+
+
+def filter_speckle(x: torch.Tensor, max_size: int, max_diff: float, min_valid: float = 0.0, invalid_value: float = -1.0,
+                   want_removed: bool = False):
+    """`mi_filter_speckle`: float32 frames (B, H, W) or (B, 1, H, W) -> the frames with every component of at most max_size
+    pixels, and every invalid pixel, set to invalid_value (cv2.filterSpeckles on float disparities); with want_removed also the
+    byte map of the VALID pixels that were dropped.  For depth frames: min_valid = min_depth, invalid_value = 0.0."""
+    v = _stereo_frames(x, "filter_speckle: x", (F32,))
+    b, h, w = (int(s) for s in v.shape)
+    out = torch.empty((b, h, w), dtype=F32, device=v.device)
+    removed = torch.empty((b, h, w), dtype=U8, device=v.device) if want_removed else None
+    work, wbytes = _workspace("mi_filter_workspace_bytes", b, h, w, device=v.device,
+                              refusal=f"filter_speckle: {b} frames of {h} x {w} are outside what mi_filter_speckle covers")
+    N.call("mi_filter_speckle", v.data_ptr(), b, h, w, float(min_valid), float(max_diff), int(max_size), float(invalid_value), out.data_ptr(),
+           None if removed is None else removed.data_ptr(), work.data_ptr(), wbytes, N.stream_ptr())
+    return (out.view(x.shape), removed.view(x.shape)) if want_removed else out.view(x.shape)
+
+
+def filter_median(x: torch.Tensor, k: int = 3, min_valid: float = 0.0, invalid_value: float = -1.0) -> torch.Tensor:
+    """`mi_filter_median`: float32 frames (B, H, W) or (B, 1, H, W) -> the k x k (3 or 5) median over the VALID taps of the
+    window (replicate border), invalid_value where the centre is invalid: it does not fill holes."""
+    v = _stereo_frames(x, "filter_median: x", (F32,))
+    b, h, w = (int(s) for s in v.shape)
+    out = torch.empty((b, h, w), dtype=F32, device=v.device)
+    N.call("mi_filter_median", v.data_ptr(), b, h, w, int(k), float(min_valid), float(invalid_value), out.data_ptr(), N.stream_ptr())
+    return out.view(x.shape)

@@ -8,7 +8,8 @@ reference: they are its hosts' OpenCV steps (pose from matches; colour frame to 
 `retrieval` (KeyframeDatabase: which stored keyframe is this frame?) has none either: loop closure detection and
 relocalisation are open boxes of the reference's roadmap.  `tracking` (FeatureTracker: pyramidal Lucas-Kanade between two
 frames) has none: the reference's hosts call OpenCV for it.  `stereo` (StereoMatcher: a rectified pair to disparity and depth by
-census and semi-global matching) has none either: the reference's OAK-D back end uses the camera's own stereo engine.
+census and semi-global matching; DisparityFilter: its speckle and median post-filters) has none either: the reference's OAK-D back
+end uses the camera's own stereo engine.
 `calibration` (Undistorter, StereoRectifier: lens undistortion and stereo rectification of frames and keypoints) has none: the
 reference keeps fx, fy, cx, cy of a camera and drops its distortion coefficients.
 """

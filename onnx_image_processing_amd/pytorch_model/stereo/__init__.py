@@ -1,3 +1,4 @@
+from .disparity_filter import DisparityFilter
 from .stereo_matcher import StereoMatcher
 
-__all__ = ["StereoMatcher"]
+__all__ = ["StereoMatcher", "DisparityFilter"]

@@ -7,6 +7,7 @@ import torch
 from torch import nn
 
 from ... import ops
+from .disparity_filter import DisparityFilter
 
 
 class StereoMatcher(nn.Module):
@@ -16,10 +17,12 @@ class StereoMatcher(nn.Module):
     ops.STEREO_NOT_UNIQUE or ops.STEREO_LR.  uniqueness = 0 and lr_max_diff < 0 turn the two tests off.
     depth(disparity, fx, baseline, min_disparity=0.5) -> fx * baseline / disparity in the baseline's unit, 0 where the
     disparity is below min_disparity (rejected pixels among them): the frame DepthToPointCloud, TsdfVolume.integrate and the
-    RGB-D estimators read."""
+    RGB-D estimators read.
+    speckle_size, speckle_range, median: DisparityFilter's arguments (K35), off by default; with one of them on, forward applies
+    the filter to its result and code is ops.FILTER_SPECKLE on a pixel the speckle filter dropped."""
 
     def __init__(self, max_disparity: int = 128, p1: int = 10, p2: int = 120, paths: int = 8, uniqueness: int = 10,
-                 lr_max_diff: int = 1) -> None:
+                 lr_max_diff: int = 1, speckle_size: int = 0, speckle_range: float = 1.0, median: int = 0) -> None:
         super().__init__()
         if max_disparity not in ops.STEREO_DISPARITIES:
             raise ValueError(f"max_disparity must be one of {ops.STEREO_DISPARITIES}, got {max_disparity}")
@@ -31,6 +34,7 @@ class StereoMatcher(nn.Module):
             raise ValueError(f"uniqueness must be in 0 .. 100, got {uniqueness}")
         self.max_disparity, self.p1, self.p2, self.paths = int(max_disparity), int(p1), int(p2), int(paths)
         self.uniqueness, self.lr_max_diff = int(uniqueness), int(lr_max_diff)
+        self.filter = DisparityFilter(speckle_size, speckle_range, median)
 
     @torch.no_grad()
     def volume(self, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
@@ -42,6 +46,8 @@ class StereoMatcher(nn.Module):
         if left.shape != right.shape:
             raise RuntimeError(f"the two views differ in shape: {tuple(left.shape)} and {tuple(right.shape)}")
         disparity, _, code = ops.stereo_select(self.volume(left, right), self.uniqueness, self.lr_max_diff, want_right=self.lr_max_diff >= 0)
+        if self.filter.active:
+            disparity, code = self.filter(disparity, code)
         return disparity.view(left.shape), code.view(left.shape)
 
     @torch.no_grad()

@@ -974,3 +974,20 @@ def synth_distorted_rig(seed: int, height: int, width: int, model: str = "pinhol
     if quantise:
         return np.rint(left).astype(np.uint8), np.rint(right).astype(np.uint8), rig
     return left.astype(np.float32), right.astype(np.float32), rig
+
+
+def synth_textureless_pair(seed: int, height: int = 40, width: int = 160):
+    """synth_stereo_pair(seed, height, width) in float32 with a textureless patch painted over the first 8 rows: left[0:8, 70:150]
+    and right[0:8, 66:146] (the same surface at the background's disparity 4) are 128 plus uniform noise of +-1 gray level, from
+    two draws of numpy.random.default_rng(1000 + seed).  On such a surface the census bits are noise and the matcher accepts
+    small blobs of wrong disparities: what the speckle filter (K35) is for.  Returns (left, right, disparity, visible, patch
+    (height, width) bool: the patch in the left view).  Needs height >= 8 and width >= 150."""
+    if height < 8 or width < 150:
+        raise ValueError("synth_textureless_pair: height >= 8 and width >= 150")
+    left, right, disp, visible = synth_stereo_pair(seed, height, width)
+    rng = np.random.default_rng(1000 + seed)
+    left[0:8, 70:150] = (128.0 + rng.uniform(-1.0, 1.0, (8, 80))).astype(np.float32)
+    right[0:8, 66:146] = (128.0 + rng.uniform(-1.0, 1.0, (8, 80))).astype(np.float32)
+    patch = np.zeros((height, width), bool)
+    patch[0:8, 70:150] = True
+    return left, right, disp, visible, patch

@@ -21,6 +21,7 @@ MI355X implementation (the very same module objects, not copies):
     from pytorch_model.geometry import SimilarityGraphOptimizer         (no counterpart in the reference: 7-DoF loop closing)
     from pytorch_model.tracking import FeatureTracker                   (no counterpart in the reference: KLT tracking, its hosts' cv2 step)
     from pytorch_model.stereo import StereoMatcher                      (no counterpart in the reference: a stereo rig's depth, cv2.StereoSGBM)
+    from pytorch_model.stereo import DisparityFilter                    (no counterpart in the reference: cv2.filterSpeckles, cv2.medianBlur on disparities)
     from pytorch_model.calibration import Undistorter, StereoRectifier  (no counterpart in the reference: cv2.remap, cv2.undistortPoints, cv2.stereoRectify)
 
 The one sub-package outside the mirrored set (`vo`, host-side numpy / OpenCV and camera drivers) does not
